@@ -6,10 +6,13 @@ k-space, normalization 'coil', L2, lr 3e-5, batch 25 000 coordinates per GPU.  O
 fused encode->forward->loss->backward kernel + slab reduction (+ RCCL all-reduce of the 1.3 MB
 gradient when N>1) + Adam/re-pack kernel, on sequential batches resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  Data is synthetic (seeded phantom), weights are random-init.
+Prints ONE JSON line on rank 0.  Data is synthetic (seeded phantom), weights are random-init.  A plain run sets up, warms
+up, times the K steps and prints the headline; --full adds the roofline and per-kernel timings, the PSNR read-out, the CPU
+baseline, batch 65 536, the bf16 path, config 5 and config 4.  --dump-outputs writes what the last timed step left to
+its caller (loss, parameters, gradient, Adam moments) as DIR/<name>.npy, before anything of --full runs.
 """
 import argparse
 import json
@@ -420,6 +423,18 @@ def multiscale_config4(dev, rank, world, pg, steps, warmup, barrier):
             "update": "sharded (reduce-scatter, Adam on 1/N, all-gather, re-pack)" if tr.sharded_update else "replicated"}
 
 
+def dump_outputs(d: str, tr, loss) -> None:
+    """What the timed step hands its caller: the loss it returned and the engine state it left (flat parameters,
+    gradient, Adam moments), float32, one .npy per array (4 x 1.3 MB for SIREN 5x256)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    eng = tr.engine
+    arrays = {"loss": loss, "params": eng.params, "grads": eng.grads, "exp_avg": eng.exp_avg,
+              "exp_avg_sq": eng.exp_avg_sq}
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -438,6 +453,11 @@ def main():
     ap.add_argument("--graph", type=int, default=0,
                     help="N=1: replay each batch's step as one captured HIP graph.  Off by default: measured slower "
                          "than eager launches on this stack (profiles/r02g_graph_vs_eager.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline and per-kernel timings, PSNR read-out, CPU baseline, batch 65 536, "
+                         "bf16 path, config 5 and config 4 objects (the --no-* and --psnr-steps options act on these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's loss, parameters, gradient and Adam moments as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -509,7 +529,7 @@ def main():
     for i in range(args.steps):
         evs[i].record()
         s_ = args.warmup + i
-        tr.step(s_ // spe, s_ % spe)
+        loss = tr.step(s_ // spe, s_ % spe)
     evs[args.steps].record()
     barrier()
     dt = time.perf_counter() - t0
@@ -524,6 +544,24 @@ def main():
         it = (args.warmup + i) % spe
         rows += min((it + 1) * tr.bs, tr.n) - it * tr.bs
     value = rows / dt
+    if rank == 0 and args.dump_outputs:  # before --full's objects: they launch more steps on the same engine
+        dump_outputs(args.dump_outputs, tr, loss)
+
+    out = {
+        "metric": "coord-samples/sec (fwd+bwd) fitting 640x368x15-coil k-space; PSNR@1k steps",
+        "value": value, "unit": "coord-samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "step_ms": {"min": min(step_ev), "median": sorted(step_ev)[len(step_ev) // 2], "max": max(step_ev),
+                    "first": step_ev[0], "event_sum_per_step": sum(step_ev) / len(step_ev),
+                    "note": "device time of each timed step between HIP events on the launch stream (rank 0); ms_per_step is "
+                            "wall clock / steps over the same window, barrier to barrier",
+                    "prewarm_ms": prewarm_ms, "prewarm_launches": n_pw},
+        "config": {"workload": "SIREN 5x256 gauss-512 k-space fit, synthetic 640x368x15-coil, L2, Adam",
+                   "batch_per_gpu": args.batch, "global_batch": args.batch * world,
+                   "parallelism": f"dp{world}" if world > 1 else "single",
+                   "launch": "hip-graph per batch" if tr.graph_steps else "eager"},
+    }
 
     # ---- roofline of the dominant kernel (the fused MLP kernel), HIP events on the launch stream
     eng = tr.engine
@@ -580,47 +618,32 @@ def main():
                     f"{info.hi}/{info.lo} column blocks of 16 coordinates; v_mfma_f32_16x16x4_f32)")
         return f"inr_mlp_kernel<8,GAUSS,SIN,FUSED> ({info.grid} workgroups x {info.rounds} round(s) of 128-coordinate tiles; v_mfma_f32_32x32x2_f32)"
 
-    k_ms = fused_kernel_ms(args.batch)
-    achieved = FLOP_FUSED_F32 * args.batch / (k_ms * 1e-3) / 1e12
-    p_ms = gradient_path_ms(args.batch)
-    p_ach = FLOP_PER_SAMPLE * args.batch / (p_ms * 1e-3) / 1e12
-    # HBM bytes per launch come from separate rocprofv3 --pmc passes (cannot be collected from inside
-    # this process); the committed summary applies only to the workload it was measured on.
-    traffic = None
-    try:
-        tj = json.load(open(os.path.join(ROOT, "profiles", "traffic_latest.json")))
-        if args.batch == 25000 and tj["kernel"].split("<")[0] == fused_kernel_name(args.batch).split("<")[0]:
-            traffic = tj["bytes_per_launch"]  # (only if the summary was taken on the kernel this run launches)
-    except (OSError, ValueError, KeyError):
-        pass
-
-    out = {
-        "metric": "coord-samples/sec (fwd+bwd) fitting 640x368x15-coil k-space; PSNR@1k steps",
-        "value": value, "unit": "coord-samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "step_ms": {"min": min(step_ev), "median": sorted(step_ev)[len(step_ev) // 2], "max": max(step_ev),
-                    "first": step_ev[0], "event_sum_per_step": sum(step_ev) / len(step_ev),
-                    "note": "device time of each timed step between HIP events on the launch stream (rank 0); ms_per_step is "
-                            "wall clock / steps over the same window, barrier to barrier",
-                    "prewarm_ms": prewarm_ms, "prewarm_launches": n_pw},
-        "config": {"workload": "SIREN 5x256 gauss-512 k-space fit, synthetic 640x368x15-coil, L2, Adam",
-                   "batch_per_gpu": args.batch, "global_batch": args.batch * world,
-                   "parallelism": f"dp{world}" if world > 1 else "single",
-                   "launch": "hip-graph per batch" if tr.graph_steps else "eager"},
-        "roofline": {"bound": "mfma", "kernel": fused_kernel_name(args.batch), "achieved": achieved,
-                     "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / F32_MFMA_PEAK_TFLOPS,
-                     "kernel_ms": k_ms, "flop_per_sample": FLOP_FUSED_F32, "traffic": traffic,
-                     "traffic_source": "profiles/traffic_latest.json: HBM bytes per launch from separate rocprofv3 --pmc "
-                                       "passes of this workload (FETCH_SIZE x 2 + WRITE_SIZE), committed with the round's "
-                                       "profiles -- not measured by this run",
-                     "note": "exact-fp32 path (fp32-input MFMA); peak = dense f32 MFMA. This kernel: encoder, "
-                             "forward, loss, dX and the last layer's dW; dW of the 256-row layers is dw_gemm_kernel",
-                     "gradient_path": {"kernels": "fused kernel + dw_gemm_kernel<128> + reduce_slabs_real_kernel",
-                                       "ms": p_ms, "flop_per_sample": FLOP_PER_SAMPLE, "achieved": p_ach,
-                                       "frac": p_ach / F32_MFMA_PEAK_TFLOPS}},
-    }
-    if world == 1 and rank == 0:
+    if args.full:
+        k_ms = fused_kernel_ms(args.batch)
+        achieved = FLOP_FUSED_F32 * args.batch / (k_ms * 1e-3) / 1e12
+        p_ms = gradient_path_ms(args.batch)
+        p_ach = FLOP_PER_SAMPLE * args.batch / (p_ms * 1e-3) / 1e12
+        # HBM bytes per launch come from separate rocprofv3 --pmc passes (cannot be collected from inside
+        # this process); the committed summary applies only to the workload it was measured on.
+        traffic = None
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", "traffic_latest.json")))
+            if args.batch == 25000 and tj["kernel"].split("<")[0] == fused_kernel_name(args.batch).split("<")[0]:
+                traffic = tj["bytes_per_launch"]  # (only if the summary was taken on the kernel this run launches)
+        except (OSError, ValueError, KeyError):
+            pass
+        out["roofline"] = {"bound": "mfma", "kernel": fused_kernel_name(args.batch), "achieved": achieved,
+                           "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / F32_MFMA_PEAK_TFLOPS,
+                           "kernel_ms": k_ms, "flop_per_sample": FLOP_FUSED_F32, "traffic": traffic,
+                           "traffic_source": "profiles/traffic_latest.json: HBM bytes per launch from separate rocprofv3 "
+                                             "--pmc passes of this workload (FETCH_SIZE x 2 + WRITE_SIZE), committed with "
+                                             "the round's profiles -- not measured by this run",
+                           "note": "exact-fp32 path (fp32-input MFMA); peak = dense f32 MFMA. This kernel: encoder, "
+                                   "forward, loss, dX and the last layer's dW; dW of the 256-row layers is dw_gemm_kernel",
+                           "gradient_path": {"kernels": "fused kernel + dw_gemm_kernel<128> + reduce_slabs_real_kernel",
+                                             "ms": p_ms, "flop_per_sample": FLOP_PER_SAMPLE, "achieved": p_ach,
+                                             "frac": p_ach / F32_MFMA_PEAK_TFLOPS}}
+    if args.full and world == 1 and rank == 0:
         done = args.warmup + args.steps
         reads, coil_steps = ([], [])
         if args.psnr_steps and args.psnr_steps > done:
@@ -652,7 +675,7 @@ def main():
                 out["psnr_at_1k_steps"]["last_epoch_reference"] = psnr_summary(ref_reads, coil_steps)
                 out["_ref_reads"] = ref_reads
                 out["_coil_steps"] = coil_steps
-    if world == 1 and rank == 0 and args.batch != 65536:  # after the PSNR read-out: these steps keep fitting
+    if args.full and world == 1 and rank == 0 and args.batch != 65536:  # after the PSNR read-out: these steps keep fitting
         # SURVEY.md 8(d) / north-star point: the same kernel and the same whole step at 65 536 coordinates
         # (2048 wave tiles = two full rounds of the chip's 1024 SIMDs, no tail)
         nsb = 65536
@@ -688,15 +711,15 @@ def main():
             traceback.print_exc(file=sys.stderr)
             return {"error": f"{name}: {type(e).__name__}: {e}"}
 
-    if world == 1 and rank == 0 and not args.no_bf16:
+    if args.full and world == 1 and rank == 0 and not args.no_bf16:
         out["bf16_path"] = secondary("bf16_path", lambda: bf16_path(cfg, image, coords, shape, dev, args, fused_kernel_ms_of, out))
         ref = out.get("cpu_baseline", {}).get("reference_psnr")
         if ref is not None and "psnr_at_1k_steps" in out["bf16_path"]:
             out["bf16_path"]["psnr_at_1k_steps"]["delta_vs_reference_db"] = (
                 out["bf16_path"]["psnr_at_1k_steps"]["psnr_db"] - ref["psnr_db"])
-    if world == 1 and rank == 0 and not args.no_config5:
+    if args.full and world == 1 and rank == 0 and not args.no_config5:
         out["config5_percoil_tv"] = secondary("config5_percoil_tv", lambda: config5_percoil(dev))
-    if not args.no_multiscale:  # every rank takes part (strong scaling over the world)
+    if args.full and not args.no_multiscale:  # every rank takes part (strong scaling over the world)
         ms = secondary("multiscale_config4", lambda: multiscale_config4(dev, rank, world, pg, args.ms_steps, 3, barrier))
         if rank == 0:
             out["multiscale_config4"] = ms

@@ -5,7 +5,7 @@ element (phase of the sine, bf8 dZ) and sin/cos come from the hardware v_sin/v_c
 oracle/inr_oracle_bf16.py, a CPU restatement of the reference's arithmetic that rounds exactly where the kernels round --
 an indexing slip or a wrong fragment order cannot hide under that bar; (ii) loosely to the exact-fp32 engine on the same
 weights (the sanity bound: how far the rounding model itself sits from the reference's numbers), to the same Adam
-trajectory within optimisation noise, and (bench.py) to PSNR within 0.1 dB of the reference-equivalent run after 1000
+trajectory within optimisation noise, and (bench.py --full) to PSNR within 0.1 dB of the reference-equivalent run after 1000
 steps (BASELINE.json north_star)."""
 import numpy as np
 import pytest
