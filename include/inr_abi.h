@@ -8,8 +8,9 @@
  *   - every function returns 0 on success, <0 on error; inr_last_error() gives the message
  *     (thread-local); nothing throws or aborts across the ABI;
  *   - all tensor arguments are DEVICE pointers to contiguous row-major fp32 buffers owned by the
- *     caller; the library retains no pointer across calls and allocates no device memory -- with ONE exception:
- *     an INR_PRECISION_BF16 plan owns 32 bytes of device memory, its gradient-scale state (inr_plan_grad_scale_state),
+ *     caller -- except inr_image_metrics' `metrics_out` and `scratch`, which are fp64 (double) device buffers; the
+ *     library retains no pointer across calls and allocates no device memory -- with ONE exception:
+ *     an INR_PRECISION_BF16 plan owns 64 bytes of device memory (16 words), its gradient-scale state (inr_plan_grad_scale_state),
  *     allocated with hipMalloc and initialised with a synchronous hipMemcpy by the first call that needs it on a device
  *     (a step, a backward, or inr_plan_grad_scale_state), freed by inr_plan_destroy.  That first call must therefore run
  *     OUTSIDE stream capture;
@@ -41,6 +42,8 @@ extern "C" {
 
 /* 7: inr_adam_step_shard (data-parallel update on the entries a rank owns), inr_reg_grad (penalty gradients, complex64 tensors
  *    included; the Adam entry points refuse l1 / l2 != 0 on plans with complex tensors).
+ *    v7 additions (no version change: nothing existing moved): inr_image_metrics_scratch, inr_image_metrics (RSS, PSNR, SSIM of
+ *    the validation epoch).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -366,6 +369,23 @@ int inr_adam_step_dev(const inr_plan* plan, float* params, const float* grads, f
 /* Host helper: host_out[2*t] = float(lr / (1 - beta1^(t+1))), host_out[2*t+1] = float(sqrt(1 - beta2^(t+1))),
  * t = 0..n-1, in the doubles torch.optim.Adam uses (the same code path as inr_adam_step).  No GPU work. */
 int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* host_out);
+
+/* (v7 addition) Image metrics of the validation epoch (train.py:221-231): replaces fastmri.complex_abs + fastmri.rss and
+ * models/utils.py:227-250 (psnr; ssim = skimage.metrics.structural_similarity of scikit-image 0.18.1).
+ * `coils` [C,H,W,2] = the coil images after the inverse FFT (the network outputs themselves in image-space configs);
+ * rss_out [H,W] = sqrt(sum_c |z_c|^2), |z| = sqrt(re^2 + im^2), in fp32 and fixed coil order.  `ref` [H,W] (the
+ * ground-truth RSS image) may be NULL: RSS only, and metrics_out / scratch are not touched (may be NULL).  Otherwise
+ * metrics_out[8] (fp64, device) = psnr, ssim, sse, max_ref, min_ref, max_rec, min_rec, data_range, where
+ *   psnr = 10 log10(max_ref / (sse / (H W) + 1e-10))  (max, not max^2, as the reference),
+ *   data_range = max(max_ref, max_rec) - min(min_ref, min_rec) in fp32,
+ *   ssim = mean over the interior (3-pixel crop) of the 7x7 uniform-window SSIM of the images cast to fp64, K1 = 0.01,
+ *          K2 = 0.03, sample covariance; NaN when data_range == 0.
+ * H or W < 7 with a reference is INR_ERR_INVALID (skimage raises).  `scratch` = scratch_doubles fp64 words, at least
+ * what inr_image_metrics_scratch gives for (C, H, W).  No atomics, no host synchronisation: three launches on `stream`,
+ * bitwise reproducible, capturable in a graph. */
+int inr_image_metrics_scratch(int64_t C, int64_t H, int64_t W, int64_t* scratch_doubles);
+int inr_image_metrics(const float* coils, int64_t C, int64_t H, int64_t W, const float* ref, float* rss_out,
+                      double* metrics_out, double* scratch, int64_t scratch_doubles, void* stream);
 
 #ifdef __cplusplus
 }

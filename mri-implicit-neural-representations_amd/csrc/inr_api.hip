@@ -1458,6 +1458,42 @@ static void adam_bias_terms(double lr, double beta1, double beta2, int32_t step,
   *bc2_sqrt = (float)std::sqrt(bc2);
 }
 
+static int image_metrics_check(int64_t C, int64_t H, int64_t W, const char* who) {
+  if (C < 1 || H < 1 || W < 1 || C > (1LL << 30) || H > (1LL << 30) || W > (1LL << 30) || C * H * W > (1LL << 40))
+    return fail(INR_ERR_INVALID, "%s: C %lld, H %lld, W %lld", who, (long long)C, (long long)H, (long long)W);
+  return INR_OK;
+}
+
+int inr_image_metrics_scratch(int64_t C, int64_t H, int64_t W, int64_t* scratch_doubles) {
+  if (scratch_doubles == nullptr) return fail(INR_ERR_INVALID, "inr_image_metrics_scratch: null argument");
+  const int rc = image_metrics_check(C, H, W, "inr_image_metrics_scratch");
+  if (rc != INR_OK) return rc;
+  *scratch_doubles = inr::image_metrics_scratch_doubles(H, W);
+  return INR_OK;
+}
+
+int inr_image_metrics(const float* coils, int64_t C, int64_t H, int64_t W, const float* ref, float* rss_out,
+                      double* metrics_out, double* scratch, int64_t scratch_doubles, void* stream) {
+  if (coils == nullptr || rss_out == nullptr) return fail(INR_ERR_INVALID, "inr_image_metrics: null argument");
+  const int rc = image_metrics_check(C, H, W, "inr_image_metrics");
+  if (rc != INR_OK) return rc;
+  if (ref != nullptr) {
+    if (metrics_out == nullptr || scratch == nullptr)
+      return fail(INR_ERR_INVALID, "inr_image_metrics: a reference image needs metrics_out and scratch");
+    if (H < 7 || W < 7)  // skimage.metrics.structural_similarity raises the same way
+      return fail(INR_ERR_INVALID, "inr_image_metrics: win_size exceeds image extent (SSIM needs H, W >= 7; got %lld x %lld)",
+                  (long long)H, (long long)W);
+    const long long need = inr::image_metrics_scratch_doubles(H, W);
+    if (scratch_doubles < need)
+      return fail(INR_ERR_INVALID, "inr_image_metrics: scratch holds %lld doubles, needs %lld", (long long)scratch_doubles,
+                  need);
+  }
+  hipError_t e = inr::launch_image_metrics(coils, (int)C, (int)H, (int)W, ref, rss_out, metrics_out, scratch,
+                                           (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "inr_image_metrics");
+  return INR_OK;
+}
+
 int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* host_out) {
   if (host_out == nullptr || n < 1) return fail(INR_ERR_INVALID, "inr_adam_schedule: null table or n < 1");
   for (int32_t t = 0; t < n; ++t) adam_bias_terms(lr, beta1, beta2, t + 1, host_out + 2 * t, host_out + 2 * t + 1);

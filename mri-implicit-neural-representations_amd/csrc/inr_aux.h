@@ -96,4 +96,9 @@ hipError_t launch_mfn_nb4(const NetDesc& nd, const LossDesc& ld, const MlpArgs& 
 hipError_t launch_mfn_nb8(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
 hipError_t launch_mfn_nb16(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
 
+// image metrics of the validation epoch (inr_eval.hip): RSS over coils, then PSNR / SSIM against `ref` when it is given
+long long image_metrics_scratch_doubles(long long H, long long W);
+hipError_t launch_image_metrics(const float* coils, int C, int H, int W, const float* ref, float* rss_out,
+                                double* metrics_out, double* scratch, hipStream_t st);
+
 }  // namespace inr

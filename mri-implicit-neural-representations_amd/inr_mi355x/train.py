@@ -10,7 +10,9 @@ collate, no ``.item()`` sync per step), the encoder is fused into layer 0, and u
 config values raise instead of falling through.
 
 CLI (same flags as the reference, train.py:255-258):
-    python -m inr_mi355x.train --config cfg.yaml [--output_path out] [--synthetic C,H,W]
+    python -m inr_mi355x.train --config cfg.yaml [--output_path out] [--synthetic C,H,W] [--val]
+--val runs the reference's validation epoch every config['val_epoch'] epochs (its line is printed) and saves a
+checkpoint every config['image_save_epoch'] epochs.
 """
 from __future__ import annotations
 
@@ -32,6 +34,7 @@ from .mfn import FourierNet, GaborNet, KGaborNet
 from .networks import FFN, SIREN, WIRE, WIRE2D, Positional_Encoder
 from .synthetic import make_kspace
 from .undersampling import Undersampler, parse_undersampling_argument
+from .validation import ValidationMixin
 
 MODELS = {"SIREN": SIREN, "FFN": FFN, "WIRE": WIRE, "WIRE2D": WIRE2D,  # train.py:55-68
           "Fourier": FourierNet, "Gabor": GaborNet, "KGabor": KGaborNet}
@@ -151,7 +154,27 @@ def center_pair_rows(kcoords: torch.Tensor, min_sample: int, n_bands: int = 2):
         yield rows1[a].contiguous(), rows2[b].contiguous()
 
 
-class INRTrainer:
+def run_epochs(trainer, max_steps, log_every, val_epoch, on_validate, on_epoch_end):
+    """Epochs of sequential batches (train.py:155-198, train_kspace_multiscale.py:161-201) with the opt-in validation
+    epoch: after the last batch of epoch e when (e + 1) % val_epoch == 0, before the next epoch's learning rate applies."""
+    logged = []
+    for epoch in range(trainer.config["max_epoch"]):
+        for it in range(trainer.steps_per_epoch):
+            if max_steps is not None and trainer.global_step >= max_steps:
+                return logged
+            loss = trainer.step(epoch, it)
+            if log_every and trainer.global_step % log_every == 0:
+                logged.append((trainer.global_step, float(loss)))
+        if val_epoch and (epoch + 1) % val_epoch == 0:
+            rec = trainer.validate(epoch)
+            if on_validate is not None:
+                on_validate(rec)
+        if on_epoch_end is not None:
+            on_epoch_end(epoch)
+    return logged
+
+
+class INRTrainer(ValidationMixin):
     def __init__(self, config: dict, image: torch.Tensor, coords: torch.Tensor, shape, device,
                  seed: int = 0, mask: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1,
                  process_group=None, mask_seed: Optional[int] = None, graph_steps: bool = False):
@@ -272,6 +295,7 @@ class INRTrainer:
                                and self.loss.kind != L.LOSS_CENTER and not self._cplx_reg)
         if "pretrain" in config:  # train.py:117-121
             self.load_checkpoint(torch.load(config["pretrain"], map_location=self.device))
+        self._init_validation()
 
     # ---- one optimizer step on batch `it` of epoch `epoch` --------------------------------------
     def _inputs(self, lo: int, hi: int):
@@ -422,17 +446,12 @@ class INRTrainer:
         self.engine.backward(self._inputs(slo, shi), self.enc_B, dout.unsqueeze(0) if self.is_mfn else dout)
         return loss
 
-    def fit(self, max_steps: Optional[int] = None, log_every: int = 0):
-        """Runs epochs of sequential batches (train.py:155-198).  Returns the list of losses logged."""
-        logged = []
-        for epoch in range(self.config["max_epoch"]):
-            for it in range(self.steps_per_epoch):
-                if max_steps is not None and self.global_step >= max_steps:
-                    return logged
-                loss = self.step(epoch, it)
-                if log_every and self.global_step % log_every == 0:
-                    logged.append((self.global_step, float(loss)))
-        return logged
+    def fit(self, max_steps: Optional[int] = None, log_every: int = 0, val_epoch: Optional[int] = None,
+            on_validate=None, on_epoch_end=None):
+        """Runs epochs of sequential batches (train.py:155-198).  Returns the list of losses logged.  ``val_epoch``
+        (opt-in): validate() after every val_epoch-th epoch, its record handed to ``on_validate``; ``on_epoch_end(epoch)``
+        after every epoch.  Validation reads the parameters only: the trajectory is the same with or without it."""
+        return run_epochs(self, max_steps, log_every, val_epoch, on_validate, on_epoch_end)
 
     # ---- validation (train.py:199-231) -----------------------------------------------------------
     @torch.no_grad()
@@ -450,6 +469,36 @@ class INRTrainer:
         ref = reconstruct(self.image_full, self.shape, in_image_space)
         rec = reconstruct(self.predict_all(), self.shape, in_image_space)
         return float(psnr(ref, rec))
+
+    @torch.no_grad()
+    def validate(self, epoch: int) -> dict:
+        """The validation epoch of train.py:199-237: a no-grad sweep over every coordinate, the test loss (the config's
+        loss over sequential val batches of batch_size rows against the FULL data, summed, divided by the train loader's
+        length -- train.py:242), RSS, PSNR and SSIM on the device, one host read.  Updates best_psnr / best_psnr_ep /
+        best_ssim / best_ssim_ep (strict '>', 0-based epoch).  Returns {'epoch', 'test_loss', 'psnr', 'ssim'};
+        test_loss is None for per-coil fits (their val batches are not pinned down by the reference: INTEGRATION.md)."""
+        if self.loss.kind == L.LOSS_CENTER:
+            # the reference's CenterLoss draws randperm pairs on the CPU generator in the test loss too, which shifts every
+            # later training pair; that consumption is not reproduced
+            raise NotImplementedError("validation with loss 'LSL' (CenterLoss)")
+        pred = self.predict_all()
+        loss_sum = None
+        if not self.per_coil:
+            loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
+            for it in range(self.steps_per_epoch):
+                lo, hi = it * self.bs, min((it + 1) * self.bs, self.n)
+                A = self._batch_hdr_A(it, lo, hi)  # HDR / tanh take the batch's kcoords (train.py:214-217)
+                loss, _ = self.engine.loss_grad(self.loss, pred[lo:hi], self.image_full[lo:hi], hi - lo, hdr_A=A)
+                loss_sum += loss
+        m = self._device_metrics(self.image_full, pred, bool(self.config.get("transform", False)))
+        return self._finish_validation(epoch, m, loss_sum, self.steps_per_epoch)
+
+    @torch.no_grad()
+    def metrics(self) -> dict:
+        """PSNR and SSIM of the current model (validate() without the test loss and the best-epoch record)."""
+        m = self._device_metrics(self.image_full, self.predict_all(), bool(self.config.get("transform", False)))
+        psnr, ssim = m[:2].cpu().tolist()
+        return {"psnr": psnr, "ssim": ssim}
 
     def checkpoint(self) -> dict:
         """Same dict as train.py:247-250 ('opt' in torch.optim.Adam.state_dict() layout)."""
@@ -477,6 +526,8 @@ def main():
     ap.add_argument("--synthetic", type=str, default=None,
                     help="C,H,W: fit a synthetic k-space of that shape instead of the scan the config names")
     ap.add_argument("--max_steps", type=int, default=None)
+    ap.add_argument("--val", action="store_true",
+                    help="validate every config['val_epoch'] epochs and checkpoint every config['image_save_epoch']")
     opts = ap.parse_args()
     config = set_default_configs(get_config(opts.config))
     if opts.synthetic:
@@ -487,11 +538,33 @@ def main():
         from .datasets import from_config, trainer_inputs
         image, coords, shape = trainer_inputs(from_config(config, "cuda"))
     tr = INRTrainer(config, image, coords, shape, "cuda")
+    run_cli(tr, config, opts)
+
+
+def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
+    """Fit, then print the JSON result (and, with --val, the reference's validation lines and checkpoints)."""
+    os.makedirs(opts.output_path, exist_ok=True)
+    kw = {}
+    if opts.val:
+        def on_validate(rec):
+            print(tr.validation_line(rec, config["max_epoch"]), flush=True)
+
+        def on_epoch_end(epoch):  # train.py:244-250
+            if (epoch + 1) % config["image_save_epoch"] == 0:
+                torch.save(tr.checkpoint(), os.path.join(opts.output_path, "model_%06d.pt" % (epoch + 1)))
+
+        kw = dict(val_epoch=config["val_epoch"], on_validate=on_validate, on_epoch_end=on_epoch_end)
     t0 = time.time()
-    tr.fit(opts.max_steps, log_every=config.get("log_iter", 20))
+    tr.fit(opts.max_steps, log_every=config.get("log_iter", 20), **kw)
     torch.cuda.synchronize()
     res = {"steps": tr.global_step, "seconds": time.time() - t0, "psnr": tr.evaluate()}
-    os.makedirs(opts.output_path, exist_ok=True)
+    if extra:
+        res.update(extra)
+    if opts.val:
+        res["ssim"] = tr.metrics()["ssim"]
+        res["validation"] = tr.val_history
+        res.update(best_psnr=tr.best_psnr, best_psnr_ep=tr.best_psnr_ep, best_ssim=tr.best_ssim,
+                   best_ssim_ep=tr.best_ssim_ep)
     torch.save(tr.checkpoint(), os.path.join(opts.output_path, "model_%06d.pt" % tr.global_step))
     print(json.dumps(res))
 

@@ -20,7 +20,8 @@ from .engine import ConsistencySpec, LossSpec
 from .evalchain import psnr, reconstruct
 from .mfn import MultiscaleBoundedFourier, MultiscaleKFourier
 from .networks import Positional_Encoder
-from .train import exchange_and_update, lr_factor, set_default_configs, shard_rows, wants_sharded_update
+from .train import exchange_and_update, lr_factor, run_epochs, set_default_configs, shard_rows, wants_sharded_update
+from .validation import ValidationMixin
 
 
 def create_pairs(values: Sequence[float], multiplication_factor: int):
@@ -29,7 +30,7 @@ def create_pairs(values: Sequence[float], multiplication_factor: int):
     return [(p[0], p[1]) for p in pairs for _ in range(multiplication_factor)]
 
 
-class MultiscaleTrainer:
+class MultiscaleTrainer(ValidationMixin):
     def __init__(self, config: dict, image: torch.Tensor, coords: torch.Tensor, dist: torch.Tensor,
                  radii: Optional[Sequence[float]], shape, device, seed: int = 0, rank: int = 0, world: int = 1,
                  process_group=None, mask: Optional[torch.Tensor] = None, mask_seed: Optional[int] = None):
@@ -102,6 +103,7 @@ class MultiscaleTrainer:
         self._cons = {}
         if "pretrain" in config:
             self.load_checkpoint(torch.load(config["pretrain"], map_location=self.device))
+        self._init_validation()
 
     def _inputs(self, lo: int, hi: int) -> torch.Tensor:
         return self.coords[lo:hi] if self.enc_B is not None else self.encoder.embedding(self.coords[lo:hi]).contiguous()
@@ -181,16 +183,10 @@ class MultiscaleTrainer:
 
         load_dict(self.model, self.encoder, self.engine, ckpt, rebind)
 
-    def fit(self, max_steps: Optional[int] = None, log_every: int = 0):
-        logged = []
-        for epoch in range(self.config["max_epoch"]):
-            for it in range(self.steps_per_epoch):
-                if max_steps is not None and self.global_step >= max_steps:
-                    return logged
-                loss = self.step(epoch, it)
-                if log_every and self.global_step % log_every == 0:
-                    logged.append((self.global_step, float(loss)))
-        return logged
+    def fit(self, max_steps: Optional[int] = None, log_every: int = 0, val_epoch: Optional[int] = None,
+            on_validate=None, on_epoch_end=None):
+        """Epochs of sequential batches; ``val_epoch`` / ``on_validate`` / ``on_epoch_end`` as INRTrainer.fit."""
+        return run_epochs(self, max_steps, log_every, val_epoch, on_validate, on_epoch_end)
 
     @torch.no_grad()
     def predict_all(self, chunk: int = 1 << 18) -> torch.Tensor:
@@ -206,17 +202,37 @@ class MultiscaleTrainer:
         ref = reconstruct(self.image_full, self.shape, False)
         return float(psnr(ref, reconstruct(self.predict_all(), self.shape, False)))
 
+    @torch.no_grad()
+    def validate(self, epoch: int) -> dict:
+        """The validation epoch of train_kspace_multiscale.py:202-243, with its quirks: the loop over the heads
+        REASSIGNS test_loss, so only the last head's loss survives (:214-224); limit_kspace is a no-op (every head sees
+        the full gt); the reconstruction is outs[-1].  Summed over val batches of batch_size rows, divided by the train
+        loader's length.  Record and best-epoch bookkeeping as INRTrainer.validate (test_loss None for per-coil fits)."""
+        pred = self.predict_all()
+        loss_sum = None
+        if not self.per_coil:
+            loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
+            for it in range(self.steps_per_epoch):
+                lo, hi = it * self.bs, min((it + 1) * self.bs, self.n)
+                loss, _ = self.engine.loss_grad(self.loss, pred[lo:hi], self.image_full[lo:hi], hi - lo)
+                loss_sum += loss * self.scale  # 0.5 * LogSpaceLoss for 'LSL' (train_kspace_multiscale.py:222)
+        m = self._device_metrics(self.image_full, pred, False)
+        return self._finish_validation(epoch, m, loss_sum, self.steps_per_epoch)
+
+    @torch.no_grad()
+    def metrics(self) -> dict:
+        """PSNR and SSIM of the current model's last head."""
+        psnr_, ssim_ = self._device_metrics(self.image_full, self.predict_all(), False)[:2].cpu().tolist()
+        return {"psnr": psnr_, "ssim": ssim_}
+
 
 def main():
     """CLI with the reference's flags (train_kspace_multiscale.py:50-52): --config, --output_path; the scan
     comes from datasets.py, or a synthetic k-space with --synthetic C,H,W."""
     import argparse
-    import json
-    import os
-    import time
 
     from .synthetic import make_kspace
-    from .train import get_config
+    from .train import get_config, run_cli
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, required=True)
     ap.add_argument("--data_samples", type=str, default="")
@@ -224,6 +240,8 @@ def main():
     ap.add_argument("--synthetic", type=str, default=None,
                     help="C,H,W: fit a synthetic k-space of that shape instead of the scan the config names")
     ap.add_argument("--max_steps", type=int, default=None)
+    ap.add_argument("--val", action="store_true",
+                    help="validate every config['val_epoch'] epochs and checkpoint every config['image_save_epoch']")
     opts = ap.parse_args()
     config = set_default_configs(get_config(opts.config))
     if config["model"] not in ("BoundedFourier",):
@@ -236,13 +254,7 @@ def main():
         image, coords, shape = trainer_inputs(from_config(config, "cuda"))
     dist = torch.sqrt(coords[:, 1] ** 2 + coords[:, 2] ** 2)
     tr = MultiscaleTrainer(config, image, coords, dist, None, shape, "cuda")
-    t0 = time.time()
-    tr.fit(opts.max_steps, log_every=config.get("log_iter", 20))
-    torch.cuda.synchronize()
-    res = {"steps": tr.global_step, "seconds": time.time() - t0, "psnr": tr.evaluate(), "radii": tr.radii}
-    os.makedirs(opts.output_path, exist_ok=True)
-    torch.save(tr.checkpoint(), os.path.join(opts.output_path, "model_%06d.pt" % tr.global_step))
-    print(json.dumps(res))
+    run_cli(tr, config, opts, extra={"radii": tr.radii})
 
 
 if __name__ == "__main__":

@@ -26,6 +26,7 @@ from .engine import LossSpec
 from .evalchain import psnr, reconstruct
 from .networks import Positional_Encoder
 from .train import MODELS, MFN_MODELS, lr_factor, set_default_configs
+from .validation import ValidationMixin
 
 
 def ring_owner(i: int, world: int) -> int:
@@ -41,7 +42,7 @@ def winning_ring(dist: torch.Tensor, radii: Sequence[float]) -> torch.Tensor:
     return win
 
 
-class RingEnsembleTrainer:
+class RingEnsembleTrainer(ValidationMixin):
     def __init__(self, config: dict, image: torch.Tensor, coords: torch.Tensor, shape, device,
                  radii: Optional[Sequence[float]] = None, seed: int = 0, rank: int = 0, world: int = 1,
                  process_group=None, jitter: float = 0.0):
@@ -79,6 +80,7 @@ class RingEnsembleTrainer:
         self.n = coords.shape[0]
         self.coords = coords.to(self.device).contiguous()
         self.image = image.to(self.device).contiguous()
+        self._init_validation()
         self.dist = torch.sqrt(self.coords[:, 1] ** 2 + self.coords[:, 2] ** 2)
         self.bs = int(config["batch_size"])
         self.steps_per_epoch = math.ceil(self.n / self.bs)
@@ -159,6 +161,14 @@ class RingEnsembleTrainer:
         in_image_space = bool(self.config.get("transform", False))
         ref = reconstruct(self.image, self.shape, in_image_space)
         return float(psnr(ref, reconstruct(self.predict_all(), self.shape, in_image_space)))
+
+    @torch.no_grad()
+    def metrics(self) -> dict:
+        """PSNR and SSIM of the assembled reconstruction on the device (the reference's ring loop has no validation
+        epoch, hence no test loss).  Every rank that calls it after the all-reduce of predict_all gets the same numbers."""
+        m = self._device_metrics(self.image, self.predict_all(), bool(self.config.get("transform", False)))
+        psnr_, ssim_ = m[:2].cpu().tolist()
+        return {"psnr": psnr_, "ssim": ssim_}
 
     def checkpoints(self) -> dict:
         """{ring: {'net', 'enc'}} of the owned rings (submodel_%d files of train_clustering.py:243-249)."""
