@@ -8,7 +8,8 @@
  *   - every function returns 0 on success, <0 on error; inr_last_error() gives the message
  *     (thread-local); nothing throws or aborts across the ABI;
  *   - all tensor arguments are DEVICE pointers to contiguous row-major fp32 buffers owned by the
- *     caller -- except inr_image_metrics' `metrics_out` and `scratch`, which are fp64 (double) device buffers; the
+ *     caller -- except inr_image_metrics' `metrics_out` and `scratch`, which are fp64 (double) device buffers, and
+ *     inr_shuffle_epoch's integer buffers (uint8 masks, int32 counts, int64 order); the
  *     library retains no pointer across calls and allocates no device memory -- with ONE exception:
  *     an INR_PRECISION_BF16 plan owns 64 bytes of device memory (16 words), its gradient-scale state (inr_plan_grad_scale_state),
  *     allocated with hipMalloc and initialised with a synchronous hipMemcpy by the first call that needs it on a device
@@ -43,7 +44,7 @@ extern "C" {
 /* 7: inr_adam_step_shard (data-parallel update on the entries a rank owns), inr_reg_grad (penalty gradients, complex64 tensors
  *    included; the Adam entry points refuse l1 / l2 != 0 on plans with complex tensors).
  *    v7 additions (no version change: nothing existing moved): inr_image_metrics_scratch, inr_image_metrics (RSS, PSNR, SSIM of
- *    the validation epoch).
+ *    the validation epoch); inr_shuffle_epoch (the keyed row permutation of a shuffled epoch).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -386,6 +387,20 @@ int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* h
 int inr_image_metrics_scratch(int64_t C, int64_t H, int64_t W, int64_t* scratch_doubles);
 int inr_image_metrics(const float* coils, int64_t C, int64_t H, int64_t W, const float* ref, float* rss_out,
                       double* metrics_out, double* scratch, int64_t scratch_doubles, void* stream);
+
+/* (v7 addition) One shuffled epoch (no reference counterpart beyond the shuffle=True its callers pass and its loaders
+ * drop, train.py:281,307 against models/utils.py:84-99): output row j is input row order(j), the keyed stateless
+ * permutation of DESIGN.md section 4.12 -- a pure function of (n, seed, epoch), restated in numpy by
+ * inr_mi355x/shuffle.py::epoch_order with the same 32-bit integers.  1 <= n < 2^31.
+ *   coords [n,3] -> coords_out, gt [n,2] -> gt_out (8-byte aligned), dist [n] -> dist_out, mask [n] u8 -> mask_out:
+ *     each pair is optional (both NULL) and must not alias; mask may come without mask_out (counts only);
+ *   batch_counts (int32, ceil(n / batch_size) entries; may be NULL): sampled rows (mask != 0; every row without a mask)
+ *     among output rows [b * batch_size, (b + 1) * batch_size) -- integer atomics on words the call zeroes first, exact;
+ *   order_out (int64 [n]; may be NULL): order(j) itself.
+ * One memset node (batch_counts only) and one kernel launch on `stream`; nothing is allocated, nothing is read back. */
+int inr_shuffle_epoch(int64_t n, int64_t batch_size, uint64_t seed, uint32_t epoch, const float* coords,
+                      const float* gt, const float* dist, const uint8_t* mask, float* coords_out, float* gt_out,
+                      float* dist_out, uint8_t* mask_out, int32_t* batch_counts, int64_t* order_out, void* stream);
 
 #ifdef __cplusplus
 }

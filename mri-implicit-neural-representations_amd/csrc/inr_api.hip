@@ -1494,6 +1494,52 @@ int inr_image_metrics(const float* coils, int64_t C, int64_t H, int64_t W, const
   return INR_OK;
 }
 
+// key schedule of the epoch permutation (inr_mi355x/shuffle.py round_keys is the same text in Python)
+static uint32_t shuffle_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7FEB352Du;
+  x ^= x >> 15;
+  x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
+
+static inr::ShuffleKeys shuffle_keys(int64_t n, uint64_t seed, uint32_t epoch) {
+  const uint32_t gold = 0x9E3779B9u;
+  inr::ShuffleKeys sk;
+  const uint32_t base = shuffle_mix(shuffle_mix(shuffle_mix((uint32_t)seed + gold) ^ (uint32_t)(seed >> 32)) + epoch);
+  for (int r = 0; r < SHUFFLE_ROUNDS; ++r) sk.k[r] = shuffle_mix(base + (uint32_t)(r + 1) * gold);
+  int k = 8;  // smallest even k >= 8 with 2^k >= n
+  while ((1LL << k) < n) k += 2;
+  sk.h = k / 2;
+  return sk;
+}
+
+int inr_shuffle_epoch(int64_t n, int64_t batch_size, uint64_t seed, uint32_t epoch, const float* coords,
+                      const float* gt, const float* dist, const uint8_t* mask, float* coords_out, float* gt_out,
+                      float* dist_out, uint8_t* mask_out, int32_t* batch_counts, int64_t* order_out, void* stream) {
+  if (n < 1 || n >= (1LL << 31))
+    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: n = %lld (the 32-bit permutation covers 1 <= n < 2^31)", (long long)n);
+  if ((coords == nullptr) != (coords_out == nullptr) || (gt == nullptr) != (gt_out == nullptr) ||
+      (dist == nullptr) != (dist_out == nullptr) || (mask == nullptr && mask_out != nullptr))
+    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: an input and its output buffer go together");
+  if (coords_out == nullptr && gt_out == nullptr && dist_out == nullptr && mask_out == nullptr &&
+      batch_counts == nullptr && order_out == nullptr)
+    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: no output");
+  if (batch_counts != nullptr && (batch_size < 1 || batch_size >= (1LL << 31)))
+    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: batch_counts with batch_size = %lld", (long long)batch_size);
+  if (((uintptr_t)gt | (uintptr_t)gt_out) & 7u)
+    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: gt / gt_out must be 8-byte aligned ([n,2] rows move as one load)");
+  if ((coords != nullptr && coords == coords_out) || (gt != nullptr && gt == gt_out) ||
+      (dist != nullptr && dist == dist_out) || (mask != nullptr && mask == mask_out))
+    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: in-place (an output buffer is its input)");
+  const inr::ShuffleKeys sk = shuffle_keys(n, seed, epoch);
+  hipError_t e = inr::launch_shuffle_epoch(sk, n, batch_size, coords, gt, dist, mask, coords_out, gt_out, dist_out,
+                                           mask_out, batch_counts, (long long*)order_out, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "inr_shuffle_epoch");
+  return INR_OK;
+}
+
 int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* host_out) {
   if (host_out == nullptr || n < 1) return fail(INR_ERR_INVALID, "inr_adam_schedule: null table or n < 1");
   for (int32_t t = 0; t < n; ++t) adam_bias_terms(lr, beta1, beta2, t + 1, host_out + 2 * t, host_out + 2 * t + 1);

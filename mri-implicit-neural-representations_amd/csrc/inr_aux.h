@@ -101,4 +101,15 @@ long long image_metrics_scratch_doubles(long long H, long long W);
 hipError_t launch_image_metrics(const float* coils, int C, int H, int W, const float* ref, float* rss_out,
                                 double* metrics_out, double* scratch, hipStream_t st);
 
+// shuffled epochs (inr_aux.hip): round keys of (seed, epoch) and the half width of the Feistel domain,
+// both made on the host (inr_api.hip shuffle_keys)
+#define SHUFFLE_ROUNDS 6
+struct ShuffleKeys {
+  unsigned k[SHUFFLE_ROUNDS];
+  int h;
+};
+hipError_t launch_shuffle_epoch(const ShuffleKeys& sk, long long n, long long bs, const float* coords, const float* gt,
+                                const float* dist, const uint8_t* mask, float* coords_out, float* gt_out, float* dist_out,
+                                uint8_t* mask_out, int* batch_counts, long long* order_out, hipStream_t st);
+
 }  // namespace inr

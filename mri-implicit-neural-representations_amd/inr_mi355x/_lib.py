@@ -100,6 +100,8 @@ SYMBOLS = {
     "inr_adam_schedule": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int32, _P]),
     "inr_image_metrics_scratch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_image_metrics": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
+    "inr_shuffle_epoch": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                    _P]),
 }
 METRICS_WORDS = 8  # inr_image_metrics' metrics_out: psnr, ssim, sse, max_ref, min_ref, max_rec, min_rec, data_range
 

@@ -325,15 +325,28 @@ def get_datasets(data, data_root, set, transform=True, sample=0, slice=0, challe
     return dataset, train
 
 
-def iter_batches(dataset, batch_size: int):
+def iter_batches(dataset, batch_size: int, shuffle_seed: Optional[int] = None, epoch: int = 0):
     """Sequential, unshuffled (coords, gt, dist, mask) batches as views -- what the reference's
     DataLoader(shuffle=False, collate_fn=collate_inr) yields (models/utils.py:84-90), minus the copies.  A
-    coil-wrapped dataset yields one coil per batch."""
+    coil-wrapped dataset yields one coil per batch.
+    With ``shuffle_seed``: the batches of epoch ``epoch`` in the order of shuffle.epoch_order(n, shuffle_seed, epoch) --
+    the order the trainers' ``config['shuffle']`` uses, made on the device by the same kernel (gathered copies, not
+    views); a coil-wrapped dataset yields its coils in shuffle.coil_order."""
     if isinstance(dataset, MRICoilWrapperDataset):
-        for c in range(len(dataset)):
+        coils = range(len(dataset))
+        if shuffle_seed is not None:
+            from .shuffle import coil_order
+            coils = coil_order(len(dataset), shuffle_seed, epoch)
+        for c in coils:
             yield dataset[c]
         return
     n = len(dataset)
+    if shuffle_seed is not None:
+        from .shuffle import device_order
+        order = device_order(n, shuffle_seed, epoch, dataset[slice(0, 1)][0].device)
+        for lo in range(0, n, batch_size):
+            yield dataset[order[lo:min(lo + batch_size, n)]]
+        return
     for lo in range(0, n, batch_size):
         yield dataset[slice(lo, min(lo + batch_size, n))]
 

@@ -2,7 +2,8 @@
 over the fused MI355X engine (tier 2), with optional data parallelism over coordinates.
 
 Kept from the reference, on purpose: sequential unshuffled batches
-(batch i = rows [i*bs,(i+1)*bs) of the C-major grid, last batch short), per-EPOCH LambdaLR
+(batch i = rows [i*bs,(i+1)*bs) of the C-major grid, last batch short) unless config['shuffle'] asks for the keyed
+per-epoch row permutation of inr_mi355x/shuffle.py (opt-in), per-EPOCH LambdaLR
 ``lr*0.2**min(epoch/max_epoch,1)``, Adam with L2-style weight decay, loss on masked rows only
 when undersampled (forward still runs on every row), ``psnr`` with max(x).
 Changed, on purpose: inputs stay resident in HBM (no per-step H2D, no per-item DataLoader
@@ -11,6 +12,7 @@ config values raise instead of falling through.
 
 CLI (same flags as the reference, train.py:255-258):
     python -m inr_mi355x.train --config cfg.yaml [--output_path out] [--synthetic C,H,W] [--val]
+                               [--shuffle] [--shuffle-seed S]
 --val runs the reference's validation epoch every config['val_epoch'] epochs (its line is printed) and saves a
 checkpoint every config['image_save_epoch'] epochs.
 """
@@ -32,6 +34,7 @@ from .engine import LossSpec
 from .evalchain import psnr, reconstruct
 from .mfn import FourierNet, GaborNet, KGaborNet
 from .networks import FFN, SIREN, WIRE, WIRE2D, Positional_Encoder
+from .shuffle import CoilOrder, EpochBuffers, shuffle_settings
 from .synthetic import make_kspace
 from .undersampling import Undersampler, parse_undersampling_argument
 from .validation import ValidationMixin
@@ -180,6 +183,7 @@ class INRTrainer(ValidationMixin):
                  process_group=None, mask_seed: Optional[int] = None, graph_steps: bool = False):
         config = set_default_configs(dict(config))
         self.config = config
+        self.shuffle, self.shuffle_seed = shuffle_settings(config, seed, graph_steps)
         self.device = torch.device(device)
         self.rank, self.world, self.pg = rank, world, process_group
         self.shape = shape
@@ -282,6 +286,18 @@ class INRTrainer(ValidationMixin):
         self.steps_per_epoch = math.ceil(self.n / self.bs)
         self.global_step = 0
         self._hdr_A = {}
+        # config['shuffle']: plain batches are views of a second set of resident buffers, refilled by one kernel call per
+        # epoch (shuffle.EpochBuffers); per-coil batches stay views of the grid and are visited in a permuted order.
+        # Validation, predict_all and the test loss keep reading the unshuffled data (the reference's val loader is
+        # never shuffled).  Off: the training views ARE the resident data.
+        self._epoch_buf = self._coil_order = None
+        self._t_coords, self._t_image, self._t_mask = self.coords, self.image, self.mask
+        if self.shuffle and self.per_coil:
+            self._coil_order = CoilOrder(self.steps_per_epoch, self.shuffle_seed)
+        elif self.shuffle:
+            self._epoch_buf = EpochBuffers(self.shuffle_seed, self.bs, self.coords, self.image, mask=self.mask)
+            self._t_coords, self._t_image, self._t_mask = self._epoch_buf.coords, self._epoch_buf.image, self._epoch_buf.mask
+            self._hdr_A_epoch = []
         # graph_steps: every batch of the epoch becomes one captured HIP graph (fused kernel, weight-gradient GEMM,
         # reduction, Adam, step advance) replayed from then on -- the batches are fixed views of the resident data
         # (sequential sampler, models/utils.py:126-130), the step count and learning rate live in device memory.
@@ -298,12 +314,13 @@ class INRTrainer(ValidationMixin):
         self._init_validation()
 
     # ---- one optimizer step on batch `it` of epoch `epoch` --------------------------------------
-    def _inputs(self, lo: int, hi: int):
+    def _inputs(self, lo: int, hi: int, train: bool = False):
+        coords = self._t_coords if train else self.coords
         if self.enc_B is not None:
-            return self.coords[lo:hi]
+            return coords[lo:hi]
         if self.config["encoder"]["embedding"] == "none":
-            return self.coords[lo:hi]
-        return self.encoder.embedding(self.coords[lo:hi])
+            return coords[lo:hi]
+        return self.encoder.embedding(coords[lo:hi])
 
     def _batch_hdr_A(self, it: int, lo: int, hi: int) -> float:
         """A = mean_i((1-f_i)^2) over ALL batch coordinates (losses.py:241-242,258; SURVEY A.4 #17)."""
@@ -316,8 +333,23 @@ class INRTrainer(ValidationMixin):
         return self._hdr_A[it]
 
     def _count(self, lo: int, hi: int) -> int:
-        """sampled rows of [lo, hi) (all of them without a mask)"""
+        """sampled rows of the training batch [lo, hi) (all of them without a mask)"""
+        if self._epoch_buf is not None:
+            return self._epoch_buf.counts[lo // self.bs]
         return hi - lo if self._mask_cum is None else int(self._mask_cum[hi] - self._mask_cum[lo])
+
+    def _begin_shuffled(self, epoch: int, it: int) -> int:
+        """Shuffled fits: the batch index step() works with.  Per-coil: the coil visited at position ``it``.  Plain
+        batches: ``it`` itself, after the first step of an epoch has refilled the epoch buffers (one kernel call, one
+        read-back of the counts) and recomputed what is tied to a batch's contents -- the HDR / Center scalar A of every
+        batch, one batched op over the epoch's coordinates and one read-back."""
+        if self._coil_order is not None:
+            return self._coil_order.at(epoch, it)
+        if self._epoch_buf.begin(epoch) and self.loss.kind in (L.LOSS_HDR, L.LOSS_CENTER):
+            kc = self._t_coords
+            f = torch.exp(-(kc[:, 1] ** 2 + kc[:, 2] ** 2) / (2 * self.loss.sigma ** 2))
+            self._hdr_A_epoch = self._epoch_buf.batch_means((1 - f) ** 2)
+        return it
 
     def _penalty(self):
         """(value, cplx_reg): the penalty VALUE the reference adds to the logged loss, at the parameters the step starts from
@@ -339,17 +371,19 @@ class INRTrainer(ValidationMixin):
         return self.l2 * mod, (0.0, self.l2, (torch.stack((s_re, -s_im)) / mod).contiguous())
 
     def step(self, epoch: int, it: int) -> torch.Tensor:
+        if self.shuffle:
+            it = self._begin_shuffled(epoch, it)
         lo, hi = it * self.bs, min((it + 1) * self.bs, self.n)
         count = self._count(lo, hi)
-        A = self._batch_hdr_A(it, lo, hi)
+        A = self._hdr_A_epoch[it] if self._epoch_buf is not None and self._hdr_A_epoch else self._batch_hdr_A(it, lo, hi)
         if self.graph_steps:
             return self._graph_step(epoch, it, lo, hi, count, A)
         if self.world == 1 and self.one_call_steps and not self.sharded_update and hi > lo:
             # single rank: nothing sits between the reduction and the update -- one call, one launch less
             cfg = self.config
             penalty, _ = self._penalty()  # value of the penalty at the parameters the step starts from, as below
-            m = self.mask[lo:hi] if self.mask is not None else None
-            loss = self.engine.train_adam_step(self._inputs(lo, hi), self.enc_B, self.image[lo:hi], self.loss,
+            m = self._t_mask[lo:hi] if self.mask is not None else None
+            loss = self.engine.train_adam_step(self._inputs(lo, hi, True), self.enc_B, self._t_image[lo:hi], self.loss,
                                                cfg["lr"] * lr_factor(epoch, cfg["max_epoch"]), count=count, mask=m,
                                                hdr_A=A, beta1=cfg["beta1"], beta2=cfg["beta2"], eps=1e-8,
                                                weight_decay=cfg["weight_decay"], l1=self.l1, l2=self.l2)
@@ -365,7 +399,7 @@ class INRTrainer(ValidationMixin):
                 self.engine.grads.zero_()
                 loss = torch.zeros((), device=self.device)
             else:
-                m = self.mask[slo:shi] if self.mask is not None else None
+                m = self._t_mask[slo:shi] if self.mask is not None else None
                 loss = self._fused(slo, shi, count, m, A)
         # the loss the reference logs includes the penalty VALUE at the parameters the step starts from
         # (train.py:185-192); its gradient is formed inside the Adam kernel.  Every rank holds the same parameters.
@@ -409,7 +443,7 @@ class INRTrainer(ValidationMixin):
                     cfg["beta2"], 1e-8, cfg["weight_decay"], self.l1, self.l2)
 
     def _fused(self, slo, shi, count, m, A):
-        return self.engine.train_step(self._inputs(slo, shi), self.enc_B, self.image[slo:shi], self.loss,
+        return self.engine.train_step(self._inputs(slo, shi, True), self.enc_B, self._t_image[slo:shi], self.loss,
                                       count=count, mask=m, hdr_A=A)
 
     def _center_step(self, lo: int, hi: int, A: float) -> torch.Tensor:
@@ -417,10 +451,10 @@ class INRTrainer(ValidationMixin):
         term of the two radial bands -> backward.  The pairs are drawn with torch.randperm on the CPU generator in the
         reference's order (band 1: inner, ring; band 2: inner, ring), from masks on dist^2 = ky^2 + kx^2 compared with the
         band RATIOS (losses.py:153-154,180-187).  Single rank, whole batches (pairs span the batch)."""
-        x, gt = self._inputs(lo, hi), self.image[lo:hi]
+        x, gt = self._inputs(lo, hi, True), self._t_image[lo:hi]
         out = self.engine.forward(x, self.enc_B, save=True)
         loss, dout = self.engine.loss_grad(self.loss, out, gt, hi - lo, hdr_A=A)
-        for rows_a, rows_b in center_pair_rows(self.coords[lo:hi], self.loss.min_sample):
+        for rows_a, rows_b in center_pair_rows(self._t_coords[lo:hi], self.loss.min_sample):
             loss = self.engine.center_pairs_grad(out, gt, dout, rows_a, rows_b, 0.1)
         self.engine.backward(x, self.enc_B, dout)
         return loss
@@ -528,8 +562,9 @@ def main():
     ap.add_argument("--max_steps", type=int, default=None)
     ap.add_argument("--val", action="store_true",
                     help="validate every config['val_epoch'] epochs and checkpoint every config['image_save_epoch']")
+    add_shuffle_flags(ap)
     opts = ap.parse_args()
-    config = set_default_configs(get_config(opts.config))
+    config = apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts)
     if opts.synthetic:
         C, H, W = (int(v) for v in opts.synthetic.split(","))
         image, coords, shape = make_kspace(C, H, W, normalization=config.get("normalization", "coil"),
@@ -539,6 +574,21 @@ def main():
         image, coords, shape = trainer_inputs(from_config(config, "cuda"))
     tr = INRTrainer(config, image, coords, shape, "cuda")
     run_cli(tr, config, opts)
+
+
+def add_shuffle_flags(ap) -> None:
+    ap.add_argument("--shuffle", action="store_true",
+                    help="random minibatches: a keyed row permutation per epoch, made on the device (config['shuffle'])")
+    ap.add_argument("--shuffle-seed", type=int, default=None,
+                    help="key of the permutation (config['shuffle_seed']; default: the trainer's seed)")
+
+
+def apply_shuffle_flags(config: dict, opts) -> dict:
+    if opts.shuffle:
+        config["shuffle"] = True
+    if opts.shuffle_seed is not None:
+        config["shuffle_seed"] = opts.shuffle_seed
+    return config
 
 
 def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
@@ -557,7 +607,8 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
     t0 = time.time()
     tr.fit(opts.max_steps, log_every=config.get("log_iter", 20), **kw)
     torch.cuda.synchronize()
-    res = {"steps": tr.global_step, "seconds": time.time() - t0, "psnr": tr.evaluate()}
+    res = {"steps": tr.global_step, "seconds": time.time() - t0, "psnr": tr.evaluate(),
+           "shuffle": tr.shuffle, "shuffle_seed": tr.shuffle_seed if tr.shuffle else None}
     if extra:
         res.update(extra)
     if opts.val:

@@ -6,6 +6,7 @@ dist) + sum_k 0.5*loss_fn(out_k, gt)  (limit_kspace is a no-op, SURVEY A.4 #2: e
 gt);  Adam;  per-epoch LambdaLR.  Radii of the nested discs come from the k-means ring partition
 (inr_mi355x/clustering.py = the reference's clustering.py; train_kspace_multiscale.py:73-84): pass ``radii`` or
 leave it None to have them computed from ``config["partition"]`` (no_steps, no_models).
+``config["shuffle"]`` (opt-in): shuffled epochs as in INRTrainer (inr_mi355x/shuffle.py).
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ from .engine import ConsistencySpec, LossSpec
 from .evalchain import psnr, reconstruct
 from .mfn import MultiscaleBoundedFourier, MultiscaleKFourier
 from .networks import Positional_Encoder
+from .shuffle import CoilOrder, EpochBuffers, shuffle_settings
 from .train import exchange_and_update, lr_factor, run_epochs, set_default_configs, shard_rows, wants_sharded_update
 from .validation import ValidationMixin
 
@@ -35,6 +37,7 @@ class MultiscaleTrainer(ValidationMixin):
                  radii: Optional[Sequence[float]], shape, device, seed: int = 0, rank: int = 0, world: int = 1,
                  process_group=None, mask: Optional[torch.Tensor] = None, mask_seed: Optional[int] = None):
         config = set_default_configs(dict(config))
+        self.shuffle, self.shuffle_seed = shuffle_settings(config, seed)
         if radii is None:  # train_kspace_multiscale.py:73-84
             from .clustering import partition_and_stats
             C, H, W = int(shape[0]), int(shape[1]), int(shape[2])
@@ -101,14 +104,44 @@ class MultiscaleTrainer(ValidationMixin):
         self.steps_per_epoch = math.ceil(self.n / self.bs)
         self.global_step = 0
         self._cons = {}
+        # config['shuffle'], as INRTrainer: epoch buffers for plain batches (dist travels with the rows), a permuted
+        # coil order for per-coil batches; validation and predict_all keep reading the unshuffled data
+        self._epoch_buf = self._coil_order = None
+        self._t_coords, self._t_image, self._t_dist, self._t_mask = self.coords, self.image, self.dist, self.mask
+        if self.shuffle and self.per_coil:
+            self._coil_order = CoilOrder(self.steps_per_epoch, self.shuffle_seed)
+        elif self.shuffle:
+            eb = EpochBuffers(self.shuffle_seed, self.bs, self.coords, self.image, dist=self.dist, mask=self.mask)
+            self._epoch_buf = eb
+            self._t_coords, self._t_image, self._t_dist, self._t_mask = eb.coords, eb.image, eb.dist, eb.mask
+            self._cons_epoch = []
         if "pretrain" in config:
             self.load_checkpoint(torch.load(config["pretrain"], map_location=self.device))
         self._init_validation()
 
-    def _inputs(self, lo: int, hi: int) -> torch.Tensor:
-        return self.coords[lo:hi] if self.enc_B is not None else self.encoder.embedding(self.coords[lo:hi]).contiguous()
+    def _inputs(self, lo: int, hi: int, train: bool = False) -> torch.Tensor:
+        coords = self._t_coords if train else self.coords
+        return coords[lo:hi] if self.enc_B is not None else self.encoder.embedding(coords[lo:hi]).contiguous()
+
+    def _begin_shuffled(self, epoch: int, it: int) -> int:
+        """Shuffled fits: the batch index step() works with (INRTrainer._begin_shuffled).  A refill of the epoch buffers
+        also recounts, per batch and disc, the rows outside the disc (the consistency term's mean): one batched op over
+        the epoch's dist and one read-back."""
+        if self._coil_order is not None:
+            return self._coil_order.at(epoch, it)
+        if self._epoch_buf.begin(epoch):
+            d = self._t_dist
+            rows = []
+            if self.pairs[:-1]:
+                flags = torch.stack([(d < blo) | (d > bhi) for (blo, bhi) in self.pairs[:-1]])
+                rows = self._epoch_buf.batch_sums(flags).tolist()
+            self._cons_epoch = [ConsistencySpec(0.1, self.pairs, [1.0 / (2.0 * r[b]) if r[b] else 0.0 for r in rows] + [0.0], 2)
+                                for b in range(self._epoch_buf.n_batches)]
+        return it
 
     def _cons_spec(self, it: int, lo: int, hi: int) -> ConsistencySpec:
+        if self._epoch_buf is not None:
+            return self._cons_epoch[it]
         if it not in self._cons:
             # (numpy, not torch: a torch CPU reduction per step leaves its worker threads spinning, which drove the container
             # into its CPU quota -- 87 ms stalls, profiles/r03_config5_steps.txt; here: a first visit of every batch of epoch 0)
@@ -147,8 +180,13 @@ class MultiscaleTrainer(ValidationMixin):
         return loss
 
     def step(self, epoch: int, it: int) -> torch.Tensor:
+        if self.shuffle:
+            it = self._begin_shuffled(epoch, it)
         lo, hi = it * self.bs, min((it + 1) * self.bs, self.n)
-        count = hi - lo if self._mask_cum is None else self._mask_cum[hi] - self._mask_cum[lo]
+        if self._epoch_buf is not None:
+            count = self._epoch_buf.counts[it]
+        else:
+            count = hi - lo if self._mask_cum is None else self._mask_cum[hi] - self._mask_cum[lo]
         if self.use_tv:
             loss = self._tv_step(it, lo, hi, count)
         else:
@@ -157,9 +195,9 @@ class MultiscaleTrainer(ValidationMixin):
                 self.engine.grads.zero_()
                 loss = torch.zeros((), device=self.device)
             else:
-                loss = self.engine.train_step(self._inputs(slo, shi), self.enc_B, self.image[slo:shi], self.loss,
-                                              count=count, mask=None if self.mask is None else self.mask[slo:shi],
-                                              dist=self.dist[slo:shi], scale=self.scale,
+                loss = self.engine.train_step(self._inputs(slo, shi, True), self.enc_B, self._t_image[slo:shi], self.loss,
+                                              count=count, mask=None if self.mask is None else self._t_mask[slo:shi],
+                                              dist=self._t_dist[slo:shi], scale=self.scale,
                                               cons=self._cons_spec(it, lo, hi))
         lr = self.config["lr"] * lr_factor(epoch, self.config["max_epoch"])
         loss = exchange_and_update(self.engine, loss, self.world, self.pg, self.sharded_update, lr, self.config["beta1"],
@@ -232,7 +270,7 @@ def main():
     import argparse
 
     from .synthetic import make_kspace
-    from .train import get_config, run_cli
+    from .train import add_shuffle_flags, apply_shuffle_flags, get_config, run_cli
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, required=True)
     ap.add_argument("--data_samples", type=str, default="")
@@ -242,8 +280,9 @@ def main():
     ap.add_argument("--max_steps", type=int, default=None)
     ap.add_argument("--val", action="store_true",
                     help="validate every config['val_epoch'] epochs and checkpoint every config['image_save_epoch']")
+    add_shuffle_flags(ap)
     opts = ap.parse_args()
-    config = set_default_configs(get_config(opts.config))
+    config = apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts)
     if config["model"] not in ("BoundedFourier",):
         config["model"] = "MultiscaleKFourier"  # train_kspace_multiscale.py:93-98: anything else is the unbounded net
     if opts.synthetic:

@@ -11,7 +11,8 @@ Parallel mapping: ring i is owned by rank i % world.  Models are independent, so
 training; the evaluation sweep adds the ranks' disjoint contributions with one SUM all-reduce.
 
 Kept different from the stale reference script, on purpose: batches are the sequential unshuffled ranges of the
-maintained loops (the script shuffles), and the +-N(0, 0.05) jitter of the ring bounds (:166-167, an unseeded numpy
+maintained loops (the script shuffles; ``config["shuffle"]`` opts into the keyed per-epoch permutation of
+inr_mi355x/shuffle.py -- not the script's DataLoader order, which nothing pins down), and the +-N(0, 0.05) jitter of the ring bounds (:166-167, an unseeded numpy
 draw per model per step) is off by default and seeded when enabled.
 """
 from __future__ import annotations
@@ -25,6 +26,7 @@ import torch
 from .engine import LossSpec
 from .evalchain import psnr, reconstruct
 from .networks import Positional_Encoder
+from .shuffle import EpochBuffers, shuffle_settings
 from .train import MODELS, MFN_MODELS, lr_factor, set_default_configs
 from .validation import ValidationMixin
 
@@ -47,6 +49,7 @@ class RingEnsembleTrainer(ValidationMixin):
                  radii: Optional[Sequence[float]] = None, seed: int = 0, rank: int = 0, world: int = 1,
                  process_group=None, jitter: float = 0.0):
         config = set_default_configs(dict(config))
+        self.shuffle, self.shuffle_seed = shuffle_settings(config, seed)
         self.config, self.device = config, torch.device(device)
         self.rank, self.world, self.pg = rank, world, process_group
         self.shape = shape
@@ -88,33 +91,61 @@ class RingEnsembleTrainer(ValidationMixin):
         self.jitter = float(jitter)
         self._rng = np.random.RandomState(seed)
         self._masks = {}
+        # config['shuffle']: batches are views of the epoch buffers (every rank fills its own with the same order);
+        # predict_all / evaluate / metrics keep reading the unshuffled data
+        self._epoch_buf = None
+        self._t_coords, self._t_image, self._t_dist = self.coords, self.image, self.dist
+        if self.shuffle:
+            self._epoch_buf = EpochBuffers(self.shuffle_seed, self.bs, self.coords, self.image)
+            self._t_coords, self._t_image = self._epoch_buf.coords, self._epoch_buf.image
 
-    def _inputs(self, lo: int, hi: int):
+    def _inputs(self, lo: int, hi: int, train: bool = False):
+        coords = self._t_coords if train else self.coords
         emb = self.config["encoder"]["embedding"]
         if self.enc_B is not None or emb == "none":
-            return self.coords[lo:hi]
-        return self.encoder.embedding(self.coords[lo:hi])
+            return coords[lo:hi]
+        return self.encoder.embedding(coords[lo:hi])
+
+    def _begin_shuffled(self, epoch: int) -> None:
+        """First step of a shuffled epoch: refill the epoch buffers, then every ring's row mask over the whole buffer and
+        its per-batch counts -- one batched op and one read-back (the cached masks are tied to the batches' contents)."""
+        if not self._epoch_buf.begin(epoch):
+            return
+        c = self._t_coords
+        self._t_dist = d = torch.sqrt(c[:, 1] ** 2 + c[:, 2] ** 2)
+        self._masks = {}
+        if self.jitter > 0.0:
+            return
+        masks = torch.stack([((d >= self.radii[i]) & (d <= self.radii[i + 1])).to(torch.uint8)
+                             for i in range(self.no_models)])
+        counts = self._epoch_buf.batch_sums(masks).tolist()
+        for i in range(self.no_models):
+            for b in range(self._epoch_buf.n_batches):
+                lo = b * self.bs
+                self._masks[(i, lo)] = (masks[i, lo:min(lo + self.bs, self.n)], counts[i][b])
 
     def _ring_mask(self, i: int, lo: int, hi: int):
         r0, r1 = self.radii[i], self.radii[i + 1]
         if self.jitter > 0.0:  # train_clustering.py:166-167 (every rank draws for every ring: same stream everywhere)
             r0 = max(0.0, r0 - abs(self._rng.normal(0, self.jitter)))
             r1 = r1 + abs(self._rng.normal(0, self.jitter))
-            d = self.dist[lo:hi]
+            d = self._t_dist[lo:hi]
             m = ((d >= r0) & (d <= r1)).to(torch.uint8)
             return m, int(m.sum())
         key = (i, lo)
         if key not in self._masks:
-            d = self.dist[lo:hi]
+            d = self._t_dist[lo:hi]
             m = ((d >= r0) & (d <= r1)).to(torch.uint8).contiguous()
             self._masks[key] = (m, int(m.sum()))
         return self._masks[key]
 
     def step(self, epoch: int, it: int) -> List[Optional[float]]:
         """One batch through every owned ring model; returns the per-ring losses (None: ring absent from the batch)."""
+        if self.shuffle:
+            self._begin_shuffled(epoch)
         lo, hi = it * self.bs, min((it + 1) * self.bs, self.n)
         lr = self.config["lr"] * lr_factor(epoch, self.config["max_epoch"])
-        x, gt = self._inputs(lo, hi), self.image[lo:hi]
+        x, gt = self._inputs(lo, hi, True), self._t_image[lo:hi]
         out: List[Optional[torch.Tensor]] = [None] * self.no_models
         for i in range(self.no_models):
             mask, cnt = self._ring_mask(i, lo, hi)  # drawn for every ring to keep the jitter stream rank-independent
