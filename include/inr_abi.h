@@ -9,7 +9,8 @@
  *     (thread-local); nothing throws or aborts across the ABI;
  *   - all tensor arguments are DEVICE pointers to contiguous row-major fp32 buffers owned by the
  *     caller -- except inr_image_metrics' `metrics_out` and `scratch`, which are fp64 (double) device buffers, and
- *     inr_shuffle_epoch's integer buffers (uint8 masks, int32 counts, int64 order); the
+ *     inr_shuffle_epoch's integer buffers (uint8 masks, int32 counts, int64 order), inr_gray8's uint8 `lut` / `out` and
+ *     inr_coil_stats' fp64 `stats` / `scratch`; the
  *     library retains no pointer across calls and allocates no device memory -- with ONE exception:
  *     an INR_PRECISION_BF16 plan owns 64 bytes of device memory (16 words), its gradient-scale state (inr_plan_grad_scale_state),
  *     allocated with hipMalloc and initialised with a synchronous hipMemcpy by the first call that needs it on a device
@@ -44,7 +45,8 @@ extern "C" {
 /* 7: inr_adam_step_shard (data-parallel update on the entries a rank owns), inr_reg_grad (penalty gradients, complex64 tensors
  *    included; the Adam entry points refuse l1 / l2 != 0 on plans with complex tensors).
  *    v7 additions (no version change: nothing existing moved): inr_image_metrics_scratch, inr_image_metrics (RSS, PSNR, SSIM of
- *    the validation epoch); inr_shuffle_epoch (the keyed row permutation of a shuffled epoch).
+ *    the validation epoch); inr_shuffle_epoch (the keyed row permutation of a shuffled epoch); inr_kspace_display, inr_gray8,
+ *    inr_coil_stats and their scratch queries (the pictures and the per-coil table of the validation epoch).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -401,6 +403,41 @@ int inr_image_metrics(const float* coils, int64_t C, int64_t H, int64_t W, const
 int inr_shuffle_epoch(int64_t n, int64_t batch_size, uint64_t seed, uint32_t epoch, const float* coords,
                       const float* gt, const float* dist, const uint8_t* mask, float* coords_out, float* gt_out,
                       float* dist_out, uint8_t* mask_out, int32_t* batch_counts, int64_t* order_out, void* stream);
+
+/* (v7 additions) The pictures and the per-coil table of the validation epoch (train.py:221-238, models/utils.py:254-287).
+ * All three: no atomics, fixed-order two-stage reductions (bitwise reproducible), no host synchronisation, nothing
+ * allocated, capturable in a graph; scratch is the caller's, its size comes from the matching *_scratch query.
+ *
+ * inr_kspace_display -- the is_kspace branch of save_im (models/utils.py:262-267) in fp32: `coils` [C,H,W,2]; `minus`
+ * [C,H,W,2] or NULL (non-NULL: the input is coils - minus, the error picture of train.py:225); both 8-byte aligned.
+ *   g = sqrt(sum_c |z_c|^2), |z| = sqrt(re^2 + im^2);  g *= expm1(smoothing_factor) / max(g);  g = log1p(g);
+ *   out [H,W] = g / max(g), in 0..1.
+ * max propagates NaN (torch.max).  An all-zero input gives NaN in every pixel, as the reference's 0 * (expm1(sf) / 0) does.
+ * Three launches on `stream`; scratch = scratch_floats fp32 words.
+ *
+ * inr_gray8 -- the byte plt.imsave(..., format="png", cmap="gray") stores in the R (= G = B) channel for img [H,W]:
+ *   x = |img| when take_abs (save_im's np.abs, models/utils.py:257,260), else img;
+ *   vmin, vmax = the arguments when has_range != 0 (vmin <= vmax, else INR_ERR_INVALID), else the extrema of the finite x;
+ *   n = (x - vmin) / (vmax - vmin) in fp32, n = 0 everywhere when vmax == vmin (a constant picture is all zeros);
+ *   index = min(floor(256 n), 255), 0 for n < 0, 255 for n > 1;  out [H,W] uint8 = lut[index].
+ * `lut` = 256 device bytes, matplotlib's table for the 'gray' map -- uint8(trunc(i * (1 / 255) * 255)) in float64, which is
+ * NOT the identity (i - 1 at i = 33, 37, 41, ...); the caller uploads it once.  Non-finite pixels are masked by
+ * matplotlib: byte 0 here, NaN in norm_out.  norm_out [H,W] fp32 (may be NULL) receives n.  scratch (scratch_floats fp32
+ * words) is only touched when has_range == 0 and may be NULL otherwise.  One launch with a range, two without.
+ *
+ * inr_coil_stats -- stats_per_coil (models/utils.py:274-283): coils [C,H,W,2] (8-byte aligned, C <= 65535) ->
+ * stats [C,4] fp64 = mean, std (unbiased, n - 1: torch.Tensor.std's default), max, min over the 2 H W values of each
+ * coil.  Sums are accumulated in fp64, the deviations in a second pass from the fp64 mean; max / min are exact.  Inputs
+ * are taken as finite.  Three launches; scratch = scratch_doubles fp64 words. */
+int inr_kspace_display_scratch(int64_t C, int64_t H, int64_t W, int64_t* scratch_floats);
+int inr_kspace_display(const float* coils, const float* minus, int64_t C, int64_t H, int64_t W, float smoothing_factor,
+                       float* out, float* scratch, int64_t scratch_floats, void* stream);
+int inr_gray8_scratch(int64_t H, int64_t W, int64_t* scratch_floats);
+int inr_gray8(const float* img, int64_t H, int64_t W, int32_t take_abs, int32_t has_range, float vmin, float vmax,
+              const uint8_t* lut, uint8_t* out, float* norm_out, float* scratch, int64_t scratch_floats, void* stream);
+int inr_coil_stats_scratch(int64_t C, int64_t H, int64_t W, int64_t* scratch_doubles);
+int inr_coil_stats(const float* coils, int64_t C, int64_t H, int64_t W, double* stats, double* scratch,
+                   int64_t scratch_doubles, void* stream);
 
 #ifdef __cplusplus
 }

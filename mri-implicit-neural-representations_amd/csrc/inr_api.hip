@@ -1494,6 +1494,95 @@ int inr_image_metrics(const float* coils, int64_t C, int64_t H, int64_t W, const
   return INR_OK;
 }
 
+// ---- pictures and per-coil table of the validation epoch (inr_display.hip) ----
+int inr_kspace_display_scratch(int64_t C, int64_t H, int64_t W, int64_t* scratch_floats) {
+  if (scratch_floats == nullptr) return fail(INR_ERR_INVALID, "inr_kspace_display_scratch: null argument");
+  const int rc = image_metrics_check(C, H, W, "inr_kspace_display_scratch");
+  if (rc != INR_OK) return rc;
+  *scratch_floats = inr::kspace_display_scratch_floats(H, W);
+  return INR_OK;
+}
+
+int inr_kspace_display(const float* coils, const float* minus, int64_t C, int64_t H, int64_t W, float smoothing_factor,
+                       float* out, float* scratch, int64_t scratch_floats, void* stream) {
+  if (coils == nullptr || out == nullptr || scratch == nullptr)
+    return fail(INR_ERR_INVALID, "inr_kspace_display: null argument");
+  const int rc = image_metrics_check(C, H, W, "inr_kspace_display");
+  if (rc != INR_OK) return rc;
+  if (((uintptr_t)coils | (uintptr_t)minus) & 7u)
+    return fail(INR_ERR_INVALID, "inr_kspace_display: coils / minus must be 8-byte aligned ((re, im) pairs move as one load)");
+  if (!(smoothing_factor == smoothing_factor))
+    return fail(INR_ERR_INVALID, "inr_kspace_display: smoothing_factor is NaN");
+  const long long need = inr::kspace_display_scratch_floats(H, W);
+  if (scratch_floats < need)
+    return fail(INR_ERR_INVALID, "inr_kspace_display: scratch holds %lld floats, needs %lld", (long long)scratch_floats, need);
+  // torch.expm1 of the fp32 scalar (models/utils.py:264-265): evaluated in double here and rounded once
+  const float em = (float)std::expm1((double)smoothing_factor);
+  hipError_t e = inr::launch_kspace_display(coils, minus, (int)C, (int)H, (int)W, em, out, scratch, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "inr_kspace_display");
+  return INR_OK;
+}
+
+int inr_gray8_scratch(int64_t H, int64_t W, int64_t* scratch_floats) {
+  if (scratch_floats == nullptr) return fail(INR_ERR_INVALID, "inr_gray8_scratch: null argument");
+  const int rc = image_metrics_check(1, H, W, "inr_gray8_scratch");
+  if (rc != INR_OK) return rc;
+  *scratch_floats = inr::gray8_scratch_floats(H, W);
+  return INR_OK;
+}
+
+int inr_gray8(const float* img, int64_t H, int64_t W, int32_t take_abs, int32_t has_range, float vmin, float vmax,
+              const uint8_t* lut, uint8_t* out, float* norm_out, float* scratch, int64_t scratch_floats, void* stream) {
+  if (img == nullptr || lut == nullptr || out == nullptr) return fail(INR_ERR_INVALID, "inr_gray8: null argument");
+  const int rc = image_metrics_check(1, H, W, "inr_gray8");
+  if (rc != INR_OK) return rc;
+  if (has_range) {
+    if (!(vmin <= vmax))  // matplotlib.colors.Normalize raises the same way
+      return fail(INR_ERR_INVALID, "inr_gray8: minvalue must be less than or equal to maxvalue (vmin %g, vmax %g)",
+                  (double)vmin, (double)vmax);
+  } else {
+    const long long need = inr::gray8_scratch_floats(H, W);
+    if (scratch == nullptr || scratch_floats < need)
+      return fail(INR_ERR_INVALID, "inr_gray8: scratch holds %lld floats, needs %lld",
+                  scratch == nullptr ? 0LL : (long long)scratch_floats, need);
+  }
+  hipError_t e = inr::launch_gray8(img, (int)H, (int)W, take_abs != 0, has_range != 0, vmin, vmax, lut, out, norm_out,
+                                   scratch, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "inr_gray8");
+  return INR_OK;
+}
+
+static int coil_stats_check(int64_t C, int64_t H, int64_t W, const char* who) {
+  const int rc = image_metrics_check(C, H, W, who);
+  if (rc != INR_OK) return rc;
+  if (C > 65535) return fail(INR_ERR_INVALID, "%s: C %lld (one grid row per coil: at most 65535)", who, (long long)C);
+  return INR_OK;
+}
+
+int inr_coil_stats_scratch(int64_t C, int64_t H, int64_t W, int64_t* scratch_doubles) {
+  if (scratch_doubles == nullptr) return fail(INR_ERR_INVALID, "inr_coil_stats_scratch: null argument");
+  const int rc = coil_stats_check(C, H, W, "inr_coil_stats_scratch");
+  if (rc != INR_OK) return rc;
+  *scratch_doubles = inr::coil_stats_scratch_doubles(C, H, W);
+  return INR_OK;
+}
+
+int inr_coil_stats(const float* coils, int64_t C, int64_t H, int64_t W, double* stats, double* scratch,
+                   int64_t scratch_doubles, void* stream) {
+  if (coils == nullptr || stats == nullptr || scratch == nullptr)
+    return fail(INR_ERR_INVALID, "inr_coil_stats: null argument");
+  const int rc = coil_stats_check(C, H, W, "inr_coil_stats");
+  if (rc != INR_OK) return rc;
+  if ((uintptr_t)coils & 7u)
+    return fail(INR_ERR_INVALID, "inr_coil_stats: coils must be 8-byte aligned ((re, im) pairs move as one load)");
+  const long long need = inr::coil_stats_scratch_doubles(C, H, W);
+  if (scratch_doubles < need)
+    return fail(INR_ERR_INVALID, "inr_coil_stats: scratch holds %lld doubles, needs %lld", (long long)scratch_doubles, need);
+  hipError_t e = inr::launch_coil_stats(coils, (int)C, (int)H, (int)W, stats, scratch, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "inr_coil_stats");
+  return INR_OK;
+}
+
 // key schedule of the epoch permutation (inr_mi355x/shuffle.py round_keys is the same text in Python)
 static uint32_t shuffle_mix(uint32_t x) {
   x ^= x >> 16;

@@ -101,6 +101,16 @@ long long image_metrics_scratch_doubles(long long H, long long W);
 hipError_t launch_image_metrics(const float* coils, int C, int H, int W, const float* ref, float* rss_out,
                                 double* metrics_out, double* scratch, hipStream_t st);
 
+// pictures and per-coil table of the validation epoch (inr_display.hip)
+long long kspace_display_scratch_floats(long long H, long long W);
+hipError_t launch_kspace_display(const float* coils, const float* minus, int C, int H, int W, float expm1_sf, float* out,
+                                 float* scratch, hipStream_t st);
+long long gray8_scratch_floats(long long H, long long W);
+hipError_t launch_gray8(const float* img, int H, int W, int take_abs, int has_range, float vmin, float vmax,
+                        const unsigned char* lut, unsigned char* out, float* norm_out, float* scratch, hipStream_t st);
+long long coil_stats_scratch_doubles(long long C, long long H, long long W);
+hipError_t launch_coil_stats(const float* coils, int C, int H, int W, double* stats, double* scratch, hipStream_t st);
+
 // shuffled epochs (inr_aux.hip): round keys of (seed, epoch) and the half width of the Feistel domain,
 // both made on the host (inr_api.hip shuffle_keys)
 #define SHUFFLE_ROUNDS 6

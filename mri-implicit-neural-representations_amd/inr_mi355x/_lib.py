@@ -102,6 +102,13 @@ SYMBOLS = {
     "inr_image_metrics": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
     "inr_shuffle_epoch": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                     _P]),
+    "inr_kspace_display_scratch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "inr_kspace_display": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, _P, C.c_int64, _P]),
+    "inr_gray8_scratch": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "inr_gray8": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P,
+                            C.c_int64, _P]),
+    "inr_coil_stats_scratch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "inr_coil_stats": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
 }
 METRICS_WORDS = 8  # inr_image_metrics' metrics_out: psnr, ssim, sse, max_ref, min_ref, max_rec, min_rec, data_range
 

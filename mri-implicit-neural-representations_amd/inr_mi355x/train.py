@@ -12,9 +12,13 @@ config values raise instead of falling through.
 
 CLI (same flags as the reference, train.py:255-258):
     python -m inr_mi355x.train --config cfg.yaml [--output_path out] [--synthetic C,H,W] [--val]
-                               [--shuffle] [--shuffle-seed S]
+                               [--shuffle] [--shuffle-seed S] [--save-images] [--data_samples samples.yaml]
 --val runs the reference's validation epoch every config['val_epoch'] epochs (its line is printed) and saves a
-checkpoint every config['image_save_epoch'] epochs.
+checkpoint every config['image_save_epoch'] epochs.  --save-images (with --val) also writes the reference's pictures
+(train.png, train_kspace.png, recon_kspace_{e}dB.png, recon_kspace_{e}_error.png, recon_{e}_{psnr}_psnr_{ssim}_ssim.png)
+to <output_path>/images, moves the checkpoints to <output_path>/checkpoints (models/utils.py:35-44) and prints the
+per-coil table after each validation line.  --data_samples names a YAML ``samples: {sample: [slices...]}``: one fit per
+(sample, slice) in <output_path>/sample_{s}_slice_{k}/, one JSON line each (train.py:292-318).
 """
 from __future__ import annotations
 
@@ -527,6 +531,9 @@ class INRTrainer(ValidationMixin):
         m = self._device_metrics(self.image_full, pred, bool(self.config.get("transform", False)))
         return self._finish_validation(epoch, m, loss_sum, self.steps_per_epoch)
 
+    def _display_source(self):
+        return self.image_full, bool(self.config.get("transform", False))
+
     @torch.no_grad()
     def metrics(self) -> dict:
         """PSNR and SSIM of the current model (validate() without the test loss and the best-epoch record)."""
@@ -563,17 +570,56 @@ def main():
     ap.add_argument("--val", action="store_true",
                     help="validate every config['val_epoch'] epochs and checkpoint every config['image_save_epoch']")
     add_shuffle_flags(ap)
+    add_image_flags(ap)
     opts = ap.parse_args()
+    check_image_flags(ap, opts)
     config = apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts)
-    if opts.synthetic:
-        C, H, W = (int(v) for v in opts.synthetic.split(","))
-        image, coords, shape = make_kspace(C, H, W, normalization=config.get("normalization", "coil"),
-                                           image_space=bool(config.get("transform", False)))
-    else:  # train.py:271-287: config['data_root'/'data'/'set'/'sample'/'slice'] (or 'custom_file_or_path')
-        from .datasets import from_config, trainer_inputs
-        image, coords, shape = trainer_inputs(from_config(config, "cuda"))
-    tr = INRTrainer(config, image, coords, shape, "cuda")
-    run_cli(tr, config, opts)
+    for cfg, fit_opts in cli_fits(config, opts):
+        if opts.synthetic:
+            C, H, W = (int(v) for v in opts.synthetic.split(","))
+            image, coords, shape = make_kspace(C, H, W, normalization=cfg.get("normalization", "coil"),
+                                               image_space=bool(cfg.get("transform", False)))
+        else:  # train.py:271-287: config['data_root'/'data'/'set'/'sample'/'slice'] (or 'custom_file_or_path')
+            from .datasets import from_config, trainer_inputs
+            image, coords, shape = trainer_inputs(from_config(cfg, "cuda"))
+        tr = INRTrainer(cfg, image, coords, shape, "cuda")
+        run_cli(tr, cfg, fit_opts)
+
+
+def add_image_flags(ap) -> None:
+    ap.add_argument("--save-images", action="store_true",
+                    help="with --val: write the reference's pictures to <output_path>/images, checkpoints to "
+                         "<output_path>/checkpoints, and print the per-coil table after each validation line")
+
+
+def check_image_flags(ap, opts) -> None:
+    if opts.save_images and not opts.val:
+        ap.error("--save-images needs --val (the pictures are those of the validation epoch)")
+
+
+def expand_data_samples(config: dict, samples) -> list:
+    """train.py:292-318: ``samples`` = {sample: [slices...]} (the 'samples' entry of the --data_samples YAML) ->
+    [(config_i, subdir)], one fit per (sample, slice) with config_i['sample'] / ['slice'] set from the loop (as
+    training_script(sample=sample, slice_no=_slice) is called there) and subdir 'sample_{s}_slice_{k}'.  Empty or None:
+    the single fit of the config itself, in place ([(config, '')])."""
+    if not samples:
+        return [(config, "")]
+    fits = []
+    for sample, slices in samples.items():
+        for k in slices:
+            cfg = dict(config)
+            cfg["sample"], cfg["slice"] = sample, k
+            fits.append((cfg, "sample_{}_slice_{}".format(sample, k)))
+    return fits
+
+
+def cli_fits(config: dict, opts):
+    """(config_i, opts_i) of every fit a command line asks for: one, or one per (sample, slice) of --data_samples,
+    each with its own output folder."""
+    samples = (get_config(opts.data_samples) or {}).get("samples") if opts.data_samples else None
+    for cfg, sub in expand_data_samples(config, samples):
+        o = opts if not sub else argparse.Namespace(**dict(vars(opts), output_path=os.path.join(opts.output_path, sub)))
+        yield cfg, o
 
 
 def add_shuffle_flags(ap) -> None:
@@ -592,16 +638,27 @@ def apply_shuffle_flags(config: dict, opts) -> dict:
 
 
 def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
-    """Fit, then print the JSON result (and, with --val, the reference's validation lines and checkpoints)."""
+    """Fit, then print the JSON result (and, with --val, the reference's validation lines and checkpoints; with
+    --save-images, the pictures and the per-coil table as well)."""
     os.makedirs(opts.output_path, exist_ok=True)
+    ckpt_dir, image_dir = opts.output_path, None
+    if getattr(opts, "save_images", False):  # train.py:45-46,136-143: the folder tree, then the training pictures
+        from .display import coil_stats_table, prepare_sub_folder
+        ckpt_dir, image_dir = prepare_sub_folder(opts.output_path)
+        tr.enable_validation_images()
+        tr.save_training_images(image_dir)
     kw = {}
     if opts.val:
         def on_validate(rec):
             print(tr.validation_line(rec, config["max_epoch"]), flush=True)
+            if image_dir is not None:
+                stats = tr.save_validation_images(rec["epoch"], rec, image_dir)
+                if not tr._display_source()[1]:  # train.py:226: the table belongs to the k-space branch
+                    print(coil_stats_table(stats), flush=True)
 
         def on_epoch_end(epoch):  # train.py:244-250
             if (epoch + 1) % config["image_save_epoch"] == 0:
-                torch.save(tr.checkpoint(), os.path.join(opts.output_path, "model_%06d.pt" % (epoch + 1)))
+                torch.save(tr.checkpoint(), os.path.join(ckpt_dir, "model_%06d.pt" % (epoch + 1)))
 
         kw = dict(val_epoch=config["val_epoch"], on_validate=on_validate, on_epoch_end=on_epoch_end)
     t0 = time.time()
@@ -616,7 +673,7 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
         res["validation"] = tr.val_history
         res.update(best_psnr=tr.best_psnr, best_psnr_ep=tr.best_psnr_ep, best_ssim=tr.best_ssim,
                    best_ssim_ep=tr.best_ssim_ep)
-    torch.save(tr.checkpoint(), os.path.join(opts.output_path, "model_%06d.pt" % tr.global_step))
+    torch.save(tr.checkpoint(), os.path.join(ckpt_dir, "model_%06d.pt" % tr.global_step))
     print(json.dumps(res))
 
 

@@ -257,6 +257,9 @@ class MultiscaleTrainer(ValidationMixin):
         m = self._device_metrics(self.image_full, pred, False)
         return self._finish_validation(epoch, m, loss_sum, self.steps_per_epoch)
 
+    def _display_source(self):
+        return self.image_full, False
+
     @torch.no_grad()
     def metrics(self) -> dict:
         """PSNR and SSIM of the current model's last head."""
@@ -265,12 +268,13 @@ class MultiscaleTrainer(ValidationMixin):
 
 
 def main():
-    """CLI with the reference's flags (train_kspace_multiscale.py:50-52): --config, --output_path; the scan
-    comes from datasets.py, or a synthetic k-space with --synthetic C,H,W."""
+    """CLI with the reference's flags (train_kspace_multiscale.py:50-52): --config, --output_path, --data_samples; the scan
+    comes from datasets.py, or a synthetic k-space with --synthetic C,H,W.  --val / --save-images as inr_mi355x.train."""
     import argparse
 
     from .synthetic import make_kspace
-    from .train import add_shuffle_flags, apply_shuffle_flags, get_config, run_cli
+    from .train import (add_image_flags, add_shuffle_flags, apply_shuffle_flags, check_image_flags, cli_fits, get_config,
+                        run_cli)
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, required=True)
     ap.add_argument("--data_samples", type=str, default="")
@@ -281,19 +285,22 @@ def main():
     ap.add_argument("--val", action="store_true",
                     help="validate every config['val_epoch'] epochs and checkpoint every config['image_save_epoch']")
     add_shuffle_flags(ap)
+    add_image_flags(ap)
     opts = ap.parse_args()
+    check_image_flags(ap, opts)
     config = apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts)
     if config["model"] not in ("BoundedFourier",):
         config["model"] = "MultiscaleKFourier"  # train_kspace_multiscale.py:93-98: anything else is the unbounded net
-    if opts.synthetic:
-        C, H, W = (int(v) for v in opts.synthetic.split(","))
-        image, coords, shape = make_kspace(C, H, W, normalization=config.get("normalization", "max"))
-    else:  # train_kspace_multiscale.py:57-72: the scan named by config['data_root'/'data'/'set'/'sample'/'slice']
-        from .datasets import from_config, trainer_inputs
-        image, coords, shape = trainer_inputs(from_config(config, "cuda"))
-    dist = torch.sqrt(coords[:, 1] ** 2 + coords[:, 2] ** 2)
-    tr = MultiscaleTrainer(config, image, coords, dist, None, shape, "cuda")
-    run_cli(tr, config, opts, extra={"radii": tr.radii})
+    for cfg, fit_opts in cli_fits(config, opts):  # one fit, or one per (sample, slice) of --data_samples
+        if opts.synthetic:
+            C, H, W = (int(v) for v in opts.synthetic.split(","))
+            image, coords, shape = make_kspace(C, H, W, normalization=cfg.get("normalization", "max"))
+        else:  # train_kspace_multiscale.py:57-72: the scan named by config['data_root'/'data'/'set'/'sample'/'slice']
+            from .datasets import from_config, trainer_inputs
+            image, coords, shape = trainer_inputs(from_config(cfg, "cuda"))
+        dist = torch.sqrt(coords[:, 1] ** 2 + coords[:, 2] ** 2)
+        tr = MultiscaleTrainer(cfg, image, coords, dist, None, shape, "cuda")
+        run_cli(tr, cfg, fit_opts, extra={"radii": tr.radii})
 
 
 if __name__ == "__main__":

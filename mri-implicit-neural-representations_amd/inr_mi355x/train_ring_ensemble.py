@@ -193,6 +193,9 @@ class RingEnsembleTrainer(ValidationMixin):
         ref = reconstruct(self.image, self.shape, in_image_space)
         return float(psnr(ref, reconstruct(self.predict_all(), self.shape, in_image_space)))
 
+    def _display_source(self):
+        return self.image, bool(self.config.get("transform", False))
+
     @torch.no_grad()
     def metrics(self) -> dict:
         """PSNR and SSIM of the assembled reconstruction on the device (the reference's ring loop has no validation
@@ -204,3 +207,62 @@ class RingEnsembleTrainer(ValidationMixin):
     def checkpoints(self) -> dict:
         """{ring: {'net', 'enc'}} of the owned rings (submodel_%d files of train_clustering.py:243-249)."""
         return {i: {"net": self.models[i].state_dict(), "enc": self.encoder.B} for i in self.owned}
+
+
+def main():
+    """python -m inr_mi355x.train_ring_ensemble --config cfg.yaml [--output_path out] [--synthetic C,H,W]
+    [--max_steps N] [--shuffle] [--shuffle-seed S] [--save-images]: fit the rings (radii from config['partition']), print
+    one JSON line with the assembled reconstruction's PSNR / SSIM and save the submodel_%d files of
+    train_clustering.py:243-249.  --save-images writes train.png / train_kspace.png and the final metrics()' pictures
+    to <output_path>/images (the ring loop has no validation epoch), the submodels to <output_path>/checkpoints, and
+    prints the per-coil table."""
+    import argparse
+    import json
+    import os
+    import time
+
+    from .synthetic import make_kspace
+    from .train import add_image_flags, add_shuffle_flags, apply_shuffle_flags, get_config
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", type=str, required=True)
+    ap.add_argument("--output_path", type=str, default=".")
+    ap.add_argument("--synthetic", type=str, default=None,
+                    help="C,H,W: fit a synthetic k-space of that shape instead of the scan the config names")
+    ap.add_argument("--max_steps", type=int, default=None)
+    add_shuffle_flags(ap)
+    add_image_flags(ap)
+    opts = ap.parse_args()
+    config = apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts)
+    if opts.synthetic:
+        C, H, W = (int(v) for v in opts.synthetic.split(","))
+        image, coords, shape = make_kspace(C, H, W, normalization=config.get("normalization", "coil"),
+                                           image_space=bool(config.get("transform", False)))
+    else:
+        from .datasets import from_config, trainer_inputs
+        image, coords, shape = trainer_inputs(from_config(config, "cuda"))
+    tr = RingEnsembleTrainer(config, image, coords, shape, "cuda")
+    os.makedirs(opts.output_path, exist_ok=True)
+    ckpt_dir, image_dir = opts.output_path, None
+    if opts.save_images:
+        from .display import coil_stats_table, prepare_sub_folder
+        ckpt_dir, image_dir = prepare_sub_folder(opts.output_path)
+        tr.enable_validation_images()
+        tr.save_training_images(image_dir)
+    t0 = time.time()
+    tr.fit(opts.max_steps, log_every=config.get("log_iter", 20))
+    torch.cuda.synchronize()
+    res = {"steps": tr.global_step, "seconds": time.time() - t0, "radii": tr.radii, "shuffle": tr.shuffle,
+           "shuffle_seed": tr.shuffle_seed if tr.shuffle else None}
+    res.update(tr.metrics())
+    if image_dir is not None:
+        last_epoch = max(0, -(-tr.global_step // tr.steps_per_epoch) - 1)
+        stats = tr.save_validation_images(last_epoch, res, image_dir)
+        if not tr._display_source()[1]:
+            print(coil_stats_table(stats), flush=True)
+    for i, sd in tr.checkpoints().items():
+        torch.save(sd, os.path.join(ckpt_dir, "submodel_%d.pt" % i))
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,8 +1,10 @@
 """Validation epoch of the reference's loops (train.py:199-242, train_kspace_multiscale.py:202-250), shared by the
 trainers: predictions -> coil images -> RSS / PSNR / SSIM in the library's kernels (evalchain.image_metrics), the
-"best @ epoch" record and the line the reference prints."""
+"best @ epoch" record and the line the reference prints; opt-in, the pictures and the per-coil table the reference writes
+next to them (train.py:136-143,221-238), from the same device buffers through the display kernels (display.py)."""
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -33,6 +35,9 @@ class ValidationMixin:
         self.val_history = []
         self._ref_rss = None
         self._metric_bufs = None
+        self._keep_images = False  # enable_validation_images(): keep what the pictures are made of
+        self._last_pred = None
+        self._display_bufs = None
 
     def update_best(self, epoch: int, psnr: float, ssim: float) -> None:
         if psnr > self.best_psnr:
@@ -53,7 +58,83 @@ class ValidationMixin:
             self._ref_rss = image_metrics(None, coil_images(gt_flat, self.shape, in_image_space))[0]
         rss, m, scratch = self._metric_bufs
         image_metrics(self._ref_rss, coil_images(pred_flat, self.shape, in_image_space), rss, m, scratch)
+        if self._keep_images:  # the sweep's output; its RSS image stays in the metric buffers
+            self._last_pred = pred_flat
         return m
+
+    # ---- pictures and per-coil table (opt-in; nothing below runs unless enable_validation_images() was called) ----
+    def _display_source(self):
+        """(ground-truth rows [(C*H*W),2], in_image_space) of the trainer: what validate() compares against."""
+        raise NotImplementedError
+
+    def enable_validation_images(self) -> None:
+        """From now on validate() / metrics() keep their prediction (a reference, no copy) for save_validation_images."""
+        self._keep_images = True
+
+    def _display(self):
+        from . import display as D
+        if self._display_bufs is None:
+            C, H, W = (int(v) for v in self.shape[:3])
+            dev = self.device
+            self._display_bufs = dict(
+                disp=torch.empty(H, W, device=dev), u8=torch.empty(H, W, device=dev, dtype=torch.uint8),
+                stats=torch.empty(C, 4, device=dev, dtype=torch.float64),
+                fs=torch.empty(max(D.kspace_display_scratch_floats(C, H, W), D.gray8_scratch_floats(H, W)), device=dev),
+                ds=torch.empty(D.coil_stats_scratch_doubles(C, H, W), device=dev, dtype=torch.float64))
+        return D, self._display_bufs
+
+    def _write_gray(self, D, b, path: str, img: torch.Tensor, take_abs: bool) -> str:
+        D.write_png_gray(path, D.gray8(img, take_abs=take_abs, out=b["u8"], scratch=b["fs"]).cpu())  # H*W bytes cross
+        return path
+
+    def _write_kspace(self, D, b, path: str, coils: torch.Tensor, minus: Optional[torch.Tensor] = None) -> str:
+        D.kspace_display(coils, minus, out=b["disp"], scratch=b["fs"])
+        return self._write_gray(D, b, path, b["disp"], False)
+
+    @torch.no_grad()
+    def save_training_images(self, directory: str) -> list:
+        """train.py:136-143: train_kspace.png (k-space configs: save_im(..., is_kspace=True) of the full data) and
+        train.png (the ground-truth RSS image).  Returns the paths."""
+        D, b = self._display()
+        gt, in_image_space = self._display_source()
+        C, H, W = (int(v) for v in self.shape[:3])
+        os.makedirs(directory, exist_ok=True)
+        paths = []
+        if not in_image_space:
+            paths.append(self._write_kspace(D, b, os.path.join(directory, "train_kspace.png"), gt.reshape(C, H, W, 2)))
+        if self._ref_rss is None:
+            self._ref_rss = image_metrics(None, coil_images(gt, self.shape, in_image_space))[0]
+        paths.append(self._write_gray(D, b, os.path.join(directory, "train.png"), self._ref_rss, True))
+        return paths
+
+    @torch.no_grad()
+    def save_validation_images(self, epoch: int, rec: dict, directory: str) -> torch.Tensor:
+        """The files of train.py:221-238 for the validation that has just run (0-based ``epoch``; names carry
+        epoch + 1 as there): recon_kspace_{e}dB.png and recon_kspace_{e}_error.png (k-space configs only: the prediction,
+        and the prediction minus the full data, through save_im's k-space display) and
+        recon_{e}_{psnr:.4g}_psnr_{ssim:.4g}_ssim.png (the RSS image validate() scored).  No second sweep: the prediction
+        and the RSS image are the ones validate() / metrics() left on the device.  ``rec`` (their record) gains
+        'images' (the paths) and 'coil_stats' ([C][mean, std, max, min] of the prediction).  Returns the [C,4] fp64
+        statistics on the host."""
+        if not self._keep_images or self._last_pred is None:
+            raise RuntimeError("save_validation_images: call enable_validation_images() before validate() / metrics()")
+        D, b = self._display()
+        gt, in_image_space = self._display_source()
+        C, H, W = (int(v) for v in self.shape[:3])
+        os.makedirs(directory, exist_ok=True)
+        pred = self._last_pred.reshape(C, H, W, 2)
+        e = epoch + 1
+        paths = []
+        if not in_image_space:
+            paths.append(self._write_kspace(D, b, os.path.join(directory, "recon_kspace_{}dB.png".format(e)), pred))
+            paths.append(self._write_kspace(D, b, os.path.join(directory, "recon_kspace_{}_error.png".format(e)), pred,
+                                            gt.reshape(C, H, W, 2)))
+        stats = D.coil_stats(pred, b["stats"], b["ds"]).cpu()  # 32 * C bytes cross
+        name = "recon_{}_{:.4g}_psnr_{:.4g}_ssim.png".format(e, rec["psnr"], rec["ssim"])
+        paths.append(self._write_gray(D, b, os.path.join(directory, name), self._metric_bufs[0], True))
+        rec["images"] = paths
+        rec["coil_stats"] = stats.tolist()
+        return stats
 
     def _finish_validation(self, epoch: int, m: torch.Tensor, loss_sum: Optional[torch.Tensor], n_train_batches: int):
         """The one host read of a validation: PSNR, SSIM and the summed test loss together."""
