@@ -141,6 +141,15 @@ def last_error() -> str:
     return buf.value.decode()
 
 
+# INR_ERR_UNSUPPORTED: a valid request the engine has no kernel for.  Invariant: the library returns it only BEFORE any
+# launch (today from inr_plan_create alone, csrc/inr_api.hip), so check() may raise it as NotImplementedError and the
+# hyperparameter search may record such a trial as a harmless refusal.  An entry that can fail after it has launched
+# something must return another code.
+ERR_UNSUPPORTED = -2
+
+
 def check(rc: int) -> None:
+    if rc == ERR_UNSUPPORTED:  # still a RuntimeError (NotImplementedError derives from it), told apart from a failed call
+        raise NotImplementedError(f"libinr_mi355x: error {rc}: {last_error()}")
     if rc != 0:
         raise RuntimeError(f"libinr_mi355x: error {rc}: {last_error()}")

@@ -184,7 +184,8 @@ def run_epochs(trainer, max_steps, log_every, val_epoch, on_validate, on_epoch_e
 class INRTrainer(ValidationMixin):
     def __init__(self, config: dict, image: torch.Tensor, coords: torch.Tensor, shape, device,
                  seed: int = 0, mask: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1,
-                 process_group=None, mask_seed: Optional[int] = None, graph_steps: bool = False):
+                 process_group=None, mask_seed: Optional[int] = None, graph_steps: bool = False,
+                 model_seed: Optional[int] = None):
         config = set_default_configs(dict(config))
         self.config = config
         self.shuffle, self.shuffle_seed = shuffle_settings(config, seed, graph_steps)
@@ -198,6 +199,8 @@ class INRTrainer(ValidationMixin):
         # construction order and RNG use of train.py:52-71: encoder, then model, on the CPU generator
         torch.manual_seed(seed)
         self.encoder = Positional_Encoder(config["encoder"], device=self.device)
+        if model_seed is not None:  # hp_model_training.py:46-49: the search reseeds between the encoder and the model
+            torch.manual_seed(model_seed)
         self.model = MODELS[config["model"]](config["net"]).to(self.device)
         emb = config["encoder"]["embedding"]
         self.is_mfn = config["model"] in MFN_MODELS

@@ -108,14 +108,15 @@ class ValidationMixin:
         return paths
 
     @torch.no_grad()
-    def save_validation_images(self, epoch: int, rec: dict, directory: str) -> torch.Tensor:
+    def save_validation_images(self, epoch: int, rec: dict, directory: str, prefix: str = "") -> torch.Tensor:
         """The files of train.py:221-238 for the validation that has just run (0-based ``epoch``; names carry
         epoch + 1 as there): recon_kspace_{e}dB.png and recon_kspace_{e}_error.png (k-space configs only: the prediction,
         and the prediction minus the full data, through save_im's k-space display) and
         recon_{e}_{psnr:.4g}_psnr_{ssim:.4g}_ssim.png (the RSS image validate() scored).  No second sweep: the prediction
         and the RSS image are the ones validate() / metrics() left on the device.  ``rec`` (their record) gains
         'images' (the paths) and 'coil_stats' ([C][mean, std, max, min] of the prediction).  Returns the [C,4] fp64
-        statistics on the host."""
+        statistics on the host.  ``prefix`` goes in front of every file name (the search's 'config_{i}_',
+        hp_model_training.py:189-211)."""
         if not self._keep_images or self._last_pred is None:
             raise RuntimeError("save_validation_images: call enable_validation_images() before validate() / metrics()")
         D, b = self._display()
@@ -126,11 +127,11 @@ class ValidationMixin:
         e = epoch + 1
         paths = []
         if not in_image_space:
-            paths.append(self._write_kspace(D, b, os.path.join(directory, "recon_kspace_{}dB.png".format(e)), pred))
-            paths.append(self._write_kspace(D, b, os.path.join(directory, "recon_kspace_{}_error.png".format(e)), pred,
+            paths.append(self._write_kspace(D, b, os.path.join(directory, prefix + "recon_kspace_{}dB.png".format(e)), pred))
+            paths.append(self._write_kspace(D, b, os.path.join(directory, prefix + "recon_kspace_{}_error.png".format(e)), pred,
                                             gt.reshape(C, H, W, 2)))
         stats = D.coil_stats(pred, b["stats"], b["ds"]).cpu()  # 32 * C bytes cross
-        name = "recon_{}_{:.4g}_psnr_{:.4g}_ssim.png".format(e, rec["psnr"], rec["ssim"])
+        name = prefix + "recon_{}_{:.4g}_psnr_{:.4g}_ssim.png".format(e, rec["psnr"], rec["ssim"])
         paths.append(self._write_gray(D, b, os.path.join(directory, name), self._metric_bufs[0], True))
         rec["images"] = paths
         rec["coil_stats"] = stats.tolist()

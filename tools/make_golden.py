@@ -726,11 +726,82 @@ def ingest_vectors():
         json.dump(meta, f, indent=1, sort_keys=True)
 
 
+HP_BASE = dict(model="SIREN", loss="L2", lr=1e-4, batch_size=1024, max_epoch=100, val_epoch=1, weight_decay=0.0,
+               beta1=0.9, beta2=0.999, normalization="coil", transform=False,
+               net=dict(network_input_size=64, network_output_size=2, network_depth=3, network_width=64),
+               encoder=dict(embedding="gauss", scale=2, embedding_size=32, coordinates_size=3))
+HP_WIRE_NET = dict(network_input_size=3, network_output_size=2, network_depth=2, network_width=46,
+                   first_omega_0=30, hidden_omega_0=30, scale=15)
+HP_RANDOM = [  # (seed, num_search, search_space)
+    (0, 4, {"lr": {"values": [1e-5, 1e-3], "type": "log"}, "net.network_depth": {"values": [2, 4], "type": "int"},
+            "encoder.scale": {"values": [1.0, 4.0], "type": "float"},
+            "normalization": {"values": ["coil", "max", "none"], "type": "item"}}),
+    (7, 3, {"loss": {"values": ["L2", "L1"], "type": "item"}, "batch_size": {"values": [10000, 25000], "type": "int"},
+            "lr": {"values": [0.00001, 0.00003], "type": "log"}, "net.network_width": {"values": [256], "type": "item"}}),
+    # a non-positive 'log' bound and an unknown type: both keys are skipped, with the reference's messages
+    (11, 3, {"lr": {"values": [0.0, 1e-3], "type": "log"}, "weight_decay": {"values": [-1e-4, 1e-2], "type": "log"},
+             "beta1": {"values": [0.8, 0.99], "type": "uniform"}, "net.network_width": {"values": [32, 128], "type": "int"},
+             "encoder.embedding_size": {"values": [16, 32, 64], "type": "item"}}),
+    (123, 5, {"lr": {"values": [1e-4, 1e-2], "type": "log"}}),
+]
+HP_GRID = [
+    {"lr": {"values": [1e-4, 3e-4], "type": "item"}, "encoder.scale": {"values": [2, 4], "type": "item"}},
+    {"normalization": {"values": ["coil", "max"], "type": "item"}, "net.network_width": {"values": [32, 64, 1024], "type": "int"},
+     "batch_size": {"values": [512], "type": "int"}},
+]
+
+
+def hp_search_vectors():
+    """What the reference's own search-space code produces (parameter_search/find_best_config.py): the configs
+    random_search samples for (seed, search_space) pairs after random.seed(seed), grid_search's expansion, and the model
+    configs update_model_config leaves trial after trial on ONE running dict.  find_best_config.py imports the training
+    function through the ``src`` package at module scope (which drags in fastmri / tqdm / h5py): an in-memory stand-in is
+    registered for it, and findBestConfig -- the loop that trains -- is replaced by one that hands back the hp configs
+    it was given.  Plus the SHA-256 of a SIREN's and a WIRE's initial state_dict after torch.manual_seed(42)
+    (hp_model_training.py:49), for the small nets the search tests use."""
+    import copy
+    import platform
+    import random
+    for name in ("src", "src.parameter_search", "src.parameter_search.hp_model_training"):
+        sys.modules.setdefault(name, types.ModuleType(name))
+    sys.modules["src.parameter_search.hp_model_training"].hp_training_function = None
+    from parameter_search import find_best_config as ref
+    ref.findBestConfig = lambda model_configs, hp_configs, epochs, device: hp_configs
+
+    def merged(hp_configs):
+        running = copy.deepcopy(HP_BASE)
+        out = []
+        for i, hp in enumerate(hp_configs):
+            running = ref.update_model_config(running, hp)
+            running["config_index"] = i + 1  # find_best_config.py:50
+            out.append(copy.deepcopy(running))
+        return out
+
+    out = {"python": platform.python_version(), "base_config": HP_BASE, "random": [], "grid": []}
+    for seed, n, space in HP_RANDOM:
+        random.seed(seed)
+        configs = quiet(ref.random_search, "SIREN", None, None, num_search=n, epochs=2,
+                        random_search_spaces=copy.deepcopy(space))
+        out["random"].append({"seed": seed, "num_search": n, "search_space": space, "configs": configs,
+                              "merged": merged(configs)})
+    for space in HP_GRID:
+        configs = quiet(ref.grid_search, "SIREN", None, None, epochs=2, grid_search_spaces=copy.deepcopy(space))
+        out["grid"].append({"search_space": space, "configs": configs, "merged": merged(configs)})
+    out["init_seed"] = 42
+    out["init"] = {}
+    for name, net in (("SIREN", HP_BASE["net"]), ("WIRE", HP_WIRE_NET)):
+        torch.manual_seed(42)
+        model = quiet(CTORS[name], net)
+        out["init"][name] = {"net": net, "sha256": {k: sha(v) for k, v in model.state_dict().items()}}
+    with open(os.path.join(OUT, "hp_search.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=False)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     parts = dict(ingest=ingest_vectors, clustering=clustering_vectors, undersampling=undersampling_vectors, init=init_hashes,
                  models=model_vectors, losses=loss_vectors, center=center_vectors, trajectory=trajectory,
-                 multiscale=multiscale_trajectory, extra=extra_trajectories)
+                 multiscale=multiscale_trajectory, extra=extra_trajectories, hp_search=hp_search_vectors)
     for name in (sys.argv[1:] or list(parts)):  # python tools/make_golden.py [part ...]; default: everything
         parts[name]()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
