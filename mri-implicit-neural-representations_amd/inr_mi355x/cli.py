@@ -1,0 +1,153 @@
+"""The command line the three drivers share (python -m inr_mi355x.train / .train_kspace_multiscale / .train_ring_ensemble):
+the parser, the data a fit runs on, the --save-images folders and pictures, and the fit-and-report of the two loops that
+have a validation epoch."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import time
+from typing import Optional
+
+import torch
+import yaml
+
+from .trainer_base import set_default_configs
+
+
+def get_config(path: str) -> dict:
+    """models/utils.py:25-32."""
+    if not path:
+        return {}
+    with open(path, "r") as f:
+        return yaml.load(f, Loader=yaml.Loader)
+
+
+def add_shuffle_flags(ap) -> None:
+    ap.add_argument("--shuffle", action="store_true",
+                    help="random minibatches: a keyed row permutation per epoch, made on the device (config['shuffle'])")
+    ap.add_argument("--shuffle-seed", type=int, default=None,
+                    help="key of the permutation (config['shuffle_seed']; default: the trainer's seed)")
+
+
+def apply_shuffle_flags(config: dict, opts) -> dict:
+    if opts.shuffle:
+        config["shuffle"] = True
+    if opts.shuffle_seed is not None:
+        config["shuffle_seed"] = opts.shuffle_seed
+    return config
+
+
+def parse_cli(val_and_samples: bool = True):
+    """(opts, config) of a driver's command line: --config, --output_path, --synthetic, --max_steps, the shuffle flags and
+    --save-images; ``val_and_samples``: --val and --data_samples as well (the loops with a validation epoch), and then
+    --save-images needs --val."""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", type=str, required=True)
+    if val_and_samples:
+        ap.add_argument("--data_samples", type=str, default="")
+    ap.add_argument("--output_path", type=str, default=".")
+    ap.add_argument("--synthetic", type=str, default=None,
+                    help="C,H,W: fit a synthetic k-space of that shape instead of the scan the config names")
+    ap.add_argument("--max_steps", type=int, default=None)
+    if val_and_samples:
+        ap.add_argument("--val", action="store_true",
+                        help="validate every config['val_epoch'] epochs and checkpoint every config['image_save_epoch']")
+    add_shuffle_flags(ap)
+    ap.add_argument("--save-images", action="store_true",
+                    help="with --val: write the reference's pictures to <output_path>/images, checkpoints to "
+                         "<output_path>/checkpoints, and print the per-coil table after each validation line")
+    opts = ap.parse_args()
+    if val_and_samples and opts.save_images and not opts.val:
+        ap.error("--save-images needs --val (the pictures are those of the validation epoch)")
+    return opts, apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts)
+
+
+def expand_data_samples(config: dict, samples) -> list:
+    """train.py:292-318: ``samples`` = {sample: [slices...]} (the 'samples' entry of the --data_samples YAML) ->
+    [(config_i, subdir)], one fit per (sample, slice) with config_i['sample'] / ['slice'] set from the loop (as
+    training_script(sample=sample, slice_no=_slice) is called there) and subdir 'sample_{s}_slice_{k}'.  Empty or None:
+    the single fit of the config itself, in place ([(config, '')])."""
+    if not samples:
+        return [(config, "")]
+    fits = []
+    for sample, slices in samples.items():
+        for k in slices:
+            cfg = dict(config)
+            cfg["sample"], cfg["slice"] = sample, k
+            fits.append((cfg, "sample_{}_slice_{}".format(sample, k)))
+    return fits
+
+
+def cli_fits(config: dict, opts):
+    """(config_i, opts_i) of every fit a command line asks for: one, or one per (sample, slice) of --data_samples,
+    each with its own output folder."""
+    samples = (get_config(opts.data_samples) or {}).get("samples") if opts.data_samples else None
+    for cfg, sub in expand_data_samples(config, samples):
+        o = opts if not sub else argparse.Namespace(**dict(vars(opts), output_path=os.path.join(opts.output_path, sub)))
+        yield cfg, o
+
+
+def cli_data(opts, config: dict, normalization: str, image_space: bool = False):
+    """(image, coords, shape) of a fit: --synthetic C,H,W (``normalization``: the default where the config names none),
+    or the scan named by config['data_root'/'data'/'set'/'sample'/'slice'] or 'custom_file_or_path' (train.py:271-287,
+    train_kspace_multiscale.py:57-72)."""
+    if opts.synthetic:
+        from .synthetic import make_kspace
+        C, H, W = (int(v) for v in opts.synthetic.split(","))
+        return make_kspace(C, H, W, normalization=config.get("normalization", normalization), image_space=image_space)
+    from .datasets import from_config, trainer_inputs
+    return trainer_inputs(from_config(config, "cuda"))
+
+
+def cli_folders(tr, opts):
+    """(checkpoint folder, image folder or None).  --save-images (train.py:45-46,136-143): the folder tree, then the
+    training pictures."""
+    os.makedirs(opts.output_path, exist_ok=True)
+    if not getattr(opts, "save_images", False):
+        return opts.output_path, None
+    from .display import prepare_sub_folder
+    ckpt_dir, image_dir = prepare_sub_folder(opts.output_path)
+    tr.enable_validation_images()
+    tr.save_training_images(image_dir)
+    return ckpt_dir, image_dir
+
+
+def cli_validation_images(tr, epoch: int, rec: dict, image_dir: str) -> None:
+    """The pictures of the validation that has just run, and the per-coil table."""
+    from .display import coil_stats_table
+    stats = tr.save_validation_images(epoch, rec, image_dir)
+    if not tr._display_source()[1]:  # train.py:226: the table belongs to the k-space branch
+        print(coil_stats_table(stats), flush=True)
+
+
+def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
+    """Fit, then print the JSON result (and, with --val, the reference's validation lines and checkpoints; with
+    --save-images, the pictures and the per-coil table as well)."""
+    ckpt_dir, image_dir = cli_folders(tr, opts)
+    kw = {}
+    if opts.val:
+        def on_validate(rec):
+            print(tr.validation_line(rec, config["max_epoch"]), flush=True)
+            if image_dir is not None:
+                cli_validation_images(tr, rec["epoch"], rec, image_dir)
+
+        def on_epoch_end(epoch):  # train.py:244-250
+            if (epoch + 1) % config["image_save_epoch"] == 0:
+                torch.save(tr.checkpoint(), os.path.join(ckpt_dir, "model_%06d.pt" % (epoch + 1)))
+
+        kw = dict(val_epoch=config["val_epoch"], on_validate=on_validate, on_epoch_end=on_epoch_end)
+    t0 = time.time()
+    tr.fit(opts.max_steps, log_every=config.get("log_iter", 20), **kw)
+    torch.cuda.synchronize()
+    res = {"steps": tr.global_step, "seconds": time.time() - t0, "psnr": tr.evaluate(),
+           "shuffle": tr.shuffle, "shuffle_seed": tr.shuffle_seed if tr.shuffle else None}
+    if extra:
+        res.update(extra)
+    if opts.val:
+        res["ssim"] = tr.metrics()["ssim"]
+        res["validation"] = tr.val_history
+        res.update(best_psnr=tr.best_psnr, best_psnr_ep=tr.best_psnr_ep, best_ssim=tr.best_ssim,
+                   best_ssim_ep=tr.best_ssim_ep)
+    torch.save(tr.checkpoint(), os.path.join(ckpt_dir, "model_%06d.pt" % tr.global_step))
+    print(json.dumps(res))

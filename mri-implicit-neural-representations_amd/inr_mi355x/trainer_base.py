@@ -1,0 +1,265 @@
+"""What the three fitting drivers share (train.py, train_kspace_multiscale.py, train_ring_ensemble.py): a fit over data
+that stays resident in HBM -- undersampling, the training views of a shuffled fit, batch ranges and counts, the epoch
+loop, the prediction sweep, validation's test loss, PSNR / SSIM and the checkpoint.  A driver derives from ResidentFit,
+builds its model(s) and engine(s) between the set-up calls below and writes its own step(); what differs between the
+drivers lives in their hooks, never in a switch here.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .evalchain import psnr, reconstruct
+from .networks import Positional_Encoder
+from .shuffle import CoilOrder, EpochBuffers, shuffle_settings
+from .undersampling import Undersampler, parse_undersampling_argument
+from .validation import ValidationMixin
+
+
+def set_default_configs(config: dict) -> dict:
+    """utils.py:7-23."""
+    config.setdefault("per_coil", False)
+    config.setdefault("use_tv", False)
+    if "regularization" not in config:
+        config["regularization"] = {"type": "none"}
+    config.setdefault("undersampling", None)
+    return config
+
+
+def lr_factor(epoch: int, max_epoch: int) -> float:
+    """LambdaLR lambda of train.py:153."""
+    return 0.2 ** min(epoch / max_epoch, 1)
+
+
+def shard_rows(lo: int, hi: int, rank: int, world: int):
+    """Contiguous split of batch rows [lo,hi) over ranks: rank r gets
+    [lo + r*n//world, lo + (r+1)*n//world)."""
+    n = hi - lo
+    return lo + (rank * n) // world, lo + ((rank + 1) * n) // world
+
+
+def sampled_prefix(mask_cpu: torch.Tensor) -> np.ndarray:
+    """Sampled rows in front of every row of the flattened CPU mask: int64 [n + 1], so that a batch's count is a
+    difference of two entries.  (A `mask[lo:hi].sum()` per step is a multi-threaded CPU reduction whose worker threads
+    spin on after it: on the GPU boxes that drove the container into its CPU quota -- 87 ms stalls every ~17 steps of the
+    per-coil loop, profiles/r03_config5_steps.txt.  A numpy array, not a Python list: 15 coils are 3.5 M entries -- a list
+    of ints of that length is > 100 MB.)"""
+    cum = np.zeros(mask_cpu.numel() + 1, dtype=np.int64)
+    np.cumsum(mask_cpu.flatten().to(torch.int64).numpy(), out=cum[1:])
+    return cum
+
+
+def mfn_engine(model, encoder, embedding: str):
+    """(engine, enc_B) of a filter network: 'gauss' is fused into every filter (the model runs on raw coordinates and the
+    kernels take the encoder matrix); with 'LogF' / 'none' the filters read encoder.embedding(coords) from memory."""
+    if embedding == "gauss":
+        model.bind_encoder(encoder)
+        return model._engine("gauss"), encoder.B.contiguous()
+    return model._engine("x"), None
+
+
+def run_epochs(trainer, max_steps, log_every, val_epoch, on_validate, on_epoch_end):
+    """Epochs of sequential batches (train.py:155-198, train_kspace_multiscale.py:161-201) with the opt-in validation
+    epoch: after the last batch of epoch e when (e + 1) % val_epoch == 0, before the next epoch's learning rate applies."""
+    logged = []
+    for epoch in range(trainer.config["max_epoch"]):
+        for it in range(trainer.steps_per_epoch):
+            if max_steps is not None and trainer.global_step >= max_steps:
+                return logged
+            loss = trainer.step(epoch, it)
+            if log_every and trainer.global_step % log_every == 0:
+                logged.append((trainer.global_step, trainer._log_value(loss)))
+        if val_epoch and (epoch + 1) % val_epoch == 0:
+            rec = trainer.validate(epoch)
+            if on_validate is not None:
+                on_validate(rec)
+        if on_epoch_end is not None:
+            on_epoch_end(epoch)
+    return logged
+
+
+class ResidentFit(ValidationMixin):
+    """A driver's __init__ calls, in this order: _init_fit; (whatever must precede the seed: the k-means partition);
+    _seeded_encoder; its model(s) and engine(s); _resident_data; _finish_init.  It provides step(epoch, it),
+    _forward_chunk(lo, hi) and, where it trains from epoch buffers, _refilled()."""
+
+    in_image_space = False  # the data are coil images, not k-space (config['transform']): no inverse FFT in validation
+    scale = 1.0  # factor on the test loss of validation
+    predict_chunk = 1 << 18  # rows per forward call of predict_all
+
+    # ---- set-up ----------------------------------------------------------------------------------
+    def _init_fit(self, config: dict, shape, device, seed: int, rank: int, world: int, process_group,
+                  graph_steps: bool = False) -> dict:
+        """Defaults, the shuffle settings (which refuse shuffle with graph steps before anything is allocated) and where
+        the fit runs.  Returns the trainer's own copy of the config."""
+        config = set_default_configs(dict(config))
+        self.config = config
+        self.shuffle, self.shuffle_seed = shuffle_settings(config, seed, graph_steps)
+        self.device = torch.device(device)
+        self.rank, self.world, self.pg = rank, world, process_group
+        self.shape = shape
+        return config
+
+    def _seeded_encoder(self, seed: int, model_seed: Optional[int] = None) -> None:
+        """Construction order and RNG use of train.py:52-71: the seed, then the encoder; the model(s) follow on the same CPU
+        generator.  ``model_seed`` (hp_model_training.py:46-49): the search reseeds between the encoder and the model."""
+        torch.manual_seed(seed)
+        self.encoder = Positional_Encoder(self.config["encoder"], device=self.device)
+        if model_seed is not None:
+            torch.manual_seed(model_seed)
+
+    def _resident_data(self, image: torch.Tensor, coords: torch.Tensor, undersampling=None,
+                       mask: Optional[torch.Tensor] = None, mask_seed: Optional[int] = None, per_coil: bool = False,
+                       dist: Optional[torch.Tensor] = None) -> None:
+        """Data resident in HBM for the whole fit, and the views the training batches are cut from.
+        ``undersampling`` (config['undersampling'], models/utils.py:102-123): train on the zero-filled k-space with the loss
+        on sampled rows only; validation still compares with the full k-space (val_loader, utils.py:131-137).  A ``mask``
+        given by the caller replaces the drawn one.  ``per_coil``: one batch per coil (MRICoilWrapperDataset,
+        nerp_datasets.py:397-441; loader batch_size 1 = one coil, models/utils.py:65-66) so that TV can see a whole coil
+        grid.  ``dist`` (device, [n]): a per-row input that travels with the rows."""
+        C, H, W = int(self.shape[0]), int(self.shape[1]), int(self.shape[2])
+        self.image_full = image.to(self.device).contiguous()
+        method, uparams = parse_undersampling_argument(undersampling)
+        if mask is None and method is not None and method.lower() != "none":
+            masked, _, gm = Undersampler(method, seed=mask_seed).apply(image.reshape(C, H, W, 2).cpu(), uparams)
+            image, mask = masked.reshape(-1, 2), gm[:, 0].contiguous()
+        self.n = coords.shape[0]
+        self.coords = coords.to(self.device).contiguous()
+        self.image = self.image_full if mask is None else image.to(self.device).contiguous()
+        self.dist = dist
+        self.mask_cpu = mask
+        self._mask_cum = None if mask is None else sampled_prefix(mask)
+        self.mask = mask.to(torch.uint8).to(self.device).contiguous() if mask is not None else None
+        self.per_coil = bool(per_coil)
+        self.bs = H * W if self.per_coil else int(self.config["batch_size"])
+        self.steps_per_epoch = math.ceil(self.n / self.bs)
+        self.global_step = 0
+        # config['shuffle']: plain batches are views of a second set of resident buffers, refilled by one kernel call per
+        # epoch (shuffle.EpochBuffers); per-coil batches stay views of the grid and are visited in a permuted order.
+        # Validation, predict_all and the test loss keep reading the unshuffled data (the reference's val loader is
+        # never shuffled).  Off: the training views ARE the resident data.
+        self._epoch_buf = self._coil_order = None
+        t = self
+        if self.shuffle and self.per_coil:
+            self._coil_order = CoilOrder(self.steps_per_epoch, self.shuffle_seed)
+        elif self.shuffle:
+            t = self._epoch_buf = EpochBuffers(self.shuffle_seed, self.bs, self.coords, self.image, dist=dist, mask=self.mask)
+        self._t_coords, self._t_image, self._t_dist, self._t_mask = t.coords, t.image, t.dist, t.mask
+
+    def _finish_init(self) -> None:
+        if "pretrain" in self.config:  # train.py:117-121
+            self.load_checkpoint(torch.load(self.config["pretrain"], map_location=self.device))
+        self._init_validation()
+
+    # ---- batches ---------------------------------------------------------------------------------
+    def _range(self, it: int):
+        """rows [lo, hi) of batch ``it`` (the last batch is short)"""
+        return it * self.bs, min((it + 1) * self.bs, self.n)
+
+    def _count(self, lo: int, hi: int) -> int:
+        """sampled rows of the training batch [lo, hi) (all of them without a mask)"""
+        if self._epoch_buf is not None:
+            return self._epoch_buf.counts[lo // self.bs]
+        return hi - lo if self._mask_cum is None else int(self._mask_cum[hi] - self._mask_cum[lo])
+
+    def _lr(self, epoch: int) -> float:
+        return self.config["lr"] * lr_factor(epoch, self.config["max_epoch"])
+
+    def _on_shard(self, lo: int, hi: int, run) -> torch.Tensor:
+        """``run(slo, shi)`` on this rank's shard of [lo, hi).  A short last batch (or more ranks than image rows) can leave
+        a rank without rows: it contributes zeros to the sum."""
+        slo, shi = shard_rows(lo, hi, self.rank, self.world)
+        if shi == slo:
+            self.engine.grads.zero_()
+            return torch.zeros((), device=self.device)
+        return run(slo, shi)
+
+    def _begin_shuffled(self, epoch: int, it: int) -> int:
+        """Shuffled fits: the batch index step() works with.  Per-coil: the coil visited at position ``it``.  Plain
+        batches: ``it`` itself, after the first step of an epoch has refilled the epoch buffers (one kernel call, one
+        read-back of the counts) and _refilled() has recomputed what is tied to a batch's contents."""
+        if self._coil_order is not None:
+            return self._coil_order.at(epoch, it)
+        if self._epoch_buf.begin(epoch):
+            self._refilled()
+        return it
+
+    def _refilled(self) -> None:
+        """The epoch buffers hold a new epoch's rows."""
+
+    # ---- the loop --------------------------------------------------------------------------------
+    def _log_value(self, loss):
+        """what fit() keeps of step()'s return value"""
+        return float(loss)
+
+    def fit(self, max_steps: Optional[int] = None, log_every: int = 0, val_epoch: Optional[int] = None,
+            on_validate=None, on_epoch_end=None):
+        """Runs epochs of sequential batches (train.py:155-198).  Returns the list of losses logged.  ``val_epoch``
+        (opt-in): validate() after every val_epoch-th epoch, its record handed to ``on_validate``; ``on_epoch_end(epoch)``
+        after every epoch.  Validation reads the parameters only: the trajectory is the same with or without it."""
+        return run_epochs(self, max_steps, log_every, val_epoch, on_validate, on_epoch_end)
+
+    # ---- validation (train.py:199-231) -----------------------------------------------------------
+    def _forward_chunk(self, lo: int, hi: int) -> torch.Tensor:
+        """[hi - lo, 2]: the reconstruction's rows [lo, hi) of the unshuffled data"""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def predict_all(self, chunk: Optional[int] = None) -> torch.Tensor:
+        chunk = chunk or self.predict_chunk
+        return torch.cat([self._forward_chunk(lo, min(lo + chunk, self.n)) for lo in range(0, self.n, chunk)], 0)
+
+    @torch.no_grad()
+    def evaluate(self) -> float:
+        ref = reconstruct(self.image_full, self.shape, self.in_image_space)
+        return float(psnr(ref, reconstruct(self.predict_all(), self.shape, self.in_image_space)))
+
+    def _batch_hdr_A(self, it: int, lo: int, hi: int) -> float:
+        """the loss's scalar A of batch ``it`` of the unshuffled data, where the loss has one"""
+        return 0.0
+
+    def _validated(self, epoch: int, pred: torch.Tensor) -> dict:
+        """Scores the sweep ``pred`` of a validation epoch: the test loss (the config's loss over sequential val batches of
+        batch_size rows against the FULL data, times ``scale``, summed, divided by the train loader's length --
+        train.py:242), RSS, PSNR and SSIM on the device, one host read.  Updates best_psnr / best_psnr_ep / best_ssim /
+        best_ssim_ep (strict '>', 0-based epoch).  Returns {'epoch', 'test_loss', 'psnr', 'ssim'}; test_loss is None for
+        per-coil fits (their val batches are not pinned down by the reference: INTEGRATION.md)."""
+        loss_sum = None
+        if not self.per_coil:
+            loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
+            for it in range(self.steps_per_epoch):
+                lo, hi = self._range(it)
+                A = self._batch_hdr_A(it, lo, hi)  # HDR / tanh take the batch's kcoords (train.py:214-217)
+                loss, _ = self.engine.loss_grad(self.loss, pred[lo:hi], self.image_full[lo:hi], hi - lo, hdr_A=A)
+                loss_sum += loss * self.scale
+        m = self._device_metrics(self.image_full, pred, self.in_image_space)
+        return self._finish_validation(epoch, m, loss_sum, self.steps_per_epoch)
+
+    def _display_source(self):
+        return self.image_full, self.in_image_space
+
+    @torch.no_grad()
+    def metrics(self) -> dict:
+        """PSNR and SSIM of the current model (validate() without the test loss and the best-epoch record)."""
+        m = self._device_metrics(self.image_full, self.predict_all(), self.in_image_space)
+        psnr_, ssim_ = m[:2].cpu().tolist()
+        return {"psnr": psnr_, "ssim": ssim_}
+
+    # ---- checkpoints -----------------------------------------------------------------------------
+    def checkpoint(self) -> dict:
+        """Same dict as train.py:247-250 ('opt' in torch.optim.Adam.state_dict() layout)."""
+        from .checkpoint import save_dict
+        return save_dict(self.model, self.encoder, self.engine, self.config)
+
+    def _rebind_encoder(self, enc) -> None:
+        """a checkpoint replaced encoder.B: the fused kernels hold their own contiguous copy"""
+        if self.enc_B is not None:
+            self.enc_B = enc.B.contiguous()
+
+    def load_checkpoint(self, ckpt: dict) -> None:
+        """train.py:117-121 (config['pretrain']): weights, Adam moments / step count and the encoder matrix."""
+        from .checkpoint import load_dict
+        load_dict(self.model, self.encoder, self.engine, ckpt, self._rebind_encoder)

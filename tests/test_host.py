@@ -324,6 +324,21 @@ def test_shard_rows_and_schedule():
     assert lr_factor(0, 10) == 1.0 and abs(lr_factor(10, 10) - 0.2) < 1e-12 and lr_factor(50, 10) == lr_factor(10, 10)
 
 
+def test_sampled_prefix_gives_every_batch_count():
+    """The prefix count of sampled rows: a numpy int64 array of n + 1 entries whose differences are the batches' counts,
+    the short last batch included."""
+    from inr_mi355x.trainer_base import sampled_prefix
+    g = torch.Generator().manual_seed(3)
+    mask = torch.randint(0, 2, (3, 8, 6), generator=g)
+    n, bs = mask.numel(), 50
+    cum = sampled_prefix(mask)
+    assert isinstance(cum, np.ndarray) and cum.dtype == np.int64 and cum.shape == (n + 1,)
+    assert n % bs != 0
+    for lo in range(0, n, bs):
+        hi = min(lo + bs, n)
+        assert cum[hi] - cum[lo] == int(mask.flatten()[lo:hi].sum())
+
+
 def test_synthetic_kspace_contract():
     from inr_mi355x.synthetic import make_kspace
     import oracle as O
