@@ -34,5 +34,8 @@ struct DwGemmArgs {
 hipError_t launch_dw_gemm(DwGemmArgs& a, hipStream_t st);
 // number of workgroup tiles of all items; fills mt / nt / unit0
 int dw_gemm_units(DwGemmArgs& a);
+// inr_dw_gemm_split.hip: the same GEMM (TL = 128, WB = 4) on the bf16 matrix pipe, each fp32 operand as three bf16 terms;
+// launch_dw_gemm takes it for those shapes unless INR_DW_SPLIT=0 (read per call)
+hipError_t launch_dw_gemm_split(const DwGemmArgs& a, hipStream_t st);
 
 }  // namespace inr

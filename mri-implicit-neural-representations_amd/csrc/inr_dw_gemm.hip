@@ -14,6 +14,8 @@
 // dW rows follow the C layout of the MFMA: register r of lane (li, half) is row (r&3) + 8(r>>2) + 4 half, column li.
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "inr_dw_gemm.h"
 #include "inr_stamp_rt.h"
 #include "inr_launch.h"
@@ -225,6 +227,11 @@ extern long long* g_stamp_buf;  // inr_api.hip
 extern long long g_stamp_cap;
 #endif
 
+static bool dw_split_enabled() {  // (read per call: a test compares the two kernels in one process)
+  const char* e = getenv("INR_DW_SPLIT");
+  return !(e != nullptr && e[0] == '0');
+}
+
 hipError_t launch_dw_gemm(DwGemmArgs& a, hipStream_t st) {
   if (a.n_items <= 0) return hipSuccess;
 #ifdef INR_STAMPS
@@ -235,6 +242,7 @@ hipError_t launch_dw_gemm(DwGemmArgs& a, hipStream_t st) {
   a.units = a.blocks_per_chunk;
   const dim3 grid((unsigned)(a.n_chunks * a.blocks_per_chunk));
   const int wbm = a.WBM > 0 ? a.WBM : a.WB;
+  if (a.TL == 128 && a.WB == 4 && dw_split_enabled()) return launch_dw_gemm_split(a, st);
   if (a.TL == 128 && a.WB == 4 && wbm == 4) return launch_tl<128, 4, 4>(a, grid, st);
   if (a.TL == 128 && a.WB == 4 && wbm == 2) return launch_tl<128, 2, 4>(a, grid, st);
   if (a.TL == 64 && a.WB == 4 && wbm == 4) return launch_tl<64, 4, 4>(a, grid, st);
