@@ -46,7 +46,8 @@ extern "C" {
  *    included; the Adam entry points refuse l1 / l2 != 0 on plans with complex tensors).
  *    v7 additions (no version change: nothing existing moved): inr_image_metrics_scratch, inr_image_metrics (RSS, PSNR, SSIM of
  *    the validation epoch); inr_shuffle_epoch (the keyed row permutation of a shuffled epoch); inr_kspace_display, inr_gray8,
- *    inr_coil_stats and their scratch queries (the pictures and the per-coil table of the validation epoch).
+ *    inr_coil_stats and their scratch queries (the pictures and the per-coil table of the validation epoch); inr_grid_rows
+ *    (rows of a coordinate grid, made on the device: reconstruction from a checkpoint on any grid).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -438,6 +439,29 @@ int inr_gray8(const float* img, int64_t H, int64_t W, int32_t take_abs, int32_t 
 int inr_coil_stats_scratch(int64_t C, int64_t H, int64_t W, int64_t* scratch_doubles);
 int inr_coil_stats(const float* coils, int64_t C, int64_t H, int64_t W, double* stats, double* scratch,
                    int64_t scratch_doubles, void* stream);
+
+/* (v7 addition) Rows of a coordinate grid, made on the device (replaces create_coords, data/utils.py:98-108, and the
+ * upload of its result).  Row r = (k H + y) W + x of the flattened (k, y, x) grid is
+ *   (v(coils[k]; -1, 1, coils_total), v(y; y0, y1, H), v(x; x0, x1, W)),  dist = sqrt(y^2 + x^2)  (y, x: the values),
+ *   v(i; a, b, n) = a when n == 1, else a + step i for i < n / 2 and b - step (n - 1 - i) for the rest,
+ *   step = (b - a) / (n - 1),
+ * everything in fp32, every operation rounded on its own (no FMA), the square root correctly rounded: a pure function
+ * of its arguments, restated in numpy by inr_mi355x/grid.py::grid_rows_numpy.  It is NOT torch.linspace bit for bit
+ * (whose CPU values depend on the host's vector width); the two differ by at most 2^-24 on [-1, 1].
+ *   coords [n_rows,3] and dist [n_rows] (may be NULL) receive rows [row_lo, row_lo + n_rows) of the
+ *   n_coils * H * W rows, and nothing behind them; 0 <= n_rows < 2^31 per call, the grid's total is int64;
+ *   n_rows == 0 succeeds without a launch.  16-byte aligned buffers are written with 16-byte stores.
+ * INR_ERR_INVALID before any launch: null g / coords; H, W, n_coils or coils_total < 1; n_coils > 64; a coil index
+ * outside [0, coils_total); a non-finite window bound; negative or out-of-range rows.
+ * One kernel launch on `stream`; nothing is allocated, nothing is read back; capturable in a graph. */
+typedef struct {
+  int32_t coils_total;    /* C of the fit: the coil axis is v(c; -1, 1, C) */
+  int32_t n_coils;        /* which coils, in output order */
+  int32_t coils[64];
+  int32_t H, W;           /* points per axis of the rendered grid */
+  float y0, y1, x0, x1;   /* window; the fit's own grid is -1, 1, -1, 1 */
+} inr_grid_desc;
+int inr_grid_rows(const inr_grid_desc* g, int64_t row_lo, int64_t n_rows, float* coords, float* dist, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1629,6 +1629,56 @@ int inr_shuffle_epoch(int64_t n, int64_t batch_size, uint64_t seed, uint32_t epo
   return INR_OK;
 }
 
+// ---- rows of a coordinate grid (inr_grid.hip) ----
+// step of an axis of n points over [a, b]: one fp32 subtraction and one fp32 division (IEEE on the host)
+static float grid_step(float a, float b, int32_t n) {
+  if (n == 1) return 0.f;
+  const float span = b - a;
+  return span / (float)(n - 1);
+}
+
+int inr_grid_rows(const inr_grid_desc* g, int64_t row_lo, int64_t n_rows, float* coords, float* dist, void* stream) {
+  if (g == nullptr || coords == nullptr) return fail(INR_ERR_INVALID, "inr_grid_rows: null argument");
+  if (g->H < 1 || g->W < 1 || g->n_coils < 1 || g->coils_total < 1)
+    return fail(INR_ERR_INVALID, "inr_grid_rows: H = %d, W = %d, n_coils = %d, coils_total = %d (each must be >= 1)",
+                (int)g->H, (int)g->W, (int)g->n_coils, (int)g->coils_total);
+  if (g->n_coils > 64) return fail(INR_ERR_INVALID, "inr_grid_rows: n_coils = %d (at most 64 per call)", (int)g->n_coils);
+  for (int k = 0; k < g->n_coils; ++k)
+    if (g->coils[k] < 0 || g->coils[k] >= g->coils_total)
+      return fail(INR_ERR_INVALID, "inr_grid_rows: coils[%d] = %d is outside [0, %d)", k, (int)g->coils[k],
+                  (int)g->coils_total);
+  if (!std::isfinite(g->y0) || !std::isfinite(g->y1) || !std::isfinite(g->x0) || !std::isfinite(g->x1))
+    return fail(INR_ERR_INVALID, "inr_grid_rows: non-finite window (%g, %g, %g, %g)", (double)g->y0, (double)g->y1,
+                (double)g->x0, (double)g->x1);
+  const long long plane = (long long)g->H * g->W;  // < 2^62; 64 planes may not fit
+  if (plane > INT64_MAX / g->n_coils)
+    return fail(INR_ERR_INVALID, "inr_grid_rows: %d x %d x %d rows do not fit in 63 bits", (int)g->n_coils, (int)g->H, (int)g->W);
+  const long long total = plane * g->n_coils;
+  if (row_lo < 0 || n_rows < 0 || n_rows >= (1LL << 31) || row_lo > total || n_rows > total - row_lo)
+    return fail(INR_ERR_INVALID, "inr_grid_rows: rows [%lld, %lld + %lld) of a grid of %lld (0 <= n_rows < 2^31 per call)",
+                (long long)row_lo, (long long)row_lo, (long long)n_rows, total);
+  if (n_rows == 0) return INR_OK;
+  inr::GridArgs a;
+  a.coils_total = g->coils_total;
+  a.n_coils = g->n_coils;
+  a.H = g->H;
+  a.W = g->W;
+  a.wy0 = g->y0;
+  a.wy1 = g->y1;
+  a.wx0 = g->x0;
+  a.wx1 = g->x1;
+  a.step_z = grid_step(-1.f, 1.f, g->coils_total);
+  a.step_y = grid_step(g->y0, g->y1, g->H);
+  a.step_x = grid_step(g->x0, g->x1, g->W);
+  a.x_lo = (unsigned)(row_lo % g->W);
+  a.y_lo = (unsigned)((row_lo / g->W) % g->H);
+  a.k_lo = (unsigned)(row_lo / plane);
+  for (int k = 0; k < 64; ++k) a.coils[k] = k < g->n_coils ? g->coils[k] : 0;
+  hipError_t e = inr::launch_grid_rows(a, n_rows, coords, dist, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "inr_grid_rows");
+  return INR_OK;
+}
+
 int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* host_out) {
   if (host_out == nullptr || n < 1) return fail(INR_ERR_INVALID, "inr_adam_schedule: null table or n < 1");
   for (int32_t t = 0; t < n; ++t) adam_bias_terms(lr, beta1, beta2, t + 1, host_out + 2 * t, host_out + 2 * t + 1);

@@ -122,4 +122,15 @@ hipError_t launch_shuffle_epoch(const ShuffleKeys& sk, long long n, long long bs
                                 const float* dist, const uint8_t* mask, float* coords_out, float* gt_out, float* dist_out,
                                 uint8_t* mask_out, int* batch_counts, long long* order_out, hipStream_t st);
 
+// rows of a coordinate grid (inr_grid.hip): the description of inr_grid_desc plus what the host derives
+// from it -- the three steps (IEEE divisions) and the (k, y, x) of the chunk's first row
+struct GridArgs {
+  int coils_total, n_coils, H, W;
+  float wy0, wy1, wx0, wx1;
+  float step_z, step_y, step_x;
+  unsigned k_lo, y_lo, x_lo;
+  int coils[64];
+};
+hipError_t launch_grid_rows(const GridArgs& g, long long n_rows, float* coords, float* dist, hipStream_t st);
+
 }  // namespace inr

@@ -44,6 +44,12 @@ class Workspace(C.Structure):
     _fields_ = [("save", C.c_void_p), ("save_floats", C.c_int64), ("slabs", C.c_void_p), ("slab_floats", C.c_int64)]
 
 
+class GridDesc(C.Structure):
+    """inr_grid_desc: which rows inr_grid_rows makes (coils of the fit, points per axis, window)"""
+    _fields_ = [("coils_total", C.c_int32), ("n_coils", C.c_int32), ("coils", C.c_int32 * 64), ("H", C.c_int32),
+                ("W", C.c_int32), ("y0", C.c_float), ("y1", C.c_float), ("x0", C.c_float), ("x1", C.c_float)]
+
+
 class Sizes(C.Structure):
     _fields_ = [("n_params", C.c_int64), ("packed_floats", C.c_int64), ("tile_rows", C.c_int64),
                 ("save_bytes_per_tile", C.c_int64), ("max_blocks", C.c_int64), ("slab_floats", C.c_int64),
@@ -109,6 +115,7 @@ SYMBOLS = {
                             C.c_int64, _P]),
     "inr_coil_stats_scratch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_coil_stats": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
+    "inr_grid_rows": (C.c_int, [C.POINTER(GridDesc), C.c_int64, C.c_int64, _P, _P, _P]),
 }
 METRICS_WORDS = 8  # inr_image_metrics' metrics_out: psnr, ssim, sse, max_ref, min_ref, max_rec, min_rec, data_range
 

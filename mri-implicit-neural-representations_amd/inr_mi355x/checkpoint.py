@@ -41,13 +41,20 @@ def save_dict(model, encoder, engine, config: dict) -> dict:
 
 
 @torch.no_grad()
-def load_dict(model, encoder, engine, ckpt: dict, rebind=None) -> None:
-    """model.load_state_dict(ckpt['net']); optim.load_state_dict(ckpt['opt']); encoder.B = ckpt['enc']."""
+def load_weights(model, encoder, ckpt: dict, rebind=None) -> None:
+    """model.load_state_dict(ckpt['net']); encoder.B = ckpt['enc'].  No optimizer state is read or touched: what a
+    reconstruction needs of a checkpoint.  The caller re-packs its engine."""
     model.load_state_dict(ckpt["net"])
     if ckpt.get("enc") is not None and encoder is not None:
         encoder.B = ckpt["enc"].to(encoder.B.device if encoder.B is not None else ckpt["enc"].device)
         if rebind is not None:
             rebind(encoder)  # the fused kernels hold their own contiguous copy of B
+
+
+@torch.no_grad()
+def load_dict(model, encoder, engine, ckpt: dict, rebind=None) -> None:
+    """model.load_state_dict(ckpt['net']); optim.load_state_dict(ckpt['opt']); encoder.B = ckpt['enc']."""
+    load_weights(model, encoder, ckpt, rebind)
     opt: Optional[dict] = ckpt.get("opt")
     engine.exp_avg.zero_()
     engine.exp_avg_sq.zero_()

@@ -154,6 +154,10 @@ class MLPEngine:
             self.enable_sharded_update(self._shard[0], self._shard[1])
         self.pack()
 
+    def drop_training_state(self) -> None:
+        """Forward-only use (inr_mi355x/reconstruct.py): frees the gradient buffer and the Adam moments."""
+        self.gbuf = self.grads = self._loss_word = self.exp_avg = self.exp_avg_sq = None
+
     def launch_dims(self, B: int):
         nt, nb = C.c_int64(), C.c_int64()
         L.check(self.lib.inr_plan_launch_dims(self.plan, B, C.byref(nt), C.byref(nb)))

@@ -1,0 +1,299 @@
+"""Reconstruct from a checkpoint on any grid: the last step of the workflow.
+
+A fitted implicit representation is a continuous function of (coil, y, x); ``Reconstructor`` loads the ``{'net', 'enc'}``
+of a ``model_%06d.pt`` checkpoint (the reference's layout, train.py:247-250; one the reference wrote loads too) into the
+same encoder, model and engine the trainers build -- without the scan and without Adam moments -- and samples it on the
+fit's own grid, a finer or coarser one, a sub-window or a subset of coils.  Coordinates are made on the device a chunk
+at a time (inr_mi355x/grid.py): no full coordinate tensor exists at any point.
+
+What the grid means depends on the domain of the fit.  In image-space configs (config['transform']) a finer grid is
+super-resolution and a window is a zoom.  In k-space configs a finer grid over the same window samples k-space more
+densely, which is a larger field of view after the inverse FFT, and a narrower window keeps the low frequencies only,
+which is a lower-resolution image.
+
+CLI:
+    python -m inr_mi355x.reconstruct --config C --checkpoint F (--shape C,H,W | --synthetic C,H,W | the config's scan)
+        [--scale S] [--height H] [--width W] [--window y0,y1,x0,x1] [--coils 0,3,5]
+        [--radii r0,r1,...] [--chunk N] [--compare] [--output_path O]
+--shape needs no data at all; with --synthetic or the config's scan the shape comes from the data.  --compare adds PSNR
+and SSIM against the data (native grid, full window, all coils only).  Prints one JSON line: shape, rows, seconds,
+rows_per_s, files (and psnr / ssim with --compare).  Ring-ensemble ``submodel_%d.pt`` files are out of scope: their
+radii are not in the file.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import time
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from .grid import GridSpec, grid_rows, resolve_size
+
+MULTISCALE_MODELS = ("MultiscaleKFourier", "BoundedFourier")  # train_kspace_multiscale.py:93-98
+FULL_WINDOW = (-1.0, 1.0, -1.0, 1.0)
+
+
+class Reconstructor:
+    """``Reconstructor(config, checkpoint, shape=(C, H, W), device="cuda", radii=None)``: ``config`` is the fit's config
+    (dict), ``checkpoint`` the dict a trainer's ``checkpoint()`` returns or the path of a file holding one, ``shape`` the
+    fit's own grid.  The single-scale model names are those of train.MODELS; 'MultiscaleKFourier' and 'BoundedFourier'
+    need the ``radii`` their trainer reported (ValueError without).  config['precision'] is honoured."""
+
+    predict_chunk = 1 << 18  # rows per forward call of render(), as ResidentFit.predict_chunk
+
+    def __init__(self, config: dict, checkpoint, shape, device="cuda", radii: Optional[Sequence[float]] = None):
+        from .networks import Positional_Encoder
+        from .train import MFN_MODELS, MODELS
+        from .trainer_base import mfn_engine, set_default_configs
+        config = set_default_configs(dict(config))
+        self.config = config
+        name = config["model"]
+        self.multiscale = name in MULTISCALE_MODELS
+        if self.multiscale and radii is None:
+            raise ValueError(f"model {name!r} needs the radii of its ring partition (the fit's JSON line reports them)")
+        if not self.multiscale and name not in MODELS:
+            raise NotImplementedError(f"model {name!r} has no MI355X kernel yet (have {sorted(MODELS) + list(MULTISCALE_MODELS)})")
+        self.shape = tuple(int(v) for v in shape)
+        if len(self.shape) != 3 or min(self.shape) < 1:
+            raise ValueError(f"shape is (C, H, W) of the fit, got {shape!r}")
+        self.device = torch.device(device)
+        self.in_image_space = bool(config.get("transform", False)) and not self.multiscale
+        self.radii = None if radii is None else [float(r) for r in radii]
+        emb = config["encoder"]["embedding"]
+        with torch.random.fork_rng(devices=[]):  # the initial draws are overwritten by the checkpoint: leave the RNG alone
+            self.encoder = Positional_Encoder(config["encoder"], device=self.device)
+            if self.multiscale:
+                from .mfn import MultiscaleBoundedFourier, MultiscaleKFourier
+                from .train_kspace_multiscale import create_pairs
+                if name == "BoundedFourier":
+                    self.model = MultiscaleBoundedFourier(config["net"], boundaries=create_pairs(self.radii, 2))
+                else:
+                    self.model = MultiscaleKFourier(config["net"])
+            else:
+                self.model = MODELS[name](config["net"])
+        self.model = self.model.to(self.device)
+        self.is_mfn = self.multiscale or name in MFN_MODELS
+        self.takes_dist = self.multiscale or name == "KGabor"  # forward(x, dist_to_center) in the reference
+        if self.is_mfn:
+            self.engine, self.enc_B = mfn_engine(self.model, self.encoder, emb)
+        elif emb == "gauss":
+            self.engine = self.model.fused_engine(config["encoder"]["embedding_size"],
+                                                  **({"precision": config["precision"]} if "precision" in config else {}))
+            self.enc_B = self.encoder.B.contiguous()
+        else:
+            self.engine = self.model._engine()
+            self.enc_B = None
+        self.engine.drop_training_state()  # forward only: no gradient buffer, no Adam moments
+        self.load(checkpoint)
+        self._bufs = None
+        self._metric_bufs = {}
+
+    # ---- the checkpoint --------------------------------------------------------------------------
+    def _rebind_encoder(self, enc) -> None:
+        """the checkpoint replaced encoder.B: the fused kernels hold their own contiguous copy (ResidentFit._rebind_encoder)"""
+        if self.enc_B is not None:
+            self.enc_B = enc.B.contiguous()
+            if self.is_mfn:
+                self.model._enc_B = self.enc_B
+
+    def load(self, checkpoint) -> None:
+        """ckpt['net'] and ckpt['enc'] (checkpoint.load_weights); ckpt['opt'] is not read."""
+        from .checkpoint import load_weights
+        if not isinstance(checkpoint, dict):
+            checkpoint = torch.load(checkpoint, map_location=self.device)
+        if "net" not in checkpoint:
+            raise ValueError("not a {'net', 'enc', 'opt'} checkpoint (ring-ensemble submodel files are not supported)")
+        load_weights(self.model, self.encoder, checkpoint, self._rebind_encoder)
+        self.engine.pack()
+
+    # ---- sampling --------------------------------------------------------------------------------
+    def grid(self, height: Optional[int] = None, width: Optional[int] = None, scale: Optional[float] = None,
+             window: Optional[Sequence[float]] = None, coils: Optional[Sequence[int]] = None) -> GridSpec:
+        """The grid render() samples: grid.resolve_size's resolution rule on the fit's H x W, the window (default: the
+        fit's own, -1, 1, -1, 1) and the coils (default: all)."""
+        C, H, W = self.shape
+        h, w = resolve_size(H, W, height, width, scale)
+        return GridSpec(C, h, w, coils=coils, window=FULL_WINDOW if window is None else window)
+
+    def _forward_rows(self, coords: torch.Tensor, dist: Optional[torch.Tensor]) -> torch.Tensor:
+        """[n,2]: the forward call of the trainers' _forward_chunk on these coordinates"""
+        x = coords
+        if self.enc_B is None and self.config["encoder"]["embedding"] != "none":
+            x = self.encoder.embedding(coords).contiguous()  # LogF: the filters / first layer read the encoded rows
+        if self.is_mfn:
+            o = self.engine.forward(x, self.enc_B, save=False, dist=dist if self.takes_dist else None)
+            return o[-1]  # the last head is the reconstruction (train_kspace_multiscale.py:225); single-scale: the only one
+        return self.engine.forward(x, self.enc_B, save=False)
+
+    @torch.no_grad()
+    def render(self, height: Optional[int] = None, width: Optional[int] = None, scale: Optional[float] = None,
+               window: Optional[Sequence[float]] = None, coils: Optional[Sequence[int]] = None,
+               chunk: Optional[int] = None) -> torch.Tensor:
+        """[C', H', W', 2] fp32 on the device.  ``scale`` multiplies H and W (rounded to the nearest integer, never below
+        1), ``height`` / ``width`` override it; ``window`` = (y0, y1, x0, x1) inside or outside the fit's -1, 1, -1, 1;
+        ``coils`` = which coils, in output order.  Image-space configs: a finer grid is super-resolution, a window a zoom.
+        k-space configs: a finer grid over the same window is a larger field of view, a narrower window a lower-resolution
+        image.  Per ``chunk`` rows: the grid kernel into two reused buffers, the trainers' forward call, a slice of the
+        output; no full coordinate tensor is made."""
+        spec = self.grid(height, width, scale, window, coils)
+        n = spec.rows
+        chunk = int(chunk or self.predict_chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk = {chunk}")
+        chunk = min(chunk, n)
+        if self._bufs is None or self._bufs[0].shape[0] < chunk:
+            self._bufs = (torch.empty(chunk, 3, device=self.device), torch.empty(chunk, device=self.device))
+        cbuf, dbuf = self._bufs
+        out = torch.empty(n, 2, device=self.device)
+        for lo in range(0, n, chunk):
+            hi = min(lo + chunk, n)
+            c, d = grid_rows(spec, lo, hi, coords_out=cbuf[:hi - lo], dist_out=dbuf[:hi - lo] if self.takes_dist else None,
+                             with_dist=self.takes_dist)
+            out[lo:hi] = self._forward_rows(c, d)
+        return out.reshape(*spec.shape, 2)
+
+    # ---- pictures and numbers --------------------------------------------------------------------
+    def _coil_images(self, pred: torch.Tensor) -> torch.Tensor:
+        from .evalchain import ifft2c
+        if pred.dim() != 4 or pred.shape[-1] != 2:
+            raise RuntimeError(f"pred has shape {tuple(pred.shape)}, expected [C,H,W,2]")
+        return (pred if self.in_image_space else ifft2c(pred)).contiguous()
+
+    @torch.no_grad()
+    def rss(self, pred: torch.Tensor) -> torch.Tensor:
+        """[H', W']: the root-sum-of-squares image of a prediction -- ifft2c first unless config['transform'], then
+        inr_image_metrics without a reference (the kernel of the validation epoch)."""
+        from .evalchain import image_metrics
+        return image_metrics(None, self._coil_images(pred))[0]
+
+    @torch.no_grad()
+    def compare(self, pred: torch.Tensor, image_full: torch.Tensor) -> dict:
+        """{'psnr', 'ssim'} of a prediction on the fit's own full grid against the data ``image_full`` [(C*H*W),2] (or
+        [C,H,W,2]), through the kernel validate() scores with."""
+        from .evalchain import image_metrics
+        C, H, W = self.shape
+        if tuple(pred.shape) != (C, H, W, 2):
+            raise ValueError(f"compare() takes a prediction on the fit's own grid {(C, H, W, 2)}, got {tuple(pred.shape)}")
+        ref = image_metrics(None, self._coil_images(image_full.to(self.device).reshape(C, H, W, 2)))[0]
+        m = image_metrics(ref, self._coil_images(pred))[1]
+        psnr, ssim = m[:2].cpu().tolist()
+        return {"psnr": psnr, "ssim": ssim}
+
+    @torch.no_grad()
+    def save(self, directory: str, pred: torch.Tensor) -> list:
+        """Writes recon.npy (the prediction), recon.png (its RSS image through inr_gray8) and, for k-space configs,
+        recon_kspace.png (inr_kspace_display of the prediction, as the validation epoch's recon_kspace picture).
+        Returns the paths."""
+        from . import display as D
+        os.makedirs(directory, exist_ok=True)
+        paths = [os.path.join(directory, "recon.npy")]
+        np.save(paths[0], pred.detach().cpu().numpy())
+        paths.append(os.path.join(directory, "recon.png"))
+        D.write_png_gray(paths[-1], D.gray8(self.rss(pred), take_abs=True).cpu())
+        if not self.in_image_space:
+            paths.append(os.path.join(directory, "recon_kspace.png"))
+            D.write_png_gray(paths[-1], D.gray8(D.kspace_display(pred.contiguous())).cpu())
+        return paths
+
+
+# ---- command line ------------------------------------------------------------------------------------------------------
+def _numbers(kind, count: Optional[int], what: str):
+    def parse(text: str):
+        try:
+            vals = [kind(v) for v in text.split(",")]
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"{what}: {text!r} is not a comma-separated list of {kind.__name__} values")
+        if not vals or (count is not None and len(vals) != count):
+            raise argparse.ArgumentTypeError(f"{what}: expected {count if count is not None else 'at least one'} "
+                                             f"value(s), got {text!r}")
+        return vals
+    return parse
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m inr_mi355x.reconstruct",
+                                 description="Sample a fitted model from its checkpoint on any grid.")
+    ap.add_argument("--config", type=str, required=True)
+    ap.add_argument("--checkpoint", type=str, required=True)
+    ap.add_argument("--shape", type=_numbers(int, 3, "--shape C,H,W"), default=None,
+                    help="C,H,W of the fit: no data is read at all")
+    ap.add_argument("--synthetic", type=_numbers(int, 3, "--synthetic C,H,W"), default=None,
+                    help="C,H,W: the synthetic k-space the training command's --synthetic made")
+    ap.add_argument("--scale", type=float, default=None, help="multiplies H and W (rounded, never below 1)")
+    ap.add_argument("--height", type=int, default=None)
+    ap.add_argument("--width", type=int, default=None)
+    ap.add_argument("--window", type=_numbers(float, 4, "--window y0,y1,x0,x1"), default=None,
+                    help="y0,y1,x0,x1; the fit's own grid is -1,1,-1,1")
+    ap.add_argument("--coils", type=_numbers(int, None, "--coils"), default=None, help="coil indices, in output order")
+    ap.add_argument("--radii", type=_numbers(float, None, "--radii"), default=None,
+                    help="ring radii of a multiscale fit (its training command's JSON line)")
+    ap.add_argument("--chunk", type=int, default=None, help="rows per forward call")
+    ap.add_argument("--compare", action="store_true", help="PSNR / SSIM against the data (native grid only)")
+    ap.add_argument("--output_path", type=str, default=".")
+    return ap
+
+
+def parse_args(argv=None):
+    """The command line, with the argument errors that need no GPU: --shape with --synthetic, --compare without data or
+    off the fit's own full grid, sizes below 1."""
+    import sys
+    ap = build_parser()
+    argv, joined = list(sys.argv[1:] if argv is None else argv), []
+    while argv:  # "--window -0.5,0.25,0.1,0.7": argparse would take the list, which starts with '-', for an option
+        a = argv.pop(0)
+        joined.append(a + "=" + argv.pop(0) if a == "--window" and argv else a)
+    opts = ap.parse_args(joined)
+    if opts.shape is not None and opts.synthetic is not None:
+        ap.error("--shape and --synthetic exclude each other")
+    for name in ("shape", "synthetic"):
+        v = getattr(opts, name)
+        if v is not None and min(v) < 1:
+            ap.error(f"--{name}: C, H and W must be >= 1")
+    for name in ("height", "width", "chunk"):
+        v = getattr(opts, name)
+        if v is not None and v < 1:
+            ap.error(f"--{name} must be >= 1")
+    if opts.scale is not None and not opts.scale > 0:
+        ap.error("--scale must be positive")
+    if opts.compare:
+        if opts.shape is not None:
+            ap.error("--compare needs the data: --synthetic C,H,W or the config's scan, not --shape")
+        if any(getattr(opts, k) is not None for k in ("scale", "height", "width", "window", "coils")):
+            ap.error("--compare is valid on the native grid, full window, all coils only "
+                     "(drop --scale / --height / --width / --window / --coils)")
+    return opts
+
+
+def main(argv=None) -> None:
+    opts = parse_args(argv)
+    from .cli import cli_data, get_config
+    from .trainer_base import set_default_configs
+    config = set_default_configs(get_config(opts.config))
+    multiscale = config["model"] in MULTISCALE_MODELS
+    image = None
+    if opts.shape is not None:
+        shape = tuple(opts.shape)
+    else:
+        data_opts = argparse.Namespace(synthetic=None if opts.synthetic is None else ",".join(str(v) for v in opts.synthetic))
+        image, _, shape = cli_data(data_opts, config, "max" if multiscale else "coil",
+                                   image_space=bool(config.get("transform", False)) and not multiscale)
+    rec = Reconstructor(config, opts.checkpoint, shape, "cuda", radii=opts.radii)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    pred = rec.render(opts.height, opts.width, opts.scale, opts.window, opts.coils, opts.chunk)
+    torch.cuda.synchronize()
+    seconds = time.time() - t0
+    rows = pred.numel() // 2
+    res = {"shape": list(pred.shape[:3]), "rows": rows, "seconds": seconds, "rows_per_s": rows / max(seconds, 1e-12)}
+    if opts.compare:
+        res.update(rec.compare(pred, image))
+    res["files"] = rec.save(opts.output_path, pred)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
