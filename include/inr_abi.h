@@ -199,7 +199,8 @@ int inr_plan_workspace(const inr_plan* plan, int64_t B, int64_t* step_save_slots
  * `lo`.  row_split = 0: the plan's per-coordinate-tile kernel (inr_mlp_kernel, inr_mfn_kernel, inr_siren_bf16_kernel, ...):
  * grid = n_blocks of inr_plan_launch_dims, rounds = ceil(n_tiles / grid), the other fields 0. */
 typedef struct inr_step_info {
-  int32_t row_split, ncb, grid, rounds, hi, lo, n_hi, reserved;
+  int32_t row_split, ncb, grid, rounds, hi, lo, n_hi;
+  int32_t hidden_blocks; /* 32-row blocks of the hidden images in the plan's kernel build (either kernel; was reserved = 0) */
 } inr_step_info;
 int inr_plan_step_info(const inr_plan* plan, int64_t B, inr_step_info* out);
 /* INR_PRECISION_BF16 plans (v5; 16 words since v6).  Their backward pass stashes dZ in 8 bits under a power-of-two scale that
@@ -287,7 +288,10 @@ int inr_center_pairs_grad(const float* out, const float* gt, const int64_t* idx_
 /* Fused tier-2 step, stages 1-3 of train.py:163-189 in one launch: encode -> forward -> pointwise
  * loss -> backward, then the fixed-order slab reduction.  Leaves grads [P] and loss_out[0];
  * the caller all-reduces grads across ranks (if any) and calls inr_adam_step.  `grads` may be
- * NULL to launch the fused kernel alone and leave the slabs unreduced (used to time it). */
+ * NULL to launch the fused kernel alone and leave the slabs unreduced (used to time it).
+ * The complex-row losses (INR_LOSS_LOGSPACE and above: they read an output row as one complex number) need
+ * out_features == 2; every fused entry point -- this one, inr_train_adam_step, inr_train_step_multi -- refuses them
+ * on any other plan with INR_ERR_INVALID. */
 int inr_train_step(const inr_plan* plan, const inr_loss_desc* loss, const float* params,
                    const float* packed, const float* x, const float* enc_B, const float* gt,
                    const uint8_t* mask, int64_t B, const inr_workspace* ws, float* grads,

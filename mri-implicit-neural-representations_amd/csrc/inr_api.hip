@@ -876,6 +876,7 @@ int inr_plan_step_info(const inr_plan* plan, int64_t B, inr_step_info* out) {
   const int rc = inr_plan_launch_dims(plan, B, &nt, &nb);
   if (rc != INR_OK) return rc;
   memset(out, 0, sizeof(*out));
+  out->hidden_blocks = plan->nd.NB;
   if (rs_plan(plan) && dw_gemm_plan(plan) && rs_enabled(nt)) {
     const RsSchedule s = rs_schedule(nt);
     out->row_split = 1, out->ncb = s.ncb, out->grid = s.grid, out->rounds = s.rounds;
@@ -1401,6 +1402,8 @@ int inr_train_step_multi(const inr_plan* plan, const inr_loss_desc* loss, const 
   if (plan->nd.mfn_n == 0) return fail(INR_ERR_INVALID, "inr_train_step_multi: not a multiplicative-filter plan");
   if (loss->kind < INR_LOSS_L2_HALF || loss->kind > INR_LOSS_CENTER)
     return fail(INR_ERR_INVALID, "inr_train_step_multi: loss kind %d", loss->kind);
+  if (loss->kind >= INR_LOSS_LOGSPACE && plan->nd.out_f != 2)
+    return fail(INR_ERR_INVALID, "inr_train_step_multi: complex-row losses need out_features == 2");
   if ((loss->cons_w != 0.f || plan->nd.bounded) && dist == nullptr)
     return fail(INR_ERR_INVALID, "inr_train_step_multi: the consistency term / bounded linears need dist");
   if (B <= 0) return fail(INR_ERR_INVALID, "inr_train_step_multi: B = %lld", (long long)B);

@@ -59,7 +59,7 @@ class Sizes(C.Structure):
 class StepInfo(C.Structure):
     """inr_step_info: which kernel runs a batch's fused step, and how its tiles are dealt"""
     _fields_ = [("row_split", C.c_int32), ("ncb", C.c_int32), ("grid", C.c_int32), ("rounds", C.c_int32),
-                ("hi", C.c_int32), ("lo", C.c_int32), ("n_hi", C.c_int32), ("reserved", C.c_int32)]
+                ("hi", C.c_int32), ("lo", C.c_int32), ("n_hi", C.c_int32), ("hidden_blocks", C.c_int32)]
 
 
 # every symbol include/inr_abi.h declares: (name, restype, argtypes)

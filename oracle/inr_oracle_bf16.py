@@ -6,7 +6,8 @@ MI355X kernels round (csrc/inr_siren_bf16_impl.h, csrc/inr_dw_gemm_bf16.hip, csr
 
   forward   operands of every GEMM in bf16: bf16(W_l * w0 / 2 pi) -- the sine layers' weights carry the factor, their
             accumulators are phases in revolutions --, bf16 of the encoder features / of h_l = sin(2 pi t_l); fp32
-            accumulate; bias b_l * w0 / 2 pi in fp32; last layer bf16(W) and no factor
+            accumulate; bias b_l * w0 / 2 pi in fp32; last layer bf16(W) and no factor, its activation (none, tanh,
+            sin(w0 z) with one fp32 rounding of the product, sigmoid) and that activation's derivative in fp32
   stash     P_l = round-to-nearest-even(256 t_l) mod 256 (8 bits of phase);  G_l = bf8 e5m2 of dZ_l * mult
   backward  dZ_last * mult in bf16 against bf16(W^T * w0); dZ_l = dH_l * cos(2 pi P_l / 256) (fp32); the next GEMM's
             operand is bf16(dZ_l)
@@ -79,10 +80,28 @@ def _mm(a: Tensor, b: Tensor, wide: bool) -> Tensor:
     return (a.double() @ b.double()).float() if wide else a @ b
 
 
+def last_layer_act(z: Tensor, act: str):
+    """(y, dy/dz) of the output activation as the kernel's fp32 epilogue forms them (csrc/inr_mlp_impl.h act_fwd):
+    id | tanh | sin = sin(w0 z), the product rounded to fp32 once (networks.py:96) | sigmoid."""
+    if act == "tanh":
+        y = torch.tanh(z)
+        return y, 1.0 - y * y
+    if act == "sin":
+        t = (z * SIREN_W0).float()
+        return torch.sin(t.double()).float(), (SIREN_W0 * torch.cos(t.double())).float()
+    if act == "sigmoid":
+        y = torch.sigmoid(z)
+        return y, y * (1.0 - y)
+    assert act == "id", act
+    return z, torch.ones_like(z)
+
+
 def siren_bf16_step(sd: Dict[str, Tensor], coords: Tensor, enc_B: Tensor, net: dict, dloss_dy, mult: float,
-                    mask: Optional[Tensor] = None, wide_sums: bool = False):
+                    mask: Optional[Tensor] = None, wide_sums: bool = False, last_act: Optional[str] = None):
     """One gradient step of the bf16 path.  ``dloss_dy(y) -> g`` [B,out] is d(loss)/d(out) (rows outside ``mask`` are
     zeroed here); ``mult`` the factor the kernel multiplied it by (engine.grad_scale_state()[2] after the step).
+    ``last_act`` (id | tanh | sin | sigmoid) overrides what ``net`` says (last_tanh, network_last_linear: False = sin); a
+    sigmoid output has no model class and is only reached through a plan descriptor.
     Returns (out [B,out], grads dict in state_dict keys, largest |dZ * mult| seen).
 
     ``wide_sums``: accumulate the forward / backward GEMMs in float64.  The rounding model does not say in which order
@@ -90,8 +109,8 @@ def siren_bf16_step(sd: Dict[str, Tensor], coords: Tensor, enc_B: Tensor, net: d
     lands on the other side of a boundary moves by 12-25 %) make of 1e-7 -- 1e-4 for the last layer's gradient, 4e-3 for the
     first layer's weights, whatever the batch size.  The tests hold the device to a small multiple of THAT distance."""
     D = net["network_depth"]
-    last_tanh = net.get("last_tanh", False)
-    assert net.get("network_last_linear", True) or last_tanh
+    if last_act is None:
+        last_act = "tanh" if net.get("last_tanh", False) else ("id" if net.get("network_last_linear", True) else "sin")
     kr = np.float32(SIREN_W0) * INV_2PI_F32  # w0 / 2 pi as the packing kernel forms it (fp32 product)
     W = [sd[f"model.{k}.linear.weight"].float() for k in range(D)]
     b = [sd[f"model.{k}.linear.bias"].float() for k in range(D)]
@@ -104,8 +123,7 @@ def siren_bf16_step(sd: Dict[str, Tensor], coords: Tensor, enc_B: Tensor, net: d
         P.append(phase_byte(t))
         h = _bf16(_rev_sin(t))
     z = _mm(h, _bf16(W[D - 1]).t(), wide_sums) + b[D - 1]
-    y = torch.tanh(z) if last_tanh else z
-    dy = (1.0 - y * y) if last_tanh else torch.ones_like(y)
+    y, dy = last_layer_act(z, last_act)
     g = dloss_dy(y.detach())
     if mask is not None:
         g = g * mask.to(g.dtype)[:, None]
