@@ -13,7 +13,8 @@ Criteria -- none of them new:
 * non-L2 losses: 2e-5 on loss and flat gradient against the fp32 oracle (tests/test_gpu_parity.py::
   test_losses_fused_and_tier1; the HDR cases have a few hundred rows, where tests/test_gpu_rs.py documents 2e-5);
 * bf16: tests/test_gpu_bf16.py::test_bf16_step_matches_rounding_oracle, every assertion of it.
-The measured (e_gpu, e_cpu) pairs are recorded (conftest.record_parity; profiles/matrix_parity.jsonl is a committed copy)."""
+The measured (e_gpu, e_cpu) pairs are recorded (conftest.record_parity; profiles/matrix_parity.jsonl is a committed copy of
+the first device run, condensed: one line per case, {what: [e_gpu, e_cpu]}, three digits)."""
 import numpy as np
 import pytest
 import torch
