@@ -27,6 +27,7 @@ struct DwGemmArgs {
   int WBM;             // 0: square tiles; 2 (with WB = 4, TL = 128): 128-row x 256-column workgroup tiles for short chunks
   int n_items;
   int units, blocks_per_chunk;  // set by the launcher
+  int place;           // set by the launcher (dw_gemm_split_kernel only): 1 = a chunk's workgroups under one L2 (inr_dw_place.h)
   DwGemmItem it[INR_DWG_MAX_ITEMS];
 };
 

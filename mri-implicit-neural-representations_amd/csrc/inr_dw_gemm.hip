@@ -232,6 +232,11 @@ static bool dw_split_enabled() {  // (read per call: a test compares the two ker
   return !(e != nullptr && e[0] == '0');
 }
 
+static bool dw_place_enabled() {  // (read per call, as above: INR_DW_PLACE=0 keeps the workgroups in block-id order)
+  const char* e = getenv("INR_DW_PLACE");
+  return !(e != nullptr && e[0] == '0');
+}
+
 hipError_t launch_dw_gemm(DwGemmArgs& a, hipStream_t st) {
   if (a.n_items <= 0) return hipSuccess;
 #ifdef INR_STAMPS
@@ -240,6 +245,7 @@ hipError_t launch_dw_gemm(DwGemmArgs& a, hipStream_t st) {
   if (a.n_items > INR_DWG_MAX_ITEMS || a.n_chunks <= 0 || a.tiles_per_chunk <= 0) return hipErrorInvalidValue;
   a.blocks_per_chunk = dw_gemm_units(a);
   a.units = a.blocks_per_chunk;
+  a.place = dw_place_enabled() ? 1 : 0;
   const dim3 grid((unsigned)(a.n_chunks * a.blocks_per_chunk));
   const int wbm = a.WBM > 0 ? a.WBM : a.WB;
   if (a.TL == 128 && a.WB == 4 && dw_split_enabled()) return launch_dw_gemm_split(a, st);

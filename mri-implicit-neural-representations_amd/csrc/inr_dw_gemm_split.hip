@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "inr_dw_gemm.h"
+#include "inr_dw_place.h"
 #include "inr_stamp_rt.h"
 #include "inr_launch.h"
 
@@ -248,8 +249,10 @@ __global__ __launch_bounds__(256) void dw_gemm_split_kernel(const DwGemmArgs a) 
   extern __shared__ __attribute__((aligned(16))) char lds_split[];
   INR_RT_STAMP(a.dbg, a.dbg_cap, 4, threadIdx.x >> 6, threadIdx.x & 63, 44);
   const int bpc = a.blocks_per_chunk * SPLITM;
-  const int kc = blockIdx.x / bpc;
-  const int rem = blockIdx.x - kc * bpc;
+  // a chunk's workgroups read the same stash rows: place them under one L2 (inr_dw_place.h); a.place == 0: in id order
+  const int b = a.place ? dw_place((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+  const int kc = b / bpc;
+  const int rem = b - kc * bpc;
   const int unit = rem / SPLITM, hh = rem - unit * SPLITM;
   int k = 0;
   while (k + 1 < a.n_items && unit >= a.it[k + 1].unit0) ++k;
