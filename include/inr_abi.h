@@ -10,7 +10,7 @@
  *   - all tensor arguments are DEVICE pointers to contiguous row-major fp32 buffers owned by the
  *     caller -- except inr_image_metrics' `metrics_out` and `scratch`, which are fp64 (double) device buffers, and
  *     inr_shuffle_epoch's integer buffers (uint8 masks, int32 counts, int64 order), inr_gray8's uint8 `lut` / `out` and
- *     inr_coil_stats' fp64 `stats` / `scratch`; the
+ *     inr_coil_stats' and inr_band_stats' fp64 `stats` / `scratch` (inr_band_stats' bounds are host arrays); the
  *     library retains no pointer across calls and allocates no device memory -- with ONE exception:
  *     an INR_PRECISION_BF16 plan owns 64 bytes of device memory (16 words), its gradient-scale state (inr_plan_grad_scale_state),
  *     allocated with hipMalloc and initialised with a synchronous hipMemcpy by the first call that needs it on a device
@@ -47,7 +47,8 @@ extern "C" {
  *    v7 additions (no version change: nothing existing moved): inr_image_metrics_scratch, inr_image_metrics (RSS, PSNR, SSIM of
  *    the validation epoch); inr_shuffle_epoch (the keyed row permutation of a shuffled epoch); inr_kspace_display, inr_gray8,
  *    inr_coil_stats and their scratch queries (the pictures and the per-coil table of the validation epoch); inr_grid_rows
- *    (rows of a coordinate grid, made on the device: reconstruction from a checkpoint on any grid).
+ *    (rows of a coordinate grid, made on the device: reconstruction from a checkpoint on any grid); inr_band_stats and its
+ *    scratch query (per-band counts, energies, errors and extrema of a field against radius).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -466,6 +467,38 @@ typedef struct {
   float y0, y1, x0, x1;   /* window; the fit's own grid is -1, 1, -1, 1 */
 } inr_grid_desc;
 int inr_grid_rows(const inr_grid_desc* g, int64_t row_lo, int64_t n_rows, float* coords, float* dist, void* stream);
+
+/* (v7 addition) Radial band statistics of an [n,2] field in one pass (replaces the per-ring masked reductions of
+ * clustering.py:48-61, 100-135; the per-ring report of the validation epoch has no reference counterpart; DESIGN.md
+ * section 4.17).  dist [n], gt [n,2], pred [n,2] (may be NULL), mask [n] uint8 (may be NULL): device.  band_lo / band_hi:
+ * HOST arrays of n_bands floats.  Row i belongs to band b iff band_lo[b] <= dist[i] <= band_hi[b], compared in fp32 with
+ * both ends included; bands may overlap, nest, be empty or leave rows uncovered.  With `mask`, only rows with
+ * (mask[i] != 0) == (mask_select != 0) take part.  stats [n_bands][INR_BAND_FIELDS] (fp64, device), per band:
+ *   n         rows in the band
+ *   energy    sum of gt_re^2 + gt_im^2
+ *   sse       sum of |pred - gt|^2                                   (0 without pred)
+ *   max_abs2  max of fl32(fl32(re re) + fl32(im im)) of gt
+ *   max_comp  max of |gt component| over both components
+ *   min_comp  min of |gt component| over both components
+ *   max_err2  max of |pred - gt|^2                                   (-inf without pred)
+ * A sum term is (double)a * (double)a + (double)b * (double)b (a, b = the components, or the fp64 differences of the
+ * components), every operation rounded on its own, and the terms are added in fp64 in a fixed order; the extrema are
+ * exact.  An empty band has n = 0, sums 0, maxima -inf, minima +inf.  Inputs are taken as finite (a NaN dist is in no
+ * band).  inr_mi355x/bands.py::band_stats_numpy restates this in numpy.
+ * INR_ERR_INVALID before any launch: a null dist / gt / bounds / stats / scratch; n < 1 or n >= 2^31; n_bands outside
+ * 1..INR_BAND_MAX; a NaN bound or band_lo[b] > band_hi[b].
+ * `scratch` = at least the fp64 words inr_band_stats_scratch gives for (n, n_bands) -- a function of its arguments
+ * alone.  Two launches on `stream` (workgroup partials, then one block per band); no atomics, fixed-order reductions:
+ * two calls on the same inputs give the same bits.  Nothing is allocated, nothing is read back, capturable in a graph.
+ * 16-byte aligned dist / gt / pred (mask: 4-byte) are read with 16-byte loads, INR_BAND_TILE_ROWS rows per workgroup
+ * and step. */
+#define INR_BAND_MAX 64
+#define INR_BAND_FIELDS 7
+#define INR_BAND_TILE_ROWS 1024
+int inr_band_stats_scratch(int64_t n, int32_t n_bands, int64_t* scratch_doubles);
+int inr_band_stats(const float* dist, const float* gt, const float* pred, const uint8_t* mask, int32_t mask_select,
+                   int64_t n, const float* band_lo, const float* band_hi, int32_t n_bands, double* stats,
+                   double* scratch, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1682,6 +1682,47 @@ int inr_grid_rows(const inr_grid_desc* g, int64_t row_lo, int64_t n_rows, float*
   return INR_OK;
 }
 
+// ---- radial band statistics (inr_bands.hip) ----
+static_assert(INR_BAND_MAX == inr::BAND_MAX && INR_BAND_FIELDS == inr::BAND_FIELDS &&
+                  INR_BAND_TILE_ROWS == inr::BAND_TILE_ROWS, "inr_abi.h and inr_aux.h disagree");
+
+static int band_stats_check(int64_t n, int32_t n_bands, const char* who) {
+  if (n < 1 || n >= (1LL << 31)) return fail(INR_ERR_INVALID, "%s: n = %lld (1 <= n < 2^31 rows per call)", who, (long long)n);
+  if (n_bands < 1 || n_bands > INR_BAND_MAX)
+    return fail(INR_ERR_INVALID, "%s: n_bands = %d (1..%d)", who, (int)n_bands, INR_BAND_MAX);
+  return INR_OK;
+}
+
+int inr_band_stats_scratch(int64_t n, int32_t n_bands, int64_t* scratch_doubles) {
+  if (scratch_doubles == nullptr) return fail(INR_ERR_INVALID, "inr_band_stats_scratch: null argument");
+  const int rc = band_stats_check(n, n_bands, "inr_band_stats_scratch");
+  if (rc != INR_OK) return rc;
+  *scratch_doubles = inr::band_stats_scratch_doubles(n, n_bands);
+  return INR_OK;
+}
+
+int inr_band_stats(const float* dist, const float* gt, const float* pred, const uint8_t* mask, int32_t mask_select,
+                   int64_t n, const float* band_lo, const float* band_hi, int32_t n_bands, double* stats,
+                   double* scratch, void* stream) {
+  if (dist == nullptr || gt == nullptr || band_lo == nullptr || band_hi == nullptr || stats == nullptr || scratch == nullptr)
+    return fail(INR_ERR_INVALID, "inr_band_stats: null argument");
+  const int rc = band_stats_check(n, n_bands, "inr_band_stats");
+  if (rc != INR_OK) return rc;
+  inr::BandArgs a;
+  a.n_bands = n_bands;
+  a.mask_select = mask_select != 0;
+  for (int b = 0; b < INR_BAND_MAX; ++b) {
+    if (b < n_bands && !(band_lo[b] <= band_hi[b]))  // NaN bounds too
+      return fail(INR_ERR_INVALID, "inr_band_stats: band %d is [%g, %g] (bounds must be numbers with lo <= hi)", b,
+                  (double)band_lo[b], (double)band_hi[b]);
+    a.lo[b] = b < n_bands ? band_lo[b] : 0.f;
+    a.hi[b] = b < n_bands ? band_hi[b] : 0.f;
+  }
+  hipError_t e = inr::launch_band_stats(a, dist, gt, pred, mask, n, stats, scratch, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "inr_band_stats");
+  return INR_OK;
+}
+
 int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* host_out) {
   if (host_out == nullptr || n < 1) return fail(INR_ERR_INVALID, "inr_adam_schedule: null table or n < 1");
   for (int32_t t = 0; t < n; ++t) adam_bias_terms(lr, beta1, beta2, t + 1, host_out + 2 * t, host_out + 2 * t + 1);

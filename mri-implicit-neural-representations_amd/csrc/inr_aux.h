@@ -133,4 +133,16 @@ struct GridArgs {
 };
 hipError_t launch_grid_rows(const GridArgs& g, long long n_rows, float* coords, float* dist, hipStream_t st);
 
+// radial band statistics (inr_bands.hip): the bounds travel as kernel arguments
+constexpr int BAND_MAX = 64;          // INR_BAND_MAX
+constexpr int BAND_FIELDS = 7;        // INR_BAND_FIELDS
+constexpr int BAND_TILE_ROWS = 1024;  // INR_BAND_TILE_ROWS
+struct BandArgs {
+  int n_bands, mask_select;
+  float lo[BAND_MAX], hi[BAND_MAX];
+};
+long long band_stats_scratch_doubles(long long n, int n_bands);
+hipError_t launch_band_stats(const BandArgs& a, const float* dist, const float* gt, const float* pred,
+                             const uint8_t* mask, long long n, double* stats, double* scratch, hipStream_t st);
+
 }  // namespace inr

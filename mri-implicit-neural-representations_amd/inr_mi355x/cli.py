@@ -38,7 +38,7 @@ def apply_shuffle_flags(config: dict, opts) -> dict:
     return config
 
 
-def parse_cli(val_and_samples: bool = True):
+def parse_cli(val_and_samples: bool = True, argv=None):
     """(opts, config) of a driver's command line: --config, --output_path, --synthetic, --max_steps, the shuffle flags and
     --save-images; ``val_and_samples``: --val and --data_samples as well (the loops with a validation epoch), and then
     --save-images needs --val."""
@@ -57,9 +57,13 @@ def parse_cli(val_and_samples: bool = True):
     ap.add_argument("--save-images", action="store_true",
                     help="with --val: write the reference's pictures to <output_path>/images, checkpoints to "
                          "<output_path>/checkpoints, and print the per-coil table after each validation line")
-    opts = ap.parse_args()
+    from .bands import add_band_report_flag
+    add_band_report_flag(ap, "with --val" if val_and_samples else "after the fit")
+    opts = ap.parse_args(argv)
     if val_and_samples and opts.save_images and not opts.val:
         ap.error("--save-images needs --val (the pictures are those of the validation epoch)")
+    if opts.band_report is not None and val_and_samples and not opts.val:
+        ap.error("--band-report needs --val (the report is made from the validation epoch's prediction)")
     return opts, apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts)
 
 
@@ -113,6 +117,22 @@ def cli_folders(tr, opts):
     return ckpt_dir, image_dir
 
 
+def cli_band_report(tr, opts) -> None:
+    """--band-report [N]: validate() / metrics() report the error by radius from now on."""
+    from .bands import flag_bounds
+    b = flag_bounds(getattr(opts, "band_report", None))
+    if b is not None:
+        tr.enable_band_report(None if b is True else b)
+
+
+def print_band_tables(rec: dict) -> None:
+    """The table(s) of a record that carries a band report; nothing otherwise."""
+    from .bands import REPORT_TITLE, format_band_table
+    for key, what in (("bands", ""), ("bands_sampled", ", sampled rows"), ("bands_unsampled", ", unsampled rows")):
+        if key in rec:
+            print(format_band_table(rec[key], REPORT_TITLE + what), flush=True)
+
+
 def cli_validation_images(tr, epoch: int, rec: dict, image_dir: str) -> None:
     """The pictures of the validation that has just run, and the per-coil table."""
     from .display import coil_stats_table
@@ -125,10 +145,12 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
     """Fit, then print the JSON result (and, with --val, the reference's validation lines and checkpoints; with
     --save-images, the pictures and the per-coil table as well)."""
     ckpt_dir, image_dir = cli_folders(tr, opts)
+    cli_band_report(tr, opts)
     kw = {}
     if opts.val:
         def on_validate(rec):
             print(tr.validation_line(rec, config["max_epoch"]), flush=True)
+            print_band_tables(rec)
             if image_dir is not None:
                 cli_validation_images(tr, rec["epoch"], rec, image_dir)
 
@@ -145,7 +167,9 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
     if extra:
         res.update(extra)
     if opts.val:
-        res["ssim"] = tr.metrics()["ssim"]
+        final = tr.metrics()
+        res["ssim"] = final["ssim"]
+        res.update({k: v for k, v in final.items() if k.startswith("bands")})
         res["validation"] = tr.val_history
         res.update(best_psnr=tr.best_psnr, best_psnr_ep=tr.best_psnr_ep, best_ssim=tr.best_ssim,
                    best_ssim_ep=tr.best_ssim_ep)

@@ -20,6 +20,7 @@ sweep and metric / display kernels.
 CLI:
     python -m inr_mi355x.hp_search --config cfg.yaml --hp_config hp.yaml [--output_path out] [--synthetic C,H,W]
                                    [--seed S] [--search-seed N] [--jobs N] [--save-images] [--trial-timeout SECONDS]
+                                   [--band-report [N]]
 (--trial-timeout limits a worker process's trial, so it needs --jobs > 1: with --jobs 1 the trials run in the command's
 own process and are not limited.)
 """
@@ -216,12 +217,13 @@ def build_trial_trainer(cfg: dict, data, seed: int = 0, device="cuda"):
 
 
 def hp_training_function(config: dict, max_epoch: int, data, *, seed: int = 0, image_directory: Optional[str] = None,
-                         device="cuda") -> dict:
+                         device="cuda", band_report=None) -> dict:
     """Fits ``config`` (a merged config; its 'config_index' names the pictures) for ``max_epoch`` epochs with a
     validation every config['val_epoch'] epochs and returns {best_psnr, best_psnr_ep, best_ssim, best_ssim_ep} (initial
     values and strict '>' of hp_model_training.py:112-115,202-207) plus 'steps', 'fit_seconds' and 'build_seconds'.  A trainer
     construction that raises NotImplementedError / ValueError -- nothing has been launched yet -- returns
-    {'error': message}."""
+    {'error': message}.  ``band_report`` (True, a number of rings or (lo, hi) pairs; bands.report_bounds): the result
+    also carries 'bands', the error by radius of the validation with the best PSNR."""
     import torch
     cfg = trial_config(config, max_epoch)
     t0 = time.time()
@@ -231,6 +233,8 @@ def hp_training_function(config: dict, max_epoch: int, data, *, seed: int = 0, i
         return {"error": "{}: {}".format(type(e).__name__, e)}
     prefix = "config_{}_".format(cfg.get("config_index", 0))
     on_validate = None
+    if band_report is not None:
+        tr.enable_band_report(None if band_report is True else band_report)
     if image_directory is not None:
         tr.enable_validation_images()
         if not os.path.exists(os.path.join(image_directory, "train.png")):  # hp_model_training.py:30-38, once
@@ -249,6 +253,9 @@ def hp_training_function(config: dict, max_epoch: int, data, *, seed: int = 0, i
         stats = {"best_psnr": tr.best_psnr, "best_psnr_ep": tr.best_psnr_ep, "best_ssim": tr.best_ssim,
                  "best_ssim_ep": tr.best_ssim_ep}
         print(tr.validation_line(tr.val_history[-1], max_epoch))
+        if band_report is not None:  # the record of the epoch best_psnr names
+            best = next((r for r in tr.val_history if r["epoch"] == tr.best_psnr_ep), tr.val_history[-1])
+            stats.update({k: v for k, v in best.items() if k.startswith("bands")})
     else:
         print("hp search: config #{}: no validation epoch within max_epoch={} (val_epoch={}): its record keeps the "
               "initial {} / {}".format(cfg.get("config_index", 0), max_epoch, cfg["val_epoch"],
@@ -260,10 +267,11 @@ class LocalRunner:
     """Trials in this process: one DataCache, one library handle, for as long as the object lives."""
 
     def __init__(self, source: Callable, max_epoch: int, *, seed: int = 0, image_directory: Optional[str] = None,
-                 device="cuda", cache_bytes: int = CACHE_BUDGET_BYTES, extra_key: tuple = (), run_trial=None):
+                 device="cuda", cache_bytes: int = CACHE_BUDGET_BYTES, extra_key: tuple = (), run_trial=None,
+                 band_report=None):
         self.cache = DataCache(source, cache_bytes, device if run_trial is None else None, extra_key)
         self.max_epoch, self.seed, self.image_directory, self.device = max_epoch, seed, image_directory, device
-        self.run_trial = run_trial
+        self.run_trial, self.band_report = run_trial, band_report
 
     def __call__(self, merged: dict) -> dict:
         t0 = time.time()
@@ -273,7 +281,8 @@ class LocalRunner:
             res = dict(self.run_trial(merged, self.max_epoch, data))
         else:
             res = hp_training_function(merged, self.max_epoch, data, seed=self.seed,
-                                       image_directory=self.image_directory, device=self.device)
+                                       image_directory=self.image_directory, device=self.device,
+                                       band_report=self.band_report)
         res["setup_seconds"] = ingest + res.pop("build_seconds", 0.0)
         return res
 
@@ -299,7 +308,8 @@ def worker_main() -> int:
     syn = setup.get("synthetic")
     source = synthetic_source(*syn) if syn else dataset_source
     runner = LocalRunner(source, setup["max_epoch"], seed=setup["seed"], image_directory=setup.get("image_directory"),
-                         cache_bytes=setup.get("cache_bytes", CACHE_BUDGET_BYTES), extra_key=tuple(syn or ()))
+                         cache_bytes=setup.get("cache_bytes", CACHE_BUDGET_BYTES), extra_key=tuple(syn or ()),
+                         band_report=setup.get("band_report"))
     for line in sys.stdin:
         if not line.strip():
             continue
@@ -434,10 +444,11 @@ def run_search(config: dict, hp_config: dict, output_directory: str, *, source: 
                seed: int = 0, search_seed: Optional[int] = None, jobs: int = 1, save_images: bool = False,
                run_trial: Optional[Callable] = None, synthetic: Optional[tuple] = None,
                trial_timeout: float = TRIAL_TIMEOUT, cache_bytes: int = CACHE_BUDGET_BYTES,
-               worker_cmd: Optional[list] = None) -> dict:
+               worker_cmd: Optional[list] = None, band_report=None) -> dict:
     """hp_search_script.py:12-67 into ``output_directory`` (which exists): hp_search_config_{i}.yaml per trial,
     best_psnr_config.yaml, best_ssim_config.yaml, configs_and_results.txt, results.json; pictures in
-    <output_directory>/images with ``save_images``.
+    <output_directory>/images with ``save_images``; with ``band_report`` (True or a number of rings) every trial's record
+    in results.json carries 'bands', the error by radius of its best validation.
 
     ``source``: cfg -> (image, coords, shape), called once per distinct dataset (default: the scan the config names, or
     make_kspace of ``synthetic`` = (C, H, W)).  ``run_trial(merged_config, max_epoch, data) -> dict`` replaces the
@@ -472,7 +483,7 @@ def run_search(config: dict, hp_config: dict, output_directory: str, *, source: 
         if source is None:
             source = synthetic_source(*synthetic) if synthetic else dataset_source
         runner = LocalRunner(source, max_epoch, seed=seed, image_directory=image_directory, cache_bytes=cache_bytes,
-                             extra_key=tuple(synthetic or ()), run_trial=run_trial)
+                             extra_key=tuple(synthetic or ()), run_trial=run_trial, band_report=band_report)
         try:
             for i, cfg in enumerate(merged):
                 print("\nEvaluating Config #{} [of {}]:\n".format(i + 1, len(hp_configs)), hp_configs[i])
@@ -486,7 +497,8 @@ def run_search(config: dict, hp_config: dict, output_directory: str, *, source: 
         ingests = runner.cache.ingests
     else:
         setup = {"max_epoch": max_epoch, "seed": seed, "image_directory": image_directory,
-                 "synthetic": list(synthetic) if synthetic else None, "cache_bytes": cache_bytes}
+                 "synthetic": list(synthetic) if synthetic else None, "cache_bytes": cache_bytes,
+                 "band_report": band_report}
         out = run_workers(merged, jobs, setup, records, trial_timeout=trial_timeout, worker_cmd=worker_cmd)
         aborted, ingests = out["aborted"], out["ingests"]
 
@@ -546,6 +558,8 @@ def main(argv=None) -> int:
                          "search stops (with --jobs 1 trials run in this process and are not limited)")
     ap.add_argument("--cache-bytes", type=int, default=CACHE_BUDGET_BYTES,
                     help="bytes of resident datasets kept between trials (0: ingest for every trial)")
+    from .bands import add_band_report_flag, flag_bounds
+    add_band_report_flag(ap, "per trial")
     opts = ap.parse_args(argv)
     if opts.worker:
         return worker_main()
@@ -562,7 +576,8 @@ def main(argv=None) -> int:
     import shutil
     shutil.copy(opts.config, os.path.join(output_directory, "config.yaml"))  # hp_search_script.py:37
     res = run_search(config, hp_config, output_directory, seed=opts.seed, search_seed=opts.search_seed, jobs=opts.jobs,
-                     save_images=opts.save_images, trial_timeout=opts.trial_timeout, cache_bytes=opts.cache_bytes,
+                     save_images=opts.save_images, band_report=flag_bounds(opts.band_report),
+                     trial_timeout=opts.trial_timeout, cache_bytes=opts.cache_bytes,
                      synthetic=tuple(int(v) for v in opts.synthetic.split(",")) if opts.synthetic else None)
     print(json.dumps({"output_directory": output_directory, "trials": len(res["results"]), "ingests": res["ingests"],
                       "aborted": res["aborted"],

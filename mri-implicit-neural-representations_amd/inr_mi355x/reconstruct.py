@@ -171,9 +171,11 @@ class Reconstructor:
         return image_metrics(None, self._coil_images(pred))[0]
 
     @torch.no_grad()
-    def compare(self, pred: torch.Tensor, image_full: torch.Tensor) -> dict:
+    def compare(self, pred: torch.Tensor, image_full: torch.Tensor, bands=None) -> dict:
         """{'psnr', 'ssim'} of a prediction on the fit's own full grid against the data ``image_full`` [(C*H*W),2] (or
-        [C,H,W,2]), through the kernel validate() scores with."""
+        [C,H,W,2]), through the kernel validate() scores with.  ``bands`` ((lo, hi) pairs, a number of rings, or True for
+        the rings of the config's partition / 40): adds 'bands', bands.band_report of the prediction against the data per
+        band of the grid's own radius (grid.grid_rows' dist)."""
         from .evalchain import image_metrics
         C, H, W = self.shape
         if tuple(pred.shape) != (C, H, W, 2):
@@ -181,7 +183,15 @@ class Reconstructor:
         ref = image_metrics(None, self._coil_images(image_full.to(self.device).reshape(C, H, W, 2)))[0]
         m = image_metrics(ref, self._coil_images(pred))[1]
         psnr, ssim = m[:2].cpu().tolist()
-        return {"psnr": psnr, "ssim": ssim}
+        out = {"psnr": psnr, "ssim": ssim}
+        if bands is not None:
+            from .bands import band_report, band_stats, report_bounds
+            from .grid import GridSpec, grid_rows
+            steps = int((self.config.get("partition") or {}).get("no_steps", 40))
+            dist = grid_rows(GridSpec(C, H, W), 0, C * H * W, with_dist=True, device=self.device)[1]
+            out["bands"] = band_report(band_stats(dist, image_full.to(self.device).reshape(-1, 2), pred.reshape(-1, 2),
+                                                  bounds=report_bounds(bands, steps)))
+        return out
 
     @torch.no_grad()
     def save(self, directory: str, pred: torch.Tensor) -> list:
@@ -234,6 +244,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--chunk", type=int, default=None, help="rows per forward call")
     ap.add_argument("--compare", action="store_true", help="PSNR / SSIM against the data (native grid only)")
     ap.add_argument("--output_path", type=str, default=".")
+    from .bands import add_band_report_flag
+    add_band_report_flag(ap, "with --compare")
     return ap
 
 
@@ -265,6 +277,9 @@ def parse_args(argv=None):
         if any(getattr(opts, k) is not None for k in ("scale", "height", "width", "window", "coils")):
             ap.error("--compare is valid on the native grid, full window, all coils only "
                      "(drop --scale / --height / --width / --window / --coils)")
+    if opts.band_report is not None:
+        if not opts.compare:
+            ap.error("--band-report needs --compare (the report is the prediction's error against the data)")
     return opts
 
 
@@ -290,7 +305,10 @@ def main(argv=None) -> None:
     rows = pred.numel() // 2
     res = {"shape": list(pred.shape[:3]), "rows": rows, "seconds": seconds, "rows_per_s": rows / max(seconds, 1e-12)}
     if opts.compare:
-        res.update(rec.compare(pred, image))
+        from .bands import flag_bounds, format_band_table
+        res.update(rec.compare(pred, image, bands=flag_bounds(opts.band_report)))
+        if "bands" in res:
+            print(format_band_table(res["bands"]), flush=True)
     res["files"] = rec.save(opts.output_path, pred)
     print(json.dumps(res))
 

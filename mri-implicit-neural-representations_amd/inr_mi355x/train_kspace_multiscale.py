@@ -168,7 +168,8 @@ class MultiscaleTrainer(ResidentFit):
 
 def main():
     """CLI with the reference's flags (train_kspace_multiscale.py:50-52): --config, --output_path, --data_samples; the scan
-    comes from datasets.py, or a synthetic k-space with --synthetic C,H,W.  --val / --save-images as inr_mi355x.train."""
+    comes from datasets.py, or a synthetic k-space with --synthetic C,H,W.  --val / --save-images /
+    --band-report [N] as inr_mi355x.train."""
     opts, config = parse_cli()
     if config["model"] not in ("BoundedFourier",):
         config["model"] = "MultiscaleKFourier"  # train_kspace_multiscale.py:93-98: anything else is the unbounded net

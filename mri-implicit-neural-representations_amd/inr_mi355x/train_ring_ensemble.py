@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .cli import cli_data, cli_folders, cli_validation_images, parse_cli
+from .cli import cli_band_report, cli_data, cli_folders, cli_validation_images, parse_cli, print_band_tables
 from .engine import LossSpec
 from .train import MODELS, MFN_MODELS
 from .trainer_base import ResidentFit
@@ -83,6 +83,10 @@ class RingEnsembleTrainer(ResidentFit):
         self.jitter = float(jitter)
         self._rng = np.random.RandomState(seed)
         self._masks = {}
+
+    def _default_band_bounds(self):
+        """the ensemble's own rings"""
+        return [(self.radii[i], self.radii[i + 1]) for i in range(self.no_models)]
 
     def _inputs(self, lo: int, hi: int, train: bool = False):
         coords = self._t_coords if train else self.coords
@@ -173,11 +177,13 @@ class RingEnsembleTrainer(ResidentFit):
 
 def main():
     """python -m inr_mi355x.train_ring_ensemble --config cfg.yaml [--output_path out] [--synthetic C,H,W]
-    [--max_steps N] [--shuffle] [--shuffle-seed S] [--save-images]: fit the rings (radii from config['partition']), print
+    [--max_steps N] [--shuffle] [--shuffle-seed S] [--save-images] [--band-report [N]]: fit the rings (radii from
+    config['partition']), print
     one JSON line with the assembled reconstruction's PSNR / SSIM and save the submodel_%d files of
     train_clustering.py:243-249.  --save-images writes train.png / train_kspace.png and the final metrics()' pictures
     to <output_path>/images (the ring loop has no validation epoch), the submodels to <output_path>/checkpoints, and
-    prints the per-coil table."""
+    prints the per-coil table.  --band-report prints the final metrics()' error by radius (per ring of the ensemble, or N
+    rings) and adds it to the JSON line as 'bands'."""
     import json
     import os
     import time
@@ -186,12 +192,14 @@ def main():
     image, coords, shape = cli_data(opts, config, "coil", image_space=bool(config.get("transform", False)))
     tr = RingEnsembleTrainer(config, image, coords, shape, "cuda")
     ckpt_dir, image_dir = cli_folders(tr, opts)
+    cli_band_report(tr, opts)
     t0 = time.time()
     tr.fit(opts.max_steps, log_every=config.get("log_iter", 20))
     torch.cuda.synchronize()
     res = {"steps": tr.global_step, "seconds": time.time() - t0, "radii": tr.radii, "shuffle": tr.shuffle,
            "shuffle_seed": tr.shuffle_seed if tr.shuffle else None}
     res.update(tr.metrics())
+    print_band_tables(res)
     if image_dir is not None:
         last_epoch = max(0, -(-tr.global_step // tr.steps_per_epoch) - 1)
         cli_validation_images(tr, last_epoch, res, image_dir)

@@ -246,7 +246,10 @@ class ResidentFit(ValidationMixin):
         """PSNR and SSIM of the current model (validate() without the test loss and the best-epoch record)."""
         m = self._device_metrics(self.image_full, self.predict_all(), self.in_image_space)
         psnr_, ssim_ = m[:2].cpu().tolist()
-        return {"psnr": psnr_, "ssim": ssim_}
+        rec = {"psnr": psnr_, "ssim": ssim_}
+        if self._band_bounds is not None:
+            rec.update(self._last_bands)
+        return rec
 
     # ---- checkpoints -----------------------------------------------------------------------------
     def checkpoint(self) -> dict:

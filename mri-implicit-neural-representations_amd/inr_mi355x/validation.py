@@ -38,6 +38,9 @@ class ValidationMixin:
         self._keep_images = False  # enable_validation_images(): keep what the pictures are made of
         self._last_pred = None
         self._display_bufs = None
+        self._band_bounds = None  # enable_band_report(): the per-band report of validate() / metrics()
+        self._band_dist = None
+        self._last_bands = None
 
     def update_best(self, epoch: int, psnr: float, ssim: float) -> None:
         if psnr > self.best_psnr:
@@ -60,7 +63,37 @@ class ValidationMixin:
         image_metrics(self._ref_rss, coil_images(pred_flat, self.shape, in_image_space), rss, m, scratch)
         if self._keep_images:  # the sweep's output; its RSS image stays in the metric buffers
             self._last_pred = pred_flat
+        if self._band_bounds is not None:
+            self._last_bands = self._band_records(gt_flat, pred_flat)
         return m
+
+    # ---- error by radius (opt-in; nothing below runs unless enable_band_report() was called) ----
+    def _default_band_bounds(self):
+        """ring_bounds(config['partition']['no_steps']), or 40 rings when the config has no partition"""
+        from .bands import ring_bounds
+        return ring_bounds(int((getattr(self, "config", {}).get("partition") or {}).get("no_steps", 40)))
+
+    def enable_band_report(self, bounds=None) -> None:
+        """From now on validate() / metrics() add 'bands' to their record: bands.band_report of the prediction they score
+        against the full data, per band of radius (``bounds``: (lo, hi) pairs, or a number of rings; default: the rings of
+        the config's partition) -- and, on undersampled fits, 'bands_sampled' / 'bands_unsampled' for the rows the mask
+        kept / dropped.  The parameters and every other record entry stay what they are without it.  More than 64 bands
+        (the kernel's limit; a partition of more than 64 rings needs explicit ``bounds``), NaN or lo > hi: ValueError."""
+        from .bands import report_bounds
+        self._band_bounds = report_bounds(self._default_band_bounds() if bounds is None else bounds)
+
+    def _band_records(self, gt_flat: torch.Tensor, pred_flat: torch.Tensor) -> dict:
+        """The report(s) of the sweep ``pred_flat``: one kernel call each, one read-back for all of them."""
+        from .bands import band_report, band_stats_many
+        if self._band_dist is None:  # once: the radius of every row (the multiscale / ring fits hold it already)
+            d = getattr(self, "dist", None)
+            self._band_dist = d if d is not None else torch.sqrt(self.coords[:, 1] ** 2 + self.coords[:, 2] ** 2)
+        mask = getattr(self, "mask", None)
+        names, sel = ["bands"], [(None, 1)]
+        if mask is not None:
+            names, sel = names + ["bands_sampled", "bands_unsampled"], sel + [(mask, 1), (mask, 0)]
+        stats = band_stats_many(self._band_dist, gt_flat, pred_flat, sel, self._band_bounds)
+        return {k: band_report(s) for k, s in zip(names, stats)}
 
     # ---- pictures and per-coil table (opt-in; nothing below runs unless enable_validation_images() was called) ----
     def _display_source(self):
@@ -146,6 +179,8 @@ class ValidationMixin:
         test_loss = None if loss_sum is None else float(host[2]) / n_train_batches
         self.update_best(epoch, psnr, ssim)
         rec = {"epoch": epoch, "test_loss": test_loss, "psnr": psnr, "ssim": ssim}
+        if self._band_bounds is not None:
+            rec.update(self._last_bands)
         self.val_history.append(rec)
         return rec
 
