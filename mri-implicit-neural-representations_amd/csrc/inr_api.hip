@@ -61,6 +61,13 @@ struct inr_plan {
   inr_net_desc desc;
   NetDesc nd;
   int64_t packed_floats;
+  // where a step's weight gradients come from, fixed at creation (plan_set_dw_route): 0 the fused kernels' own passes,
+  // 1 the fp32 batch GEMM (inr_dw_gemm.hip), 2 the bf16 batch GEMM (inr_dw_gemm_bf16.hip).  Route 1: `gemm` holds what no
+  // batch changes -- items, TL, WB, sizes; a call copies it and fills in tiles and chunks -- and `gemm_cover` the flat
+  // range [lo, hi) or the layer mask those items cover
+  int dw_route = 0;
+  inr::DwGemmArgs gemm;
+  inr::SlabSplit gemm_cover;
   // split steps (step_schedule below): a low-priority stream for the part of the weight-gradient GEMM that runs beside
   // the fused kernel's last, partial round.  Created on first use, destroyed with the plan; the only state a plan has.
   mutable std::mutex side_mu;
@@ -120,6 +127,8 @@ static void dz_mark(const inr_plan* p, int kind, int64_t rows, int loss_kind) {
   p->dz_rows[kind] = rows;
   p->dz_loss[kind] = loss_kind;
 }
+
+static void plan_set_dw_route(inr_plan* p);
 
 // Multiplicative filter networks (models/mfn.py).  L[] = filters 0..n | linears 0..n-1 | heads; flat
 // parameters keep the state_dict order  linear.* , output_linear(.k).* , filters.*  (SURVEY Appendix B).
@@ -271,6 +280,7 @@ static int create_mfn_plan(const inr_net_desc* d, inr_plan** out) {
   nd.w2_off = nd.w2_bias_off = -1;
   nd.save_floats_per_tile = 3 * nd.mfn_stages * NB * 32 * TL + nd.L[0].Kblk * 32 * TL + TL;  // Kblk*32 >= 2 E'
   p->packed_floats = pk;
+  plan_set_dw_route(p);
   *out = p;
   return INR_OK;
 }
@@ -477,6 +487,7 @@ int inr_plan_create(const inr_net_desc* d, inr_plan** out) {
   p->packed_floats = pk;
   p->gemm_one_class = getenv("INR_GEMM_ONE_CLASS") != nullptr;
   if (const char* e = getenv("INR_GEMM_ENC_COST")) p->gemm_enc_cost = std::max(1.0, atof(e));
+  plan_set_dw_route(p);
   *out = p;
   return INR_OK;
 }
@@ -490,10 +501,9 @@ int inr_plan_destroy(inr_plan* plan) {
   return INR_OK;
 }
 
-// items, chunking and the flat-gradient range [lo, hi) of the layers the batch-level dW GEMM covers; false: the plan
-// keeps its in-kernel dW passes
-static bool dw_gemm_setup(const inr_plan* plan, int64_t nt, inr::DwGemmArgs* g, inr::SlabSplit* split) {
-  const NetDesc& nd = plan->nd;
+// items and the flat-gradient range [lo, hi) of the layers the batch-level dW GEMM covers -- everything of its arguments
+// that no batch changes; false: the plan keeps its in-kernel dW passes
+static bool dw_gemm_items(const NetDesc& nd, inr::DwGemmArgs* g, inr::SlabSplit* split) {
   memset(g, 0, sizeof(*g));
   split->lo = split->hi = split->n2 = 0;
   split->mask = 0;
@@ -507,7 +517,7 @@ static bool dw_gemm_setup(const inr_plan* plan, int64_t nt, inr::DwGemmArgs* g, 
     const int S = nd.mfn_stages, n = nd.mfn_n, HSZ = 16 * 32 * 64;
     if (2 * S - 1 > INR_DWG_MAX_ITEMS) return false;
     g->TL = 64, g->WB = 4;
-    g->save_floats_per_tile = nd.save_floats_per_tile, g->slab_floats = nd.slab_floats, g->n_tiles = (int)nt;
+    g->save_floats_per_tile = nd.save_floats_per_tile, g->slab_floats = nd.slab_floats;
     int k = 0;
     unsigned mask = 0;
     for (int t = 0; t < 2 * S - 1; ++t) {
@@ -520,12 +530,7 @@ static bool dw_gemm_setup(const inr_plan* plan, int64_t nt, inr::DwGemmArgs* g, 
       mask |= 1u << l;
     }
     g->n_items = k;
-    const int bpc = inr::dw_gemm_units(*g);
-    const int target = std::max(1, 256 / std::max(1, bpc));
-    g->tiles_per_chunk = (int)((nt + target - 1) / target);
-    g->n_chunks = (int)((nt + g->tiles_per_chunk - 1) / g->tiles_per_chunk);
     split->mask = mask;
-    split->n2 = g->n_chunks;
     return true;
   }
   // the plain MLP kernels, fp32: 256-row tensors (one wave per coordinate group) and the two-waves-per-group shapes
@@ -536,7 +541,6 @@ static bool dw_gemm_setup(const inr_plan* plan, int64_t nt, inr::DwGemmArgs* g, 
   g->WB = nd.NB == 12 ? 3 : 4;
   g->save_floats_per_tile = nd.save_floats_per_tile;
   g->slab_floats = nd.slab_floats;
-  g->n_tiles = (int)nt;
   int k = 0, covered = 0, lo = nd.P, hi = 0;
   auto add = [&](const LayerDesc& L, int g_off, int h_off) {
     inr::DwGemmItem& it = g->it[k++];
@@ -555,31 +559,41 @@ static bool dw_gemm_setup(const inr_plan* plan, int64_t nt, inr::DwGemmArgs* g, 
   }
   if (k == 0 || covered != hi - lo) return false;  // the covered layers must be one contiguous flat range
   g->n_items = k;
-  // about one workgroup per CU: the accumulators then stay in registers over as many tiles as possible
-  auto chunking = [&]() {
-    const int bpc = inr::dw_gemm_units(*g);
-    const int target = std::max(1, 256 / std::max(1, bpc));
-    g->tiles_per_chunk = (int)((nt + target - 1) / target);
-    g->n_chunks = (int)((nt + g->tiles_per_chunk - 1) / g->tiles_per_chunk);
-  };
-  chunking();
-  // short chunks (the graded 25 000 rows: K = 512 coordinates per 256 x 256 tile): half-height tiles over twice the K --
-  // half as many slabs to store at the end of the launch and to reduce (inr_dw_gemm.hip)
-  if (TL == 128 && g->WB == 4 && nt > 1 && (int64_t)g->tiles_per_chunk * TL < 1024) {
-    g->WBM = 2;
-    chunking();
-  }
   split->lo = lo;
   split->hi = hi;
-  split->n2 = g->n_chunks;
   return true;
 }
 
-// bf16 plans with the "weights in LDS" fused kernel: every weight gradient comes from inr_dw_gemm_bf16.hip
-static bool w2_plan(const inr_plan* plan) { return plan->nd.bf16 != 0; }
+// end of plan creation: where the plan's weight gradients come from (inr_plan::dw_route), and the fp32 GEMM's items
+static void plan_set_dw_route(inr_plan* p) {
+  p->dw_route = p->nd.bf16 ? 2 : (dw_gemm_items(p->nd, &p->gemm, &p->gemm_cover) ? 1 : 0);
+}
 
+// THE chunking rule: `n` tiles in equal chunks, about `target` of them
+static void chunk_tiles(int64_t n, int target, int* tiles_per_chunk, int* n_chunks) {
+  target = std::max(1, target);
+  *tiles_per_chunk = (int)((n + target - 1) / target);
+  *n_chunks = (int)((n + *tiles_per_chunk - 1) / *tiles_per_chunk);
+}
+
+// chunks of tiles [tile0, tile1) of the fp32 GEMM for about `max_wgs` workgroups (256: one per CU -- the accumulators
+// then stay in registers over as many tiles as possible)
+static void dw_gemm_chunk(inr::DwGemmArgs& g, int64_t tile0, int64_t tile1, int max_wgs) {
+  const int64_t n = tile1 - tile0;
+  g.tile0 = (int)tile0, g.n_tiles = (int)tile1;
+  g.WBM = 0;
+  chunk_tiles(n, max_wgs / std::max(1, inr::dw_gemm_units(g)), &g.tiles_per_chunk, &g.n_chunks);
+  // short chunks (the graded 25 000 rows: K = 512 coordinates per 256 x 256 tile): half-height tiles over twice the K --
+  // half as many slabs to store at the end of the launch and to reduce (inr_dw_gemm.hip)
+  if (g.TL == 128 && g.WB == 4 && n > 1 && (int64_t)g.tiles_per_chunk * g.TL < 1024) {
+    g.WBM = 2;
+    chunk_tiles(n, max_wgs / std::max(1, inr::dw_gemm_units(g)), &g.tiles_per_chunk, &g.n_chunks);
+  }
+}
+
+// bf16 plans with the "weights in LDS" fused kernel: every weight gradient comes from inr_dw_gemm_bf16.hip
 constexpr double kEncCost = 1.5;
-static void dw_gemm_bf16_setup(const inr_plan* plan, int64_t nt, inr::DwGemmBf16Args* g) {
+static void dw_gemm_bf16_setup(const inr_plan* plan, int64_t nt, inr::DwGemmBf16Args* g, inr::SlabSplit* red) {
   const NetDesc& nd = plan->nd;
   memset(g, 0, sizeof(*g));
   const int D = nd.D;
@@ -607,43 +621,21 @@ static void dw_gemm_bf16_setup(const inr_plan* plan, int64_t nt, inr::DwGemmBf16
   const int n_enc = (nd.E + 127) / 128, others = k - n_enc;
   const LayerDesc& L0 = nd.L[0];
   const bool run0 = L0.gb_off == L0.gw_off + L0.M * L0.K && (L0.gw_off & 3) == 0 && ((L0.gb_off + L0.M) & 3) == 0;
-  auto chunks = [&](int target, int* tpc, int* n) {
-    target = std::max(1, target);
-    *tpc = (int)((nt + target - 1) / target);
-    *n = (int)((nt + *tpc - 1) / *tpc);
-  };
   if (run0 && !plan->gemm_one_class) {
     const double cost = plan->gemm_enc_cost > 0.0 ? plan->gemm_enc_cost : kEncCost;
     const double per = 256.0 / (cost * n_enc + others);  // chunks of a non-first-layer unit
     g->n_enc_units = n_enc;
-    chunks((int)(per * cost), &g->tiles_per_chunk_enc, &g->n_chunks_enc);
-    chunks((256 - n_enc * g->n_chunks_enc) / others, &g->tiles_per_chunk, &g->n_chunks);
+    chunk_tiles(nt, (int)(per * cost), &g->tiles_per_chunk_enc, &g->n_chunks_enc);
+    chunk_tiles(nt, (256 - n_enc * g->n_chunks_enc) / others, &g->tiles_per_chunk, &g->n_chunks);
   } else {
     g->n_enc_units = n_enc;
-    chunks(256 / k, &g->tiles_per_chunk, &g->n_chunks);
+    chunk_tiles(nt, 256 / k, &g->tiles_per_chunk, &g->n_chunks);
     g->tiles_per_chunk_enc = g->tiles_per_chunk, g->n_chunks_enc = g->n_chunks;
   }
+  // how the reduction reads the chunk slabs
+  *red = inr::SlabSplit{0, (nd.P + 3) & ~3, g->n_chunks, 0};  // (a multiple of 4: the fast reduction works on float4)
+  if (g->n_chunks_enc != g->n_chunks) red->lo3 = L0.gw_off, red->hi3 = L0.gb_off + L0.M, red->n3 = g->n_chunks_enc;
 }
-
-// chunk slabs of the bf16 GEMM, and how the reduction reads them
-static int dw_gemm_bf16_slabs(const inr::DwGemmBf16Args& g) { return std::max(g.n_chunks, g.n_chunks_enc); }
-static inr::SlabSplit dw_gemm_bf16_split(const inr_plan* plan, const inr::DwGemmBf16Args& g) {
-  inr::SlabSplit split{0, (plan->nd.P + 3) & ~3, g.n_chunks, 0};  // (a multiple of 4: the fast reduction works on float4)
-  if (g.n_chunks_enc != g.n_chunks) {
-    const LayerDesc& L0 = plan->nd.L[0];
-    split.lo3 = L0.gw_off, split.hi3 = L0.gb_off + L0.M, split.n3 = g.n_chunks_enc;
-  }
-  return split;
-}
-
-static bool dw_gemm_plan(const inr_plan* plan) {
-  inr::DwGemmArgs g;
-  inr::SlabSplit split;
-  return dw_gemm_setup(plan, 1, &g, &split);
-}
-
-// fused steps of these plans stash per TILE (n_tiles slots): a batch-level GEMM reads the whole batch's stash
-static bool step_save_by_tile(const inr_plan* plan) { return dw_gemm_plan(plan) || w2_plan(plan); }
 
 // ---------------------------------------------------------------------------------------------
 // How a fused step of a batch-GEMM plan is launched.  With more tiles than workgroups the persistent grid runs whole
@@ -663,55 +655,31 @@ constexpr double kGemmTileShare = 0.4;
 struct StepSchedule {
   bool split;
   int64_t full, rem, tA;
-  inr::DwGemmArgs gA, gB;  // (gB alone when !split)
+  inr::DwGemmArgs gA, gB;  // (split only)
   inr::SlabSplit red;      // for the reduction: n2 = all chunk slabs
 };
 
-static bool overlap_enabled() {  // (read per call: a test compares the two schedules in one process)
-  const char* e = getenv("INR_OVERLAP");
-  return !(e != nullptr && e[0] == '0');
-}
-
-// chunks of tiles [tile0, tile1) for about `max_wgs` workgroups (same rules as dw_gemm_setup: half-height tiles for short chunks)
-static void rechunk(inr::DwGemmArgs& g, int64_t tile0, int64_t tile1, int max_wgs) {
-  const int64_t n = tile1 - tile0;
-  g.tile0 = (int)tile0, g.n_tiles = (int)tile1;
-  auto chunking = [&]() {
-    const int units = std::max(1, inr::dw_gemm_units(g));
-    const int target = std::max(1, max_wgs / units);
-    g.tiles_per_chunk = (int)((n + target - 1) / target);
-    g.n_chunks = (int)((n + g.tiles_per_chunk - 1) / g.tiles_per_chunk);
-  };
-  g.WBM = 0;
-  chunking();
-  if (g.TL == 128 && g.WB == 4 && n > 1 && (int64_t)g.tiles_per_chunk * g.TL < 1024) {
-    g.WBM = 2;
-    chunking();
-  }
-}
-
-static bool step_schedule(const inr_plan* plan, int64_t nt, int64_t nb, StepSchedule* sc) {
+// `plain_red`: the reduction of the unsplit GEMM over the whole batch
+static void step_schedule(const inr_plan* plan, int64_t nt, int64_t nb, bool overlap, const inr::SlabSplit& plain_red,
+                          StepSchedule* sc) {
   sc->split = false;
   sc->full = nt, sc->rem = 0, sc->tA = 0;
-  if (!dw_gemm_setup(plan, nt, &sc->gB, &sc->red)) return false;
-  sc->gA = sc->gB;
-  sc->gA.n_chunks = 0;
-  if (!overlap_enabled() || nt <= nb || nt % nb == 0) return true;
+  sc->red = plain_red;
+  if (!overlap || nt <= nb || nt % nb == 0) return;
   const int64_t rem = nt % nb, full = nt - rem, idle = nb - rem;
   {
-    inr::DwGemmArgs probe = sc->gB;
-    probe.WBM = 0;
-    if (idle < inr::dw_gemm_units(probe)) return true;  // not even one chunk's workgroups fit beside the partial round
+    inr::DwGemmArgs probe = plan->gemm;  // (WBM = 0)
+    if (idle < inr::dw_gemm_units(probe)) return;  // not even one chunk's workgroups fit beside the partial round
   }
   int64_t tA = (int64_t)(0.9 * (double)idle / kGemmTileShare);
   if (tA > full) tA = full;
-  if (tA < nt / 16 || tA < 1) return true;  // nothing worth a second launch
-  rechunk(sc->gA, 0, tA, (int)idle);
-  rechunk(sc->gB, tA, nt, 256);
+  if (tA < nt / 16 || tA < 1) return;  // nothing worth a second launch
+  sc->gA = sc->gB = plan->gemm;
+  dw_gemm_chunk(sc->gA, 0, tA, (int)idle);
+  dw_gemm_chunk(sc->gB, tA, nt, 256);
   sc->split = true;
   sc->full = full, sc->rem = rem, sc->tA = tA;
   sc->red.n2 = sc->gA.n_chunks + sc->gB.n_chunks;
-  return true;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -755,17 +723,73 @@ static RsSchedule rs_schedule(int64_t nt) {
   return s;
 }
 
-static bool rs_plan(const inr_plan* plan) { return plan->nd.rs != 0; }
 // Which fused kernel runs a batch of nt 128-coordinate slots?  The row-split kernel, unless inr_mlp_kernel's rounds of 256
 // tiles are (all but) full: then both do the same MFMA work and the row-split kernel only adds a round (65 536 rows:
 // 6 + 6 + 4 column blocks per workgroup, 649 us against 629 us; 25 000 rows: 266 us against 316 us).
-// INR_RS=0 / 1 in the environment forces one or the other (read per call: tests compare the two in one process).
-static bool rs_enabled(int64_t nt) {
-  const char* e = getenv("INR_RS");
+// INR_RS=0 / 1 in the environment (`e`) forces one or the other.
+static bool rs_enabled(const char* e, int64_t nt) {
   if (e != nullptr && e[0] == '0') return false;
   if (e != nullptr && e[0] == '1') return true;
   const int64_t rounds = (nt + kMaxBlocks - 1) / kMaxBlocks;
   return (double)nt < 0.97 * (double)(rounds * kMaxBlocks);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The launch layout of one ABI call: a function of the plan, the batch size and the two per-call environment switches,
+// and of nothing else.  Every entry derives it ONCE (call_layout), checks the caller's workspace against it and launches
+// from it, so the sizes that were checked are the sizes that are written.
+// ---------------------------------------------------------------------------------------------
+struct CallLayout {
+  int64_t nt, nb;               // tiles of the batch; workgroups of inr_mlp_kernel / the filter / bf16 kernels
+  int64_t save_slots, n_slabs;  // a fused step's workspace: what inr_plan_workspace reports
+  // dw_route 1
+  bool rs;                      // the row-split kernel runs the fused step
+  RsSchedule rsched;            // row-split plans (whichever kernel runs: the slabs cover its grid)
+  inr::DwGemmArgs plain;        // the GEMM over the whole batch: unfused backward, row-split and unsplit steps
+  inr::SlabSplit plain_red;
+  StepSchedule step;            // (split = false on every other route)
+  // dw_route 2
+  inr::DwGemmBf16Args bf16;
+  inr::SlabSplit bf16_red;
+};
+
+// B >= 1.  INR_RS and INR_OVERLAP are read here, per call: tests flip them between calls on one plan in one process
+static void call_layout(const inr_plan* plan, int64_t B, CallLayout* c) {
+  const NetDesc& nd = plan->nd;
+  const char* e_rs = getenv("INR_RS");
+  const char* e_overlap = getenv("INR_OVERLAP");
+  const int tl = 32 * nd.NW;
+  const int64_t nt = c->nt = (B + tl - 1) / tl;
+  c->nb = nt < kMaxBlocks ? nt : kMaxBlocks;
+  if (nd.bf16) {  // the bf16 kernel's workgroups take two 128-coordinate tiles each
+    const int64_t wt = nt > kMaxBlocks ? (nt + 1) / 2 : nt;  // (one each while that fills fewer CUs)
+    c->nb = wt < kMaxBlocks ? wt : kMaxBlocks;
+  }
+  // fused steps of batch-GEMM plans stash per TILE (n_tiles slots): the GEMM reads the whole batch's stash
+  c->save_slots = plan->dw_route != 0 ? nt : c->nb;
+  c->n_slabs = c->nb;
+  c->rs = false;
+  c->step.split = false;
+  if (plan->dw_route == 2) {  // (the unfused backward of these plans needs nb slabs only: covered)
+    dw_gemm_bf16_setup(plan, nt, &c->bf16, &c->bf16_red);
+    c->n_slabs = c->nb + std::max(c->bf16.n_chunks, c->bf16.n_chunks_enc);
+  } else if (plan->dw_route == 1) {
+    c->plain = plan->gemm;
+    dw_gemm_chunk(c->plain, 0, nt, 256);
+    c->plain_red = plan->gemm_cover;
+    c->plain_red.n2 = c->plain.n_chunks;
+    // (a split step has its own chunking; the unfused backward keeps the plain one)
+    step_schedule(plan, nt, c->nb, !(e_overlap != nullptr && e_overlap[0] == '0'), c->plain_red, &c->step);
+    // (row-split fused steps run rs_schedule's grid -- more workgroups than tiles while the batch is under 256 slots; the
+    // workspace does not follow INR_RS: it covers both fused kernels' grids)
+    int64_t grid = c->nb;
+    if (nd.rs) {
+      c->rsched = rs_schedule(nt);
+      c->rs = rs_enabled(e_rs, nt);
+      grid = std::max<int64_t>(grid, c->rsched.grid);
+    }
+    c->n_slabs = grid + std::max(c->plain.n_chunks, c->step.red.n2);
+  }
 }
 
 static int launch_rs(const inr_plan* plan, const LossDesc& ld, inr::MlpArgs a, int64_t nt, const RsSchedule& sc,
@@ -832,6 +856,13 @@ static int check_ws(const inr_plan* plan, const inr_workspace* ws, int64_t save_
   return INR_OK;
 }
 
+// B and, from it, the call's layout: the one place an entry learns its tiles, grids, chunks and workspace
+static int begin_call(const inr_plan* plan, int64_t B, const char* who, CallLayout* c) {
+  if (B <= 0) return fail(INR_ERR_INVALID, "%s: B = %lld", who, (long long)B);
+  call_layout(plan, B, c);
+  return INR_OK;
+}
+
 int inr_plan_sizes(const inr_plan* plan, inr_sizes* out) {
   if (plan == nullptr || out == nullptr) return fail(INR_ERR_INVALID, "inr_plan_sizes: null argument");
   out->n_params = plan->nd.P;
@@ -840,49 +871,32 @@ int inr_plan_sizes(const inr_plan* plan, inr_sizes* out) {
   out->save_bytes_per_tile = (int64_t)plan->nd.save_floats_per_tile * 4;
   out->max_blocks = kMaxBlocks;
   out->slab_floats = plan->nd.slab_floats;
-  out->step_save_by_tile = step_save_by_tile(plan) ? 1 : 0;
+  out->step_save_by_tile = plan->dw_route != 0 ? 1 : 0;
   return INR_OK;
 }
 
+// (the readers of a call's layout report a bad B in inr_plan_launch_dims' name, all three)
 int inr_plan_workspace(const inr_plan* plan, int64_t B, int64_t* step_save_slots, int64_t* n_slabs) {
   if (plan == nullptr || step_save_slots == nullptr || n_slabs == nullptr)
     return fail(INR_ERR_INVALID, "inr_plan_workspace: null argument");
-  int64_t nt, nb;
-  int rc = inr_plan_launch_dims(plan, B, &nt, &nb);
-  if (rc != INR_OK) return rc;
-  *step_save_slots = step_save_by_tile(plan) ? nt : nb;
-  *n_slabs = nb;
-  if (w2_plan(plan)) {  // (the unfused backward of these plans needs nb slabs only: covered)
-    inr::DwGemmBf16Args g;
-    dw_gemm_bf16_setup(plan, nt, &g);
-    *n_slabs = nb + dw_gemm_bf16_slabs(g);
-  }
-  if (dw_gemm_plan(plan)) {
-    inr::DwGemmArgs g;
-    inr::SlabSplit split;
-    dw_gemm_setup(plan, nt, &g, &split);
-    StepSchedule sc;
-    step_schedule(plan, nt, nb, &sc);  // (a split step has its own chunking; the unfused backward keeps the plain one)
-    // (row-split fused steps run rs_schedule's grid -- more workgroups than tiles while the batch is under 256 slots)
-    const int64_t nb_rs = rs_plan(plan) ? std::max<int64_t>(nb, rs_schedule(nt).grid) : nb;
-    *n_slabs = nb_rs + std::max(g.n_chunks, sc.red.n2);
-  }
+  CallLayout c;
+  if (int rc = begin_call(plan, B, "inr_plan_launch_dims", &c)) return rc;
+  *step_save_slots = c.save_slots, *n_slabs = c.n_slabs;
   return INR_OK;
 }
 
 int inr_plan_step_info(const inr_plan* plan, int64_t B, inr_step_info* out) {
   if (plan == nullptr || out == nullptr) return fail(INR_ERR_INVALID, "inr_plan_step_info: null argument");
-  int64_t nt, nb;
-  const int rc = inr_plan_launch_dims(plan, B, &nt, &nb);
-  if (rc != INR_OK) return rc;
+  CallLayout c;
+  if (int rc = begin_call(plan, B, "inr_plan_launch_dims", &c)) return rc;
   memset(out, 0, sizeof(*out));
   out->hidden_blocks = plan->nd.NB;
-  if (rs_plan(plan) && dw_gemm_plan(plan) && rs_enabled(nt)) {
-    const RsSchedule s = rs_schedule(nt);
+  if (c.rs) {
+    const RsSchedule& s = c.rsched;
     out->row_split = 1, out->ncb = s.ncb, out->grid = s.grid, out->rounds = s.rounds;
     out->hi = s.hi, out->lo = s.lo, out->n_hi = s.x;
   } else {
-    out->grid = (int32_t)nb, out->rounds = (int32_t)((nt + nb - 1) / nb);
+    out->grid = (int32_t)c.nb, out->rounds = (int32_t)((c.nt + c.nb - 1) / c.nb);
   }
   return INR_OK;
 }
@@ -901,14 +915,9 @@ int inr_plan_grad_scale_state(const inr_plan* plan, float* host_out, void* strea
 int inr_plan_launch_dims(const inr_plan* plan, int64_t B, int64_t* n_tiles, int64_t* n_blocks) {
   if (plan == nullptr || n_tiles == nullptr || n_blocks == nullptr)
     return fail(INR_ERR_INVALID, "inr_plan_launch_dims: null argument");
-  if (B <= 0) return fail(INR_ERR_INVALID, "inr_plan_launch_dims: B = %lld", (long long)B);
-  const int tl = 32 * plan->nd.NW;
-  *n_tiles = (B + tl - 1) / tl;
-  *n_blocks = *n_tiles < kMaxBlocks ? *n_tiles : kMaxBlocks;
-  if (plan->nd.bf16) {  // the bf16 kernel's workgroups take two 128-coordinate tiles each
-    const int64_t wt = *n_tiles > kMaxBlocks ? (*n_tiles + 1) / 2 : *n_tiles;  // (one each while that fills fewer CUs)
-    *n_blocks = wt < kMaxBlocks ? wt : kMaxBlocks;
-  }
+  CallLayout c;
+  if (int rc = begin_call(plan, B, "inr_plan_launch_dims", &c)) return rc;
+  *n_tiles = c.nt, *n_blocks = c.nb;
   return INR_OK;
 }
 
@@ -980,36 +989,76 @@ int inr_encode_gauss(const float* coords, const float* enc_B, int64_t B, int32_t
   return INR_OK;
 }
 
-int inr_forward(const inr_plan* plan, const float* params, const float* packed, const float* x,
-                const float* enc_B, int64_t B, float* out, const inr_workspace* ws, void* stream) {
-  if (plan == nullptr || params == nullptr || packed == nullptr || x == nullptr || out == nullptr)
-    return fail(INR_ERR_INVALID, "inr_forward: null argument");
-  if (plan->nd.mfn_n > 0) return fail(INR_ERR_INVALID, "inr_forward: multiplicative-filter plans use inr_forward_multi");
-  if (plan->nd.input == IN_GAUSS && enc_B == nullptr) return fail(INR_ERR_INVALID, "inr_forward: enc_B is null");
-  float* save = ws != nullptr ? ws->save : nullptr;
-  if (plan->nd.hact == ACT_GABOR2D && save == nullptr)
-    return fail(INR_ERR_INVALID, "inr_forward: WIRE2D plans need a save buffer (n_tiles * save_floats_per_tile floats)");
-  if (B <= 0) return fail(INR_ERR_INVALID, "inr_forward: B = %lld", (long long)B);
-  int64_t nt, nb;
-  inr_plan_launch_dims(plan, B, &nt, &nb);
-  if (save != nullptr) {
-    const int rc = check_ws(plan, ws, nt, 0, "inr_forward");
-    if (rc != INR_OK) return rc;
-  }
+// ---- the six network calls: one prologue ----
+// Null pointers, the plan's family and what its input needs, in the order every entry has always reported them: plain
+// entries name the family first, the _multi ones the inputs (`need_dist`: forward / backward of a bounded model).
+static int check_net_call(const char* who, bool null_arg, const inr_plan* plan, bool multi, const float* enc_B,
+                          bool need_dist, const float* dist) {
+  if (null_arg) return fail(INR_ERR_INVALID, "%s: null argument", who);
+  if (!multi && plan->nd.mfn_n > 0) return fail(INR_ERR_INVALID, "%s: multiplicative-filter plans use %s_multi", who, who);
+  if (plan->nd.input == IN_GAUSS && enc_B == nullptr) return fail(INR_ERR_INVALID, "%s: enc_B is null", who);
+  if (need_dist && plan->nd.bounded && dist == nullptr) return fail(INR_ERR_INVALID, "%s: bounded model needs dist", who);
+  if (multi && plan->nd.mfn_n == 0) return fail(INR_ERR_INVALID, "%s: not a multiplicative-filter plan", who);
+  return INR_OK;
+}
+
+static int check_step_loss(const char* who, const inr_plan* plan, const inr_loss_desc* loss) {
+  if (loss->kind < INR_LOSS_L2_HALF || loss->kind > INR_LOSS_CENTER)
+    return fail(INR_ERR_INVALID, "%s: loss kind %d", who, loss->kind);
+  if (loss->kind >= INR_LOSS_LOGSPACE && plan->nd.out_f != 2)
+    return fail(INR_ERR_INVALID, "%s: complex-row losses need out_features == 2", who);
+  return INR_OK;
+}
+
+// kernel arguments every network call shares; the entry adds its outputs / targets
+static inr::MlpArgs net_args(const float* params, const float* packed, const float* x, const float* enc_B, int64_t B,
+                             const CallLayout& c, const inr_workspace* ws) {
   inr::MlpArgs a;
   memset(&a, 0, sizeof(a));
   a.params = params;
   a.packed = packed;
   a.x = x;
   a.encB = enc_B;
-  a.out = out;
-  a.save = save;
   a.B = B;
-  a.n_tiles = (int)nt;
+  a.n_tiles = (int)c.nt;
+  if (ws != nullptr) a.save = ws->save;
+  return a;
+}
+
+// ... and those of a fused step (mode 2): slabs, the plan's weight-gradient route, per-tile or per-workgroup stash
+static int step_args(const inr_plan* plan, const inr_workspace* ws, const char* who, inr::MlpArgs* a) {
+  a->slabs = ws->slabs;
+  a->dw_gemm = plan->dw_route;
+  a->save_by_block = a->dw_gemm ? 0 : 1;
+  if (a->dw_gemm == 2) {
+    a->dz_state = dz_state_alloc(plan);
+    if (a->dz_state == nullptr) return fail(INR_ERR_HIP, "%s: no gradient-scale state on this device", who);
+  }
+#ifdef INR_STAMPS
+  a->dbg = g_stamp_buf;
+  a->dbg_cap = g_stamp_cap;
+#endif
+  return INR_OK;
+}
+
+int inr_forward(const inr_plan* plan, const float* params, const float* packed, const float* x,
+                const float* enc_B, int64_t B, float* out, const inr_workspace* ws, void* stream) {
+  const char* who = "inr_forward";
+  const bool null_arg = plan == nullptr || params == nullptr || packed == nullptr || x == nullptr || out == nullptr;
+  if (int rc = check_net_call(who, null_arg, plan, false, enc_B, false, nullptr)) return rc;
+  const bool saving = ws != nullptr && ws->save != nullptr;
+  if (plan->nd.hact == ACT_GABOR2D && !saving)
+    return fail(INR_ERR_INVALID, "inr_forward: WIRE2D plans need a save buffer (n_tiles * save_floats_per_tile floats)");
+  CallLayout c;
+  if (int rc = begin_call(plan, B, who, &c)) return rc;
+  if (saving)
+    if (int rc = check_ws(plan, ws, c.nt, 0, who)) return rc;
+  inr::MlpArgs a = net_args(params, packed, x, enc_B, B, c, ws);
+  a.out = out;
   a.save_by_block = 0;
   LossDesc ld;
   memset(&ld, 0, sizeof(ld));
-  return launch(plan, ld, a, 0, (int)nb, (hipStream_t)stream);
+  return launch(plan, ld, a, 0, (int)c.nb, (hipStream_t)stream);
 }
 
 // the Adam update folded into the slab reduction's launch (inr_train_adam_step)
@@ -1027,14 +1076,14 @@ static hipError_t reduce_stage(const inr_plan* plan, const float* slabs, int nb,
   return inr::launch_reduce_slabs(plan->nd, slabs, nb, grads, loss_out, params, packed, st, split);
 }
 
-// dW GEMM (plans that use it) + deterministic slab reduction into flat gradients
-static int finish_gradients(const inr_plan* plan, const inr::MlpArgs& a, int64_t nt, int64_t nb, float* grads,
+// dW GEMM over the whole batch (plans that use it), its chunk slabs behind the `nb` workgroup slabs of the kernel that
+// ran, + deterministic slab reduction into flat gradients
+static int finish_gradients(const inr_plan* plan, const inr::MlpArgs& a, const CallLayout& c, int64_t nb, float* grads,
                             float* loss_out, const float* params, const float* packed, hipStream_t st,
                             const char* who, const AdamFuse* af = nullptr) {
   inr::SlabSplit split{0, 0, 0, 0};
   if (a.dw_gemm == 2) {  // bf16 fused step: all of dW / db from the bf16 batch GEMM, summed over its chunk slabs
-    inr::DwGemmBf16Args g;
-    dw_gemm_bf16_setup(plan, nt, &g);
+    inr::DwGemmBf16Args g = c.bf16;
     g.save = a.save;
     g.slabs = a.slabs + (size_t)nb * plan->nd.slab_floats;
     g.coords = a.x;
@@ -1044,14 +1093,14 @@ static int finish_gradients(const inr_plan* plan, const inr::MlpArgs& a, int64_t
     g.dz_count = a.dz_state + 8 + (a.dout != nullptr ? 2 : 0);
     hipError_t e = inr::launch_dw_gemm_bf16(g, st);
     if (e != hipSuccess) return hip_fail(e, (std::string(who) + ": bf16 weight-gradient GEMM").c_str());
-    split = dw_gemm_bf16_split(plan, g);
+    split = c.bf16_red;
   } else if (a.dw_gemm) {
-    inr::DwGemmArgs g;
-    dw_gemm_setup(plan, nt, &g, &split);
+    inr::DwGemmArgs g = c.plain;
     g.save = a.save;
     g.slabs = a.slabs + (size_t)nb * plan->nd.slab_floats;
     hipError_t e = inr::launch_dw_gemm(g, st);
     if (e != hipSuccess) return hip_fail(e, (std::string(who) + ": weight-gradient GEMM").c_str());
+    split = c.plain_red;
   }
   hipError_t e = reduce_stage(plan, a.slabs, (int)nb, grads, loss_out, params, packed, st, split, af);
   if (e != hipSuccess) return hip_fail(e, (std::string(who) + ": slab reduction").c_str());
@@ -1061,66 +1110,52 @@ static int finish_gradients(const inr_plan* plan, const inr::MlpArgs& a, int64_t
 int inr_backward(const inr_plan* plan, const float* params, const float* packed, const float* x,
                  const float* enc_B, int64_t B, const float* dout, const inr_workspace* ws,
                  float* grads, void* stream) {
-  if (plan == nullptr || params == nullptr || packed == nullptr || x == nullptr || dout == nullptr ||
-      ws == nullptr || grads == nullptr)
-    return fail(INR_ERR_INVALID, "inr_backward: null argument");
-  if (plan->nd.mfn_n > 0) return fail(INR_ERR_INVALID, "inr_backward: multiplicative-filter plans use inr_backward_multi");
-  if (plan->nd.input == IN_GAUSS && enc_B == nullptr) return fail(INR_ERR_INVALID, "inr_backward: enc_B is null");
-  if (B <= 0) return fail(INR_ERR_INVALID, "inr_backward: B = %lld", (long long)B);
-  int64_t nt, nb, slots, n_slabs;
-  inr_plan_launch_dims(plan, B, &nt, &nb);
-  inr_plan_workspace(plan, B, &slots, &n_slabs);
-  {
-    const int rc = check_ws(plan, ws, nt, n_slabs, "inr_backward");
-    if (rc != INR_OK) return rc;
-  }
-  inr::MlpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.params = params;
-  a.packed = packed;
-  a.x = x;
-  a.encB = enc_B;
+  const char* who = "inr_backward";
+  const bool null_arg = plan == nullptr || params == nullptr || packed == nullptr || x == nullptr || dout == nullptr ||
+                        ws == nullptr || grads == nullptr;
+  if (int rc = check_net_call(who, null_arg, plan, false, enc_B, false, nullptr)) return rc;
+  CallLayout c;
+  if (int rc = begin_call(plan, B, who, &c)) return rc;
+  if (int rc = check_ws(plan, ws, c.nt, c.n_slabs, who)) return rc;
+  inr::MlpArgs a = net_args(params, packed, x, enc_B, B, c, ws);
   a.dout = dout;
-  a.save = ws->save;
   a.slabs = ws->slabs;
-  a.B = B;
-  a.n_tiles = (int)nt;
   a.save_by_block = 0;
-  a.dw_gemm = w2_plan(plan) ? 2 : (dw_gemm_plan(plan) ? 1 : 0);
+  a.dw_gemm = plan->dw_route;
   LossDesc ld;
   memset(&ld, 0, sizeof(ld));
-  if (w2_plan(plan)) {
+  if (a.dw_gemm == 2) {
     a.dz_state = dz_state_alloc(plan);
     if (a.dz_state == nullptr) return fail(INR_ERR_HIP, "inr_backward: no gradient-scale state on this device");
     if (dz_needs_calibration(plan, 1, B, 0)) {  // a pass for the scale (the forward half's stash is not touched)
-      int rc = launch(plan, ld, a, 1, (int)nb, (hipStream_t)stream);
+      int rc = launch(plan, ld, a, 1, (int)c.nb, (hipStream_t)stream);
       if (rc != INR_OK) return rc;
       hipError_t e = inr::launch_dz_roll(a.dz_state + 4, nullptr, (hipStream_t)stream);
       if (e != hipSuccess) return hip_fail(e, "inr_backward: gradient-scale calibration");
     }
   }
-  int rc = launch(plan, ld, a, 1, (int)nb, (hipStream_t)stream);
+  int rc = launch(plan, ld, a, 1, (int)c.nb, (hipStream_t)stream);
   if (rc != INR_OK) return rc;
-  if (w2_plan(plan)) dz_mark(plan, 1, B, 0);
-  return finish_gradients(plan, a, nt, nb, grads, nullptr, params, packed, (hipStream_t)stream, "inr_backward");
+  if (a.dw_gemm == 2) dz_mark(plan, 1, B, 0);
+  return finish_gradients(plan, a, c, c.nb, grads, nullptr, params, packed, (hipStream_t)stream, who);
 }
 
-// fused step (mode 2) + weight gradients + reduction, split over two streams where step_schedule says so
-static int run_fused_step(const inr_plan* plan, const LossDesc& ld, const inr::MlpArgs& a, int64_t nt, int64_t nb,
+// fused step (mode 2) + weight gradients + reduction, split over two streams where the layout's StepSchedule says so
+static int run_fused_step(const inr_plan* plan, const LossDesc& ld, const inr::MlpArgs& a, const CallLayout& c,
                           float* grads, float* loss_out, const float* params, const float* packed, hipStream_t st,
                           const char* who, const AdamFuse* af = nullptr) {
-  if (a.dw_gemm == 1 && rs_plan(plan) && rs_enabled(nt)) {
+  const int64_t nb = c.nb;
+  if (c.rs) {
     // row-split kernel: one launch of whole rounds (no partial round to overlap), then the batch GEMM and the reduction
     // over its grid's slabs
-    const RsSchedule rs = rs_schedule(nt);
-    int rc = launch_rs(plan, ld, a, nt, rs, st);
+    int rc = launch_rs(plan, ld, a, c.nt, c.rsched, st);
     if (rc != INR_OK) return rc;
     if (grads == nullptr) return INR_OK;
-    return finish_gradients(plan, a, nt, rs.grid, grads, loss_out, params, packed, st, who, af);
+    return finish_gradients(plan, a, c, c.rsched.grid, grads, loss_out, params, packed, st, who, af);
   }
-  StepSchedule sc;
+  const StepSchedule& sc = c.step;
   hipStream_t side = nullptr;
-  if (grads != nullptr && a.dw_gemm == 1 && step_schedule(plan, nt, nb, &sc) && sc.split) side = side_stream(plan);
+  if (grads != nullptr && sc.split) side = side_stream(plan);
   if (a.dw_gemm == 2 && dz_needs_calibration(plan, 0, a.B, ld.kind)) {  // bf16: a pass of the kernel for the scale
     int rc = launch(plan, ld, a, 2, (int)nb, st);
     if (rc != INR_OK) return rc;
@@ -1132,25 +1167,26 @@ static int run_fused_step(const inr_plan* plan, const LossDesc& ld, const inr::M
     if (rc != INR_OK) return rc;
     if (a.dw_gemm == 2) dz_mark(plan, 0, a.B, ld.kind);
     if (grads == nullptr) return INR_OK;  // profiling: leave the per-block slabs unreduced
-    return finish_gradients(plan, a, nt, nb, grads, loss_out, params, packed, st, who, af);
+    return finish_gradients(plan, a, c, nb, grads, loss_out, params, packed, st, who, af);
   }
   const hipEvent_t fork = plan->fork, join = plan->join;  // (created once, with the side stream)
   float* chunk_slabs = a.slabs + (size_t)nb * plan->nd.slab_floats;
   inr::MlpArgs a1 = a, a2 = a;
   a1.n_tiles = (int)sc.full;
   a2.tile0 = (int)sc.full, a2.accumulate = 1;
-  sc.gA.save = sc.gB.save = a.save;
-  sc.gA.slabs = chunk_slabs;
-  sc.gB.slabs = chunk_slabs + (size_t)sc.gA.n_chunks * plan->nd.slab_floats;
+  inr::DwGemmArgs gA = sc.gA, gB = sc.gB;
+  gA.save = gB.save = a.save;
+  gA.slabs = chunk_slabs;
+  gB.slabs = chunk_slabs + (size_t)gA.n_chunks * plan->nd.slab_floats;
   int rc = launch(plan, ld, a1, 2, (int)nb, st);
   hipError_t e = hipSuccess;
   if (rc == INR_OK) e = hipEventRecord(fork, st);
   if (rc == INR_OK && e == hipSuccess) rc = launch(plan, ld, a2, 2, (int)sc.rem, st);  // (queued before the GEMM: the critical path)
   if (rc == INR_OK && e == hipSuccess) e = hipStreamWaitEvent(side, fork, 0);
-  if (rc == INR_OK && e == hipSuccess) e = inr::launch_dw_gemm(sc.gA, side);
+  if (rc == INR_OK && e == hipSuccess) e = inr::launch_dw_gemm(gA, side);
   if (rc == INR_OK && e == hipSuccess) e = hipEventRecord(join, side);
   if (rc == INR_OK && e == hipSuccess) e = hipStreamWaitEvent(st, join, 0);
-  if (rc == INR_OK && e == hipSuccess) e = inr::launch_dw_gemm(sc.gB, st);
+  if (rc == INR_OK && e == hipSuccess) e = inr::launch_dw_gemm(gB, st);
   if (rc == INR_OK && e == hipSuccess)
     e = reduce_stage(plan, a.slabs, (int)nb, grads, loss_out, params, packed, st, sc.red, af);
   if (rc != INR_OK) return rc;
@@ -1207,14 +1243,20 @@ int inr_loss_grad_multi(const inr_loss_desc* loss, const float* outs, const floa
   return INR_OK;
 }
 
+// weights of the TV term's horizontal and vertical differences of a W x H image
+static void tv_coeffs(float weight, int64_t W, int64_t H, float* cw, float* ch) {
+  *cw = (float)((double)weight / ((double)H * (double)(W - 1) * 2.0));
+  *ch = (float)((double)weight / ((double)(H - 1) * (double)W * 2.0));
+}
+
 int inr_tv_grad(const float* out, int64_t R, int64_t R_own, int64_t W, int64_t H, float weight,
                 float* loss_out, float* dout, void* stream) {
   if (out == nullptr || loss_out == nullptr || dout == nullptr) return fail(INR_ERR_INVALID, "inr_tv_grad: null argument");
   if (R <= 0 || R_own <= 0 || R_own > R || R > R_own + 1 || W < 2 || H < 2 || R > H)
     return fail(INR_ERR_INVALID, "inr_tv_grad: R %lld R_own %lld W %lld H %lld", (long long)R, (long long)R_own,
                 (long long)W, (long long)H);
-  const float cw = (float)((double)weight / ((double)H * (double)(W - 1) * 2.0));
-  const float ch = (float)((double)weight / ((double)(H - 1) * (double)W * 2.0));
+  float cw, ch;
+  tv_coeffs(weight, W, H, &cw, &ch);
   hipError_t e = inr::launch_tv_grad(out, R, R_own, W, cw, ch, loss_out, dout, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "inr_tv_grad");
   return INR_OK;
@@ -1231,8 +1273,8 @@ int inr_loss_tv_grad(const inr_loss_desc* loss, const float* out, const float* g
                 (long long)W, (long long)H);
   LossDesc ld;
   to_loss_desc(loss, &ld);
-  const float cw = (float)((double)tv_weight / ((double)H * (double)(W - 1) * 2.0));
-  const float ch = (float)((double)tv_weight / ((double)(H - 1) * (double)W * 2.0));
+  float cw, ch;
+  tv_coeffs(tv_weight, W, H, &cw, &ch);
   hipError_t e = inr::launch_loss_tv_grad(ld, out, gt, mask, R, R_own, W, cw, ch, loss_out, dout, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "inr_loss_tv_grad");
   return INR_OK;
@@ -1252,49 +1294,21 @@ int inr_center_pairs_grad(const float* out, const float* gt, const int64_t* idx_
 static int train_step_impl(const inr_plan* plan, const inr_loss_desc* loss, const float* params, const float* packed,
                            const float* x, const float* enc_B, const float* gt, const uint8_t* mask, int64_t B,
                            const inr_workspace* ws, float* grads, float* loss_out, void* stream, const AdamFuse* af) {
-  if (plan == nullptr || loss == nullptr || params == nullptr || packed == nullptr || x == nullptr ||
-      gt == nullptr || ws == nullptr || loss_out == nullptr)
-    return fail(INR_ERR_INVALID, "inr_train_step: null argument");
-  if (plan->nd.mfn_n > 0)
-    return fail(INR_ERR_INVALID, "inr_train_step: multiplicative-filter plans use inr_train_step_multi");
-  if (plan->nd.input == IN_GAUSS && enc_B == nullptr) return fail(INR_ERR_INVALID, "inr_train_step: enc_B is null");
-  if (loss->kind < INR_LOSS_L2_HALF || loss->kind > INR_LOSS_CENTER)
-    return fail(INR_ERR_INVALID, "inr_train_step: loss kind %d", loss->kind);
-  if (loss->kind >= INR_LOSS_LOGSPACE && plan->nd.out_f != 2)
-    return fail(INR_ERR_INVALID, "inr_train_step: complex-row losses need out_features == 2");
-  if (B <= 0) return fail(INR_ERR_INVALID, "inr_train_step: B = %lld", (long long)B);
-  int64_t nt, nb, slots, n_slabs;
-  inr_plan_launch_dims(plan, B, &nt, &nb);
-  inr_plan_workspace(plan, B, &slots, &n_slabs);
-  {
-    const int rc = check_ws(plan, ws, slots, n_slabs, "inr_train_step");
-    if (rc != INR_OK) return rc;
-  }
-  inr::MlpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.params = params;
-  a.packed = packed;
-  a.x = x;
-  a.encB = enc_B;
+  const char* who = "inr_train_step";
+  const bool null_arg = plan == nullptr || loss == nullptr || params == nullptr || packed == nullptr || x == nullptr ||
+                        gt == nullptr || ws == nullptr || loss_out == nullptr;
+  if (int rc = check_net_call(who, null_arg, plan, false, enc_B, false, nullptr)) return rc;
+  if (int rc = check_step_loss(who, plan, loss)) return rc;
+  CallLayout c;
+  if (int rc = begin_call(plan, B, who, &c)) return rc;
+  if (int rc = check_ws(plan, ws, c.save_slots, c.n_slabs, who)) return rc;
+  inr::MlpArgs a = net_args(params, packed, x, enc_B, B, c, ws);
   a.gt = gt;
   a.mask = mask;
-  a.save = ws->save;
-  a.slabs = ws->slabs;
-  a.B = B;
-  a.n_tiles = (int)nt;
-  a.dw_gemm = w2_plan(plan) ? 2 : (dw_gemm_plan(plan) ? 1 : 0);
-  a.save_by_block = a.dw_gemm ? 0 : 1;
-  if (a.dw_gemm == 2) {
-    a.dz_state = dz_state_alloc(plan);
-    if (a.dz_state == nullptr) return fail(INR_ERR_HIP, "inr_train_step: no gradient-scale state on this device");
-  }
-#ifdef INR_STAMPS
-  a.dbg = g_stamp_buf;
-  a.dbg_cap = g_stamp_cap;
-#endif
+  if (int rc = step_args(plan, ws, who, &a)) return rc;
   LossDesc ld;
   to_loss_desc(loss, &ld);
-  return run_fused_step(plan, ld, a, nt, nb, grads, loss_out, params, packed, (hipStream_t)stream, "inr_train_step", af);
+  return run_fused_step(plan, ld, a, c, grads, loss_out, params, packed, (hipStream_t)stream, who, af);
 }
 
 int inr_train_step(const inr_plan* plan, const inr_loss_desc* loss, const float* params, const float* packed,
@@ -1323,120 +1337,67 @@ int inr_plan_heads(const inr_plan* plan, int32_t* n_heads) {
 int inr_forward_multi(const inr_plan* plan, const float* params, const float* packed, const float* coords,
                       const float* enc_B, const float* dist, int64_t B, float* out, const inr_workspace* ws,
                       int32_t by_block, void* stream) {
-  if (plan == nullptr || params == nullptr || packed == nullptr || coords == nullptr || out == nullptr ||
-      ws == nullptr)
-    return fail(INR_ERR_INVALID, "inr_forward_multi: null argument");
-  if (plan->nd.input == IN_GAUSS && enc_B == nullptr) return fail(INR_ERR_INVALID, "inr_forward_multi: enc_B is null");
-  if (plan->nd.bounded && dist == nullptr) return fail(INR_ERR_INVALID, "inr_forward_multi: bounded model needs dist");
-  if (plan->nd.mfn_n == 0) return fail(INR_ERR_INVALID, "inr_forward_multi: not a multiplicative-filter plan");
-  if (B <= 0) return fail(INR_ERR_INVALID, "inr_forward_multi: B = %lld", (long long)B);
-  int64_t nt, nb;
-  inr_plan_launch_dims(plan, B, &nt, &nb);
-  {
-    const int rc = check_ws(plan, ws, by_block ? nb : nt, 0, "inr_forward_multi");
-    if (rc != INR_OK) return rc;
-  }
-  inr::MlpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.params = params;
-  a.packed = packed;
-  a.x = coords;
-  a.encB = enc_B;
+  const char* who = "inr_forward_multi";
+  const bool null_arg = plan == nullptr || params == nullptr || packed == nullptr || coords == nullptr || out == nullptr ||
+                        ws == nullptr;
+  if (int rc = check_net_call(who, null_arg, plan, true, enc_B, true, dist)) return rc;
+  CallLayout c;
+  if (int rc = begin_call(plan, B, who, &c)) return rc;
+  if (int rc = check_ws(plan, ws, by_block ? c.nb : c.nt, 0, who)) return rc;
+  inr::MlpArgs a = net_args(params, packed, coords, enc_B, B, c, ws);
   a.out = out;
   a.dist = dist;
-  a.save = ws->save;
-  a.B = B;
-  a.n_tiles = (int)nt;
   a.save_by_block = by_block ? 1 : 0;
   LossDesc ld;
   memset(&ld, 0, sizeof(ld));
-  return launch(plan, ld, a, 0, (int)nb, (hipStream_t)stream);
+  return launch(plan, ld, a, 0, (int)c.nb, (hipStream_t)stream);
 }
 
 int inr_backward_multi(const inr_plan* plan, const float* params, const float* packed, const float* coords,
                        const float* enc_B, const float* dist, int64_t B, const float* dout,
                        const inr_workspace* ws, float* grads, void* stream) {
-  if (plan == nullptr || params == nullptr || packed == nullptr || coords == nullptr || dout == nullptr ||
-      ws == nullptr || grads == nullptr)
-    return fail(INR_ERR_INVALID, "inr_backward_multi: null argument");
-  if (plan->nd.input == IN_GAUSS && enc_B == nullptr) return fail(INR_ERR_INVALID, "inr_backward_multi: enc_B is null");
-  if (plan->nd.bounded && dist == nullptr) return fail(INR_ERR_INVALID, "inr_backward_multi: bounded model needs dist");
-  if (plan->nd.mfn_n == 0) return fail(INR_ERR_INVALID, "inr_backward_multi: not a multiplicative-filter plan");
-  if (B <= 0) return fail(INR_ERR_INVALID, "inr_backward_multi: B = %lld", (long long)B);
-  int64_t nt, nb, slots, n_slabs;
-  inr_plan_launch_dims(plan, B, &nt, &nb);
-  inr_plan_workspace(plan, B, &slots, &n_slabs);
-  {
-    const int rc = check_ws(plan, ws, nt, n_slabs, "inr_backward_multi");
-    if (rc != INR_OK) return rc;
-  }
-  inr::MlpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.params = params;
-  a.packed = packed;
-  a.x = coords;
-  a.encB = enc_B;
+  const char* who = "inr_backward_multi";
+  const bool null_arg = plan == nullptr || params == nullptr || packed == nullptr || coords == nullptr || dout == nullptr ||
+                        ws == nullptr || grads == nullptr;
+  if (int rc = check_net_call(who, null_arg, plan, true, enc_B, true, dist)) return rc;
+  CallLayout c;
+  if (int rc = begin_call(plan, B, who, &c)) return rc;
+  if (int rc = check_ws(plan, ws, c.nt, c.n_slabs, who)) return rc;
+  inr::MlpArgs a = net_args(params, packed, coords, enc_B, B, c, ws);
   a.dout = dout;
   a.dist = dist;
-  a.save = ws->save;
   a.slabs = ws->slabs;
-  a.B = B;
-  a.n_tiles = (int)nt;
   a.save_by_block = 0;
+  a.dw_gemm = plan->dw_route;
   LossDesc ld;
   memset(&ld, 0, sizeof(ld));
-  a.dw_gemm = dw_gemm_plan(plan) ? 1 : 0;
-  int rc = launch(plan, ld, a, 1, (int)nb, (hipStream_t)stream);
+  int rc = launch(plan, ld, a, 1, (int)c.nb, (hipStream_t)stream);
   if (rc != INR_OK) return rc;
-  return finish_gradients(plan, a, nt, nb, grads, nullptr, params, packed, (hipStream_t)stream, "inr_backward_multi");
+  return finish_gradients(plan, a, c, c.nb, grads, nullptr, params, packed, (hipStream_t)stream, who);
 }
 
 int inr_train_step_multi(const inr_plan* plan, const inr_loss_desc* loss, const float* params, const float* packed,
                          const float* coords, const float* enc_B, const float* gt, const float* dist,
                          const uint8_t* mask, int64_t B, const inr_workspace* ws, float* grads, float* loss_out,
                          void* stream) {
-  if (plan == nullptr || loss == nullptr || params == nullptr || packed == nullptr || coords == nullptr ||
-      gt == nullptr || ws == nullptr || loss_out == nullptr)
-    return fail(INR_ERR_INVALID, "inr_train_step_multi: null argument");
-  if (plan->nd.input == IN_GAUSS && enc_B == nullptr) return fail(INR_ERR_INVALID, "inr_train_step_multi: enc_B is null");
-  if (plan->nd.mfn_n == 0) return fail(INR_ERR_INVALID, "inr_train_step_multi: not a multiplicative-filter plan");
-  if (loss->kind < INR_LOSS_L2_HALF || loss->kind > INR_LOSS_CENTER)
-    return fail(INR_ERR_INVALID, "inr_train_step_multi: loss kind %d", loss->kind);
-  if (loss->kind >= INR_LOSS_LOGSPACE && plan->nd.out_f != 2)
-    return fail(INR_ERR_INVALID, "inr_train_step_multi: complex-row losses need out_features == 2");
+  const char* who = "inr_train_step_multi";
+  const bool null_arg = plan == nullptr || loss == nullptr || params == nullptr || packed == nullptr || coords == nullptr ||
+                        gt == nullptr || ws == nullptr || loss_out == nullptr;
+  if (int rc = check_net_call(who, null_arg, plan, true, enc_B, false, nullptr)) return rc;
+  if (int rc = check_step_loss(who, plan, loss)) return rc;
   if ((loss->cons_w != 0.f || plan->nd.bounded) && dist == nullptr)
     return fail(INR_ERR_INVALID, "inr_train_step_multi: the consistency term / bounded linears need dist");
-  if (B <= 0) return fail(INR_ERR_INVALID, "inr_train_step_multi: B = %lld", (long long)B);
-  int64_t nt, nb, slots, n_slabs;
-  inr_plan_launch_dims(plan, B, &nt, &nb);
-  inr_plan_workspace(plan, B, &slots, &n_slabs);
-  {
-    const int rc = check_ws(plan, ws, slots, n_slabs, "inr_train_step_multi");
-    if (rc != INR_OK) return rc;
-  }
-  inr::MlpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.params = params;
-  a.packed = packed;
-  a.x = coords;
-  a.encB = enc_B;
+  CallLayout c;
+  if (int rc = begin_call(plan, B, who, &c)) return rc;
+  if (int rc = check_ws(plan, ws, c.save_slots, c.n_slabs, who)) return rc;
+  inr::MlpArgs a = net_args(params, packed, coords, enc_B, B, c, ws);
   a.gt = gt;
   a.dist = dist;
   a.mask = mask;
-  a.save = ws->save;
-  a.slabs = ws->slabs;
-  a.B = B;
-  a.n_tiles = (int)nt;
-  a.dw_gemm = dw_gemm_plan(plan) ? 1 : 0;
-  a.save_by_block = a.dw_gemm ? 0 : 1;
-#ifdef INR_STAMPS
-  a.dbg = g_stamp_buf;
-  a.dbg_cap = g_stamp_cap;
-#endif
+  if (int rc = step_args(plan, ws, who, &a)) return rc;
   LossDesc ld;
   to_loss_desc(loss, &ld);
-  return run_fused_step(plan, ld, a, nt, nb, grads, loss_out, params, packed, (hipStream_t)stream,
-                        "inr_train_step_multi");
+  return run_fused_step(plan, ld, a, c, grads, loss_out, params, packed, (hipStream_t)stream, who);
 }
 
 static bool has_complex_tensors(const NetDesc& nd) {
@@ -1459,6 +1420,24 @@ static void adam_bias_terms(double lr, double beta1, double beta2, int32_t step,
   const double bc2 = 1.0 - std::pow(beta2, (double)step);
   *step_size = (float)(lr / bc1);
   *bc2_sqrt = (float)std::sqrt(bc2);
+}
+
+// AdamArgs of an update from the doubles of its ABI call; (step_size, bc2_sqrt) are the caller's: adam_bias_terms, or a
+// device-resident schedule
+static inr::AdamArgs adam_args(double beta1, double beta2, double eps, double weight_decay, double l1, double l2) {
+  inr::AdamArgs aa;
+  memset(&aa, 0, sizeof(aa));
+  aa.do_update = 1;
+  aa.step_size = 0.f;
+  aa.bc2_sqrt = 1.f;
+  aa.omb1 = (float)(1.0 - beta1);
+  aa.beta2 = (float)beta2;
+  aa.omb2 = (float)(1.0 - beta2);
+  aa.eps = (float)eps;
+  aa.weight_decay = (float)weight_decay;
+  aa.l1 = (float)l1;
+  aa.l2 = (float)l2;
+  return aa;
 }
 
 static int image_metrics_check(int64_t C, int64_t H, int64_t W, const char* who) {
@@ -1737,20 +1716,10 @@ int inr_adam_step_dev(const inr_plan* plan, float* params, const float* grads, f
     return fail(INR_ERR_INVALID, "inr_adam_step_dev: null argument");
   if (n_sched < 1) return fail(INR_ERR_INVALID, "inr_adam_step_dev: empty schedule");
   if (int rc = check_real_penalty(plan, l1, l2, "inr_adam_step_dev")) return rc;
-  inr::AdamArgs aa;
-  aa.do_update = 1;
-  aa.step_size = 0.f;
-  aa.bc2_sqrt = 1.f;
+  inr::AdamArgs aa = adam_args(beta1, beta2, eps, weight_decay, l1, l2);
   aa.sched = sched;
   aa.step_dev = step_dev;
   aa.n_sched = n_sched;
-  aa.omb1 = (float)(1.0 - beta1);
-  aa.beta2 = (float)beta2;
-  aa.omb2 = (float)(1.0 - beta2);
-  aa.eps = (float)eps;
-  aa.weight_decay = (float)weight_decay;
-  aa.l1 = (float)l1;
-  aa.l2 = (float)l2;
   hipError_t e = inr::launch_adam_pack(plan->nd, params, grads, exp_avg, exp_avg_sq, packed, aa, (hipStream_t)stream);
   if (e == hipSuccess) e = inr::launch_step_advance(step_dev, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "inr_adam_step_dev");
@@ -1765,19 +1734,8 @@ int inr_adam_step(const inr_plan* plan, float* params, const float* grads, float
     return fail(INR_ERR_INVALID, "inr_adam_step: null argument");
   if (step < 1) return fail(INR_ERR_INVALID, "inr_adam_step: step %d (counts from 1)", step);
   if (int rc = check_real_penalty(plan, l1, l2, "inr_adam_step")) return rc;
-  inr::AdamArgs aa;
-  aa.do_update = 1;
-  aa.sched = nullptr;
-  aa.step_dev = nullptr;
-  aa.n_sched = 0;
+  inr::AdamArgs aa = adam_args(beta1, beta2, eps, weight_decay, l1, l2);
   adam_bias_terms(lr, beta1, beta2, step, &aa.step_size, &aa.bc2_sqrt);
-  aa.omb1 = (float)(1.0 - beta1);
-  aa.beta2 = (float)beta2;
-  aa.omb2 = (float)(1.0 - beta2);
-  aa.eps = (float)eps;
-  aa.weight_decay = (float)weight_decay;
-  aa.l1 = (float)l1;
-  aa.l2 = (float)l2;
   hipError_t e = inr::launch_adam_pack(plan->nd, params, grads, exp_avg, exp_avg_sq, packed, aa, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "inr_adam_step");
   return INR_OK;
@@ -1806,19 +1764,8 @@ int inr_adam_step_shard(const inr_plan* plan, float* params, const float* grads_
   if (lo < 0 || hi < lo || hi > plan->nd.P)
     return fail(INR_ERR_INVALID, "inr_adam_step_shard: entries [%lld, %lld) of %d", (long long)lo, (long long)hi,
                 plan->nd.P);
-  inr::AdamArgs aa;
-  aa.do_update = 1;
-  aa.sched = nullptr;
-  aa.step_dev = nullptr;
-  aa.n_sched = 0;
+  inr::AdamArgs aa = adam_args(beta1, beta2, eps, weight_decay, l1, l2);
   adam_bias_terms(lr, beta1, beta2, step, &aa.step_size, &aa.bc2_sqrt);
-  aa.omb1 = (float)(1.0 - beta1);
-  aa.beta2 = (float)beta2;
-  aa.omb2 = (float)(1.0 - beta2);
-  aa.eps = (float)eps;
-  aa.weight_decay = (float)weight_decay;
-  aa.l1 = (float)l1;
-  aa.l2 = (float)l2;
   hipError_t e = inr::launch_adam_shard(plan->nd, params, grads_shard, exp_avg, exp_avg_sq, (int)lo, (int)hi, aa,
                                         (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "inr_adam_step_shard");
@@ -1837,16 +1784,8 @@ int inr_train_adam_step(const inr_plan* plan, const inr_loss_desc* loss, float* 
     if (int rc = check_real_penalty(plan, l1, l2, "inr_train_adam_step")) return rc;
   AdamFuse af;
   af.params = params, af.m1 = exp_avg, af.m2 = exp_avg_sq, af.packed = packed;
-  memset(&af.aa, 0, sizeof(af.aa));
-  af.aa.do_update = 1;
+  af.aa = adam_args(beta1, beta2, eps, weight_decay, l1, l2);
   adam_bias_terms(lr, beta1, beta2, step, &af.aa.step_size, &af.aa.bc2_sqrt);
-  af.aa.omb1 = (float)(1.0 - beta1);
-  af.aa.beta2 = (float)beta2;
-  af.aa.omb2 = (float)(1.0 - beta2);
-  af.aa.eps = (float)eps;
-  af.aa.weight_decay = (float)weight_decay;
-  af.aa.l1 = (float)l1;
-  af.aa.l2 = (float)l2;
   return train_step_impl(plan, loss, params, packed, x, enc_B, gt, mask, B, ws, grads, loss_out, stream, &af);
 }
 

@@ -797,12 +797,38 @@ def hp_search_vectors():
         json.dump(out, f, indent=1, sort_keys=False)
 
 
+def host_layout():
+    """tests/golden/host_layout.json (tests/layout_table.py, tests/test_layout_host.py): what the BUILT LIBRARY answers, on a
+    CPU, for plan x batch size x environment switches -- a record of one commit's host layer that every later one is
+    replayed against.  Not a default part: it reads no reference code, and it is regenerated only from a commit whose
+    layouts are meant to be the new truth (HEAD, with csrc/ and include/ as committed, and the library built from them)."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(OUT))
+    pkg = os.path.join(root, "mri-implicit-neural-representations_amd")
+    for p in (root, pkg, os.path.join(root, "tests")):
+        if p not in sys.path:
+            sys.path.append(p)
+    from inr_mi355x import _lib as L
+    import layout_table as T
+    dirty = subprocess.run(["git", "-C", root, "status", "--porcelain", "--", os.path.join(pkg, "csrc"), "include"],
+                           capture_output=True, text=True, check=True).stdout.strip()
+    if dirty:
+        raise SystemExit("host_layout: csrc/ or include/ differ from HEAD -- the table must come from a committed host layer")
+    head = subprocess.run(["git", "-C", root, "rev-parse", "HEAD"], capture_output=True, text=True, check=True).stdout.strip()
+    out = {"producer_commit": head, "B": T.B_VALUES, "switches": [list(s) for s in T.SWITCHES],
+           "desc_fields": T.DESC_FIELDS, "sizes_fields": T.SIZES_FIELDS, "info_fields": T.INFO_FIELDS,
+           **T.pack([T.plan_record(L, kw, oc) for kw, oc in T.plans(L)])}
+    T.dump(out, os.path.join(OUT, "host_layout.json"))
+    print("host_layout:", len(out["plans"]), "plans,", len(out["plans"]) * len(T.B_VALUES) * len(T.SWITCHES), "records")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     parts = dict(ingest=ingest_vectors, clustering=clustering_vectors, undersampling=undersampling_vectors, init=init_hashes,
                  models=model_vectors, losses=loss_vectors, center=center_vectors, trajectory=trajectory,
                  multiscale=multiscale_trajectory, extra=extra_trajectories, hp_search=hp_search_vectors)
-    for name in (sys.argv[1:] or list(parts)):  # python tools/make_golden.py [part ...]; default: everything
-        parts[name]()
+    on_request = dict(host_layout=host_layout)
+    for name in (sys.argv[1:] or list(parts)):  # python tools/make_golden.py [part ...]; default: every reference-made part
+        {**parts, **on_request}[name]()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("golden fixtures written to", OUT, f"({tot / 1e6:.2f} MB)")
