@@ -19,7 +19,7 @@
  *   - all work is ordered on the hipStream_t passed as `stream` (void*); no implicit sync.  One exception to
  *     "enqueued on": a fused step whose tiles leave the last round of the persistent grid partly empty runs part of
  *     its weight-gradient GEMM on a low-priority side stream the plan creates on first use, forked from and joined
- *     back into `stream` with events inside the call (csrc/inr_api.hip step_schedule; INR_OVERLAP=0 disables it) --
+ *     back into `stream` with events inside the call (csrc/inr_layout.hip step_schedule; INR_OVERLAP=0 disables it) --
  *     to the caller the call still behaves as work on `stream`, including under stream capture;
  *   - a plan's description is immutable after creation (that side stream, and a bf16 plan's scale state, are its only state) and it may be shared
  *     between threads and streams as long as each in-flight call has its own workspace buffers.

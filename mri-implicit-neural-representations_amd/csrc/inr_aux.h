@@ -65,36 +65,54 @@ hipError_t launch_loss_tv_grad(const LossDesc& ld, const float* out, const float
 hipError_t launch_tv_grad(const float* out, long long R, long long R_own, long long W, float cw, float ch,
                           float* loss_out, float* dout, hipStream_t st);
 
-// per-NB dispatchers (one translation unit each): mode 0 fwd, 1 bwd, 2 fused
-hipError_t launch_mlp_nb1(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_mlp_nb2(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_mlp_nb4(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_siren_bf16(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_siren_bf16_fwd(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
-hipError_t launch_siren_bf16_bwd(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
-hipError_t launch_siren_bf16_fused(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
-hipError_t launch_mlp_nb16(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
+// ---- the fused network kernels: one translation unit per (family, hidden block count NB) / per row-split width ----
+// mode 0 fwd, 1 bwd, 2 fused
+using NetLaunch = hipError_t(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
+using StepLaunch = hipError_t(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
+NetLaunch launch_mlp_nb1, launch_mlp_nb2, launch_mlp_nb4, launch_mlp_nb8, launch_mlp_nb16, launch_siren_bf16;
+NetLaunch launch_wire_nb2, launch_wire_nb4, launch_wire_nb8, launch_wire_nb12;
+NetLaunch launch_wire2d_nb2, launch_wire2d_nb4, launch_wire2d_nb8, launch_wire2d_nb16;
+NetLaunch launch_mfn_nb1, launch_mfn_nb4, launch_mfn_nb8, launch_mfn_nb16;
+StepLaunch launch_siren_bf16_fwd, launch_siren_bf16_bwd, launch_siren_bf16_fused;
 // row-split fused step, tiles of N column blocks of 16 coordinates (inr_mlp_rs_n*.hip)
-hipError_t launch_mlp_rs_n1(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
-hipError_t launch_mlp_rs_n2(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
-hipError_t launch_mlp_rs_n3(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
-hipError_t launch_mlp_rs_n4(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
-hipError_t launch_mlp_rs_n5(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
-hipError_t launch_mlp_rs_n6(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
-hipError_t launch_mlp_rs_n7(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st);
-hipError_t launch_mlp_nb8(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_wire_nb2(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_wire_nb4(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_wire_nb8(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_wire_nb12(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_wire2d_nb2(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_wire2d_nb4(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_wire2d_nb8(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_wire2d_nb16(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_mfn_nb1(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_mfn_nb4(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_mfn_nb8(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
-hipError_t launch_mfn_nb16(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int mode, int grid, hipStream_t st);
+StepLaunch launch_mlp_rs_n1, launch_mlp_rs_n2, launch_mlp_rs_n3, launch_mlp_rs_n4, launch_mlp_rs_n5, launch_mlp_rs_n6,
+    launch_mlp_rs_n7;
+
+// The kernel of a plan: its family's build for nd.NB -- the family's LAST row (its largest build) for any other NB.
+// bf16 plans: weight panels in LDS, dW by inr_dw_gemm_bf16.hip.
+enum NetFamily { FAM_MFN, FAM_WIRE2D, FAM_WIRE, FAM_BF16, FAM_MLP };
+inline NetLaunch* net_kernel(const NetDesc& nd) {
+  static constexpr struct {
+    NetFamily fam;
+    int NB;
+    NetLaunch* fn;
+  } built[] = {
+      {FAM_MFN, 1, launch_mfn_nb1}, {FAM_MFN, 4, launch_mfn_nb4}, {FAM_MFN, 8, launch_mfn_nb8}, {FAM_MFN, 16, launch_mfn_nb16},
+      {FAM_WIRE2D, 2, launch_wire2d_nb2}, {FAM_WIRE2D, 4, launch_wire2d_nb4}, {FAM_WIRE2D, 8, launch_wire2d_nb8},
+      {FAM_WIRE2D, 16, launch_wire2d_nb16},
+      {FAM_WIRE, 2, launch_wire_nb2}, {FAM_WIRE, 4, launch_wire_nb4}, {FAM_WIRE, 8, launch_wire_nb8}, {FAM_WIRE, 12, launch_wire_nb12},
+      {FAM_BF16, 8, launch_siren_bf16},
+      {FAM_MLP, 1, launch_mlp_nb1}, {FAM_MLP, 2, launch_mlp_nb2}, {FAM_MLP, 4, launch_mlp_nb4}, {FAM_MLP, 8, launch_mlp_nb8},
+      {FAM_MLP, 16, launch_mlp_nb16},
+  };
+  const NetFamily fam = nd.mfn_n > 0 ? FAM_MFN
+                        : nd.hact == ACT_GABOR2D ? FAM_WIRE2D
+                        : nd.hact == ACT_GABOR ? FAM_WIRE
+                        : nd.bf16 ? FAM_BF16 : FAM_MLP;
+  NetLaunch* fn = nullptr;
+  for (const auto& k : built)
+    if (k.fam == fam) {
+      fn = k.fn;
+      if (k.NB == nd.NB) break;
+    }
+  return fn;
+}
+// ... and the row-split kernel for tiles of `ncb` column blocks (anything outside 1..6: the widest build)
+inline StepLaunch* rs_kernel(int ncb) {
+  static constexpr StepLaunch* built[] = {launch_mlp_rs_n1, launch_mlp_rs_n2, launch_mlp_rs_n3, launch_mlp_rs_n4,
+                                          launch_mlp_rs_n5, launch_mlp_rs_n6, launch_mlp_rs_n7};
+  return built[ncb >= 1 && ncb <= 6 ? ncb - 1 : 6];
+}
 
 // image metrics of the validation epoch (inr_eval.hip): RSS over coils, then PSNR / SSIM against `ref` when it is given
 long long image_metrics_scratch_doubles(long long H, long long W);
@@ -112,7 +130,7 @@ long long coil_stats_scratch_doubles(long long C, long long H, long long W);
 hipError_t launch_coil_stats(const float* coils, int C, int H, int W, double* stats, double* scratch, hipStream_t st);
 
 // shuffled epochs (inr_aux.hip): round keys of (seed, epoch) and the half width of the Feistel domain,
-// both made on the host (inr_api.hip shuffle_keys)
+// both made on the host (inr_api_aux.hip shuffle_keys)
 #define SHUFFLE_ROUNDS 6
 struct ShuffleKeys {
   unsigned k[SHUFFLE_ROUNDS];

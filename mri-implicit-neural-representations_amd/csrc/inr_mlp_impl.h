@@ -1215,7 +1215,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
 #endif
   const LayerDesc& LL = nd.L[D - 1];
   // hidden rows == NB*32 except for WIRE's 181 complex features (362 rows padded to 384); the plan
-  // only pairs NB == 12 with that width (inr_api.hip)
+  // only pairs NB == 12 with that width (inr_plan.hip)
   constexpr bool HFULL = true;  // hidden-layer slabs span all NB*32 rows (inr_plan_create)
 
   for (int tile = a.tile0 + blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {

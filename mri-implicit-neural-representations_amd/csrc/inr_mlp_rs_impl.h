@@ -59,7 +59,7 @@ template <int NCB>
 __device__ __forceinline__ int rs_tl(int c, int jj) {
   return ((NCB & 1) && c == NCB - 1) ? 16 * (NCB - 1) + jj : 32 * (c >> 1) + 2 * jj + (c & 1);
 }
-// does column block c exist in a tile of n blocks?  (n == NCB, or n even: inr_api.hip rs_schedule)
+// does column block c exist in a tile of n blocks?  (n == NCB, or n even: inr_layout.hip rs_schedule)
 template <int NCB>
 __device__ __forceinline__ bool rs_active(int c, int n) {
   return ((NCB & 1) && c == NCB - 1) ? n == NCB : (c | 1) < n;
@@ -95,7 +95,7 @@ __device__ __forceinline__ float rs_load1(__amdgpu_buffer_rsrc_t rs, int voff, i
 // v_accvgpr_read into a VGPR right before it is stored or multiplied; loads land in VGPRs and move over later.
 // (NCB = 8 would be all 256 AGPRs: the compiler's own AGPR copies then push act' into scratch.  Keeping four of the 16 rows
 // in VGPRs instead -- in_agpr = false -- was tried and lost them to scratch in the backward GEMM all the same: tiles stop
-// at 7 column blocks, inr_api.hip kRsMaxNcb.)
+// at 7 column blocks, inr_layout.hip kRsMaxNcb.)
 __device__ __forceinline__ float rs_dk_put(bool in_agpr, float v) {  // (in_agpr folds once the row loops are unrolled)
   if (!in_agpr) return v;
   float a;

@@ -153,7 +153,7 @@ def last_error() -> str:
 
 
 # INR_ERR_UNSUPPORTED: a valid request the engine has no kernel for.  Invariant: the library returns it only BEFORE any
-# launch (today from inr_plan_create alone, csrc/inr_api.hip), so check() may raise it as NotImplementedError and the
+# launch (today from inr_plan_create alone, csrc/inr_plan.hip), so check() may raise it as NotImplementedError and the
 # hyperparameter search may record such a trial as a harmless refusal.  An entry that can fail after it has launched
 # something must return another code.
 ERR_UNSUPPORTED = -2

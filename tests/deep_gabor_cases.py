@@ -14,7 +14,7 @@ WIRE's 181 complex features, the complex re-pack after Adam.
 
 A case = (family, depth, last activation, omega_0, scale, loss, mask, NaN in the unsampled rows, B).  Width 256, three
 coordinates in, two outputs.  ``network_depth`` counts the hidden complex layers, every one of which is an item of the
-batch GEMM (inr_api.hip::dw_gemm_items, l = 1 .. D - 2 with D = depth + 2 Linear layers): depths 2, 3, 4 give WIRE 2, 3, 4
+batch GEMM (inr_plan.hip::dw_gemm_items, l = 1 .. D - 2 with D = depth + 2 Linear layers): depths 2, 3, 4 give WIRE 2, 3, 4
 items and WIRE2D, whose orth Linear is an item too, 4, 6, 8.  ``B`` is symbolic -- tile size, persistent grid and the
 GEMM's chunking come from the plan:
   base   2 TL + 37

@@ -9,7 +9,7 @@ the previous call in its slab.  Required: g_on == g_off == the second g_on, bitw
 
 Cases: the smallest shapes that reach each form of the grid (G workgroups; the map treats G < 8, G % 8 != 0, a short
 last chunk, another number of workgroups per chunk and more than one round of the chip's 256 CUs differently).  The
-grid follows from dw_gemm_chunk / dw_gemm_units (csrc/inr_api.hip, csrc/inr_dw_gemm.hip), restated in _grid below."""
+grid follows from dw_gemm_chunk / dw_gemm_units (csrc/inr_layout.hip, csrc/inr_dw_gemm.hip), restated in _grid below."""
 import os
 
 import pytest

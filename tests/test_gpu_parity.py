@@ -331,7 +331,7 @@ def test_device_resident_adam_and_graph_steps(dev):
 def test_split_step_overlap_matches_plain_schedule(dev, model, B):
     """Batches whose tiles do not fill the last round of the persistent grid (SIREN 5x256: 313 tiles of 128 rows =
     256 + 57; WIRE: 391 tiles of 64 = 256 + 135; SIREN 8x512: 313 tiles of 64) run as a split step: the weight-gradient
-    GEMM of the finished tiles on a side stream beside the fused kernel's partial round (inr_api.hip, step_schedule).
+    GEMM of the finished tiles on a side stream beside the fused kernel's partial round (inr_layout.hip, step_schedule).
     Same forward, same per-tile sums, another chunking of the GEMM: loss and last-layer gradients bit-identical to
     the plain schedule (INR_OVERLAP=0), the GEMM's layers to summation order; run-to-run deterministic; and the
     workspace the plan asks for covers both schedules."""

@@ -157,7 +157,7 @@ def test_plan_validation_and_sizes():
 def test_bf16_plan_sizes_and_chunk_classes(monkeypatch):
     """A bf16 plan is created and sized without a GPU.  Workspace of a step = one stash slot per 128-row tile + the fused
     kernel's slabs (one per workgroup, two tiles each above 256 tiles) + the weight-gradient GEMM's chunk slabs: the larger
-    of its two chunk classes (csrc/inr_api.hip: dw_gemm_bf16_setup -- first-layer units 1.5 x the chunks of the others,
+    of its two chunk classes (csrc/inr_layout.hip: dw_gemm_bf16_setup -- first-layer units 1.5 x the chunks of the others,
     about 256 workgroups in all)."""
     from inr_mi355x import _lib as L
     lib = L.load()
