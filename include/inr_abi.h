@@ -10,7 +10,8 @@
  *   - all tensor arguments are DEVICE pointers to contiguous row-major fp32 buffers owned by the
  *     caller -- except inr_image_metrics' `metrics_out` and `scratch`, which are fp64 (double) device buffers, and
  *     inr_shuffle_epoch's integer buffers (uint8 masks, int32 counts, int64 order), inr_gray8's uint8 `lut` / `out` and
- *     inr_coil_stats' and inr_band_stats' fp64 `stats` / `scratch` (inr_band_stats' bounds are host arrays); the
+ *     inr_coil_stats' and inr_band_stats' fp64 `stats` / `scratch` (inr_band_stats' bounds are host arrays) and
+ *     inr_coil_gram's fp64 `gram` / `scratch`; the
  *     library retains no pointer across calls and allocates no device memory -- with ONE exception:
  *     an INR_PRECISION_BF16 plan owns 64 bytes of device memory (16 words), its gradient-scale state (inr_plan_grad_scale_state),
  *     allocated with hipMalloc and initialised with a synchronous hipMemcpy by the first call that needs it on a device
@@ -48,7 +49,8 @@ extern "C" {
  *    the validation epoch); inr_shuffle_epoch (the keyed row permutation of a shuffled epoch); inr_kspace_display, inr_gray8,
  *    inr_coil_stats and their scratch queries (the pictures and the per-coil table of the validation epoch); inr_grid_rows
  *    (rows of a coordinate grid, made on the device: reconstruction from a checkpoint on any grid); inr_band_stats and its
- *    scratch query (per-band counts, energies, errors and extrema of a field against radius).
+ *    scratch query (per-band counts, energies, errors and extrema of a field against radius); inr_coil_gram, its scratch
+ *    query and inr_coil_apply (software coil compression: the coil Gram matrix in one pass, the product with a small matrix).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -499,6 +501,29 @@ int inr_band_stats_scratch(int64_t n, int32_t n_bands, int64_t* scratch_doubles)
 int inr_band_stats(const float* dist, const float* gt, const float* pred, const uint8_t* mask, int32_t mask_select,
                    int64_t n, const float* band_lo, const float* band_hi, int32_t n_bands, double* stats,
                    double* scratch, void* stream);
+
+/* (v7 addition) Software coil compression (no reference counterpart).  A scan is coil-major:
+ * data [C][N][2], complex fp32 (re, im) pairs, N = H*W pixels per coil.
+ * inr_coil_gram: gram [C][C][2] (fp64, device, both triangles), G[i][j] = sum_p x_i[p] conj(x_j[p]).  Every product is
+ * formed in fp64 from the fp32 inputs (exact) and every sum is fp64; the order of the sums is fixed (workgroup partials in
+ * `scratch`, then one block per pair; no atomics), so two calls on the same input give the same bits.  G[j][i] is
+ * written as the conjugate of G[i][j] and the diagonal's imaginary part as +0.  `scratch` = at least the fp64 words
+ * inr_coil_gram_scratch gives for (C, N) -- a function of its arguments alone; `scratch_doubles` is what the caller's
+ * buffer holds.  A workgroup takes INR_COIL_TILE_PIXELS pixels of all C coils per step, with 16-byte loads when `data`
+ * is 16-byte aligned and N is even (else 8-byte loads).  Two launches on `stream`; nothing is allocated, nothing is read
+ * back, capturable in a graph.  inr_mi355x/coils.py::coil_gram_numpy restates it in numpy.
+ * inr_coil_apply: out [M][N][2] = A [M][K][2] (device, row-major complex fp32) times in [K][N][2]:
+ * y_m[p] = sum_k A[m][k] x_k[p] in fp32, k = 0..K-1 in order (re += ar xr - ai xi, im += ar xi + ai xr).  Compression
+ * passes the K x C matrix, expansion back to physical coils its conjugate transpose.  One launch; 16-byte loads and
+ * stores when in / out are 16-byte aligned and N is even.  coils.py::coil_apply_numpy restates it.
+ * INR_ERR_INVALID before any launch: a null pointer; C, M or K outside 1..INR_COIL_MAX; N < 1 or N >= 2^31; data / in /
+ * out not 8-byte aligned; scratch_doubles short of the query; out overlapping in or A. */
+#define INR_COIL_MAX 32
+#define INR_COIL_TILE_PIXELS 128
+int inr_coil_gram_scratch(int32_t C, int64_t N, int64_t* scratch_doubles);
+int inr_coil_gram(const float* data, int32_t C, int64_t N, double* gram, double* scratch, int64_t scratch_doubles,
+                  void* stream);
+int inr_coil_apply(const float* in, const float* A, int32_t M, int32_t K, int64_t N, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network: encoders, losses, TV, Adam,
-// image metrics, display, shuffle, grid rows, band statistics.  Each checks its arguments, fills an argument struct,
+// image metrics, display, shuffle, grid rows, band statistics, coil compression.  Each checks its arguments, fills an argument struct,
 // launches and maps the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -419,6 +419,61 @@ int inr_band_stats(const float* dist, const float* gt, const float* pred, const 
   }
   hipError_t e = inr::launch_band_stats(a, dist, gt, pred, mask, n, stats, scratch, (hipStream_t)stream);
   return hip_done(e, "inr_band_stats");
+}
+
+// ---- coil compression (inr_coils.hip) ----
+static_assert(INR_COIL_MAX == inr::COIL_MAX && INR_COIL_TILE_PIXELS == inr::COIL_TILE_PIXELS,
+              "inr_abi.h and inr_aux.h disagree");
+
+static int coil_count_check(int32_t v, const char* name, const char* who) {
+  if (v < 1 || v > INR_COIL_MAX) return fail(INR_ERR_INVALID, "%s: %s = %d (1..%d)", who, name, (int)v, INR_COIL_MAX);
+  return INR_OK;
+}
+
+static int coil_pixels_check(int64_t N, const char* who) {
+  if (N < 1 || N >= (1LL << 31)) return fail(INR_ERR_INVALID, "%s: N = %lld (1 <= N < 2^31 pixels per call)", who, (long long)N);
+  return INR_OK;
+}
+
+static bool ranges_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
+}
+
+int inr_coil_gram_scratch(int32_t C, int64_t N, int64_t* scratch_doubles) {
+  if (scratch_doubles == nullptr) return fail(INR_ERR_INVALID, "inr_coil_gram_scratch: null argument");
+  if (int rc = coil_count_check(C, "C", "inr_coil_gram_scratch")) return rc;
+  if (int rc = coil_pixels_check(N, "inr_coil_gram_scratch")) return rc;
+  *scratch_doubles = inr::coil_gram_scratch_doubles(C, N);
+  return INR_OK;
+}
+
+int inr_coil_gram(const float* data, int32_t C, int64_t N, double* gram, double* scratch, int64_t scratch_doubles,
+                  void* stream) {
+  if (data == nullptr || gram == nullptr || scratch == nullptr) return fail(INR_ERR_INVALID, "inr_coil_gram: null argument");
+  if (int rc = coil_count_check(C, "C", "inr_coil_gram")) return rc;
+  if (int rc = coil_pixels_check(N, "inr_coil_gram")) return rc;
+  if (((uintptr_t)data & 7u) != 0) return fail(INR_ERR_INVALID, "inr_coil_gram: data is not 8-byte aligned");
+  const int64_t need = inr::coil_gram_scratch_doubles(C, N);
+  if (scratch_doubles < need)
+    return fail(INR_ERR_INVALID, "inr_coil_gram: scratch holds %lld doubles, C = %d, N = %lld need %lld",
+                (long long)scratch_doubles, (int)C, (long long)N, (long long)need);
+  hipError_t e = inr::launch_coil_gram(data, C, N, gram, scratch, (hipStream_t)stream);
+  return hip_done(e, "inr_coil_gram");
+}
+
+int inr_coil_apply(const float* in, const float* A, int32_t M, int32_t K, int64_t N, float* out, void* stream) {
+  if (in == nullptr || A == nullptr || out == nullptr) return fail(INR_ERR_INVALID, "inr_coil_apply: null argument");
+  if (int rc = coil_count_check(M, "M", "inr_coil_apply")) return rc;
+  if (int rc = coil_count_check(K, "K", "inr_coil_apply")) return rc;
+  if (int rc = coil_pixels_check(N, "inr_coil_apply")) return rc;
+  if ((((uintptr_t)in | (uintptr_t)out) & 7u) != 0) return fail(INR_ERR_INVALID, "inr_coil_apply: in / out is not 8-byte aligned");
+  const int64_t in_bytes = (int64_t)K * N * 8, out_bytes = (int64_t)M * N * 8, a_bytes = (int64_t)M * K * 8;
+  if (ranges_overlap(out, out_bytes, in, in_bytes))
+    return fail(INR_ERR_INVALID, "inr_coil_apply: out overlaps in (every output row reads every input row: no in-place form)");
+  if (ranges_overlap(out, out_bytes, A, a_bytes)) return fail(INR_ERR_INVALID, "inr_coil_apply: out overlaps A");
+  hipError_t e = inr::launch_coil_apply(in, A, M, K, N, out, (hipStream_t)stream);
+  return hip_done(e, "inr_coil_apply");
 }
 
 int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* host_out) {

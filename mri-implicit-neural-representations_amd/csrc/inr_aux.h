@@ -163,4 +163,11 @@ long long band_stats_scratch_doubles(long long n, int n_bands);
 hipError_t launch_band_stats(const BandArgs& a, const float* dist, const float* gt, const float* pred,
                              const uint8_t* mask, long long n, double* stats, double* scratch, hipStream_t st);
 
+// coil compression (inr_coils.hip): Gram matrix of a coil-major scan, product with a small matrix
+constexpr int COIL_MAX = 32;           // INR_COIL_MAX
+constexpr int COIL_TILE_PIXELS = 128;  // INR_COIL_TILE_PIXELS
+long long coil_gram_scratch_doubles(int C, long long N);
+hipError_t launch_coil_gram(const float* data, int C, long long N, double* gram, double* scratch, hipStream_t st);
+hipError_t launch_coil_apply(const float* in, const float* A, int M, int K, long long N, float* out, hipStream_t st);
+
 }  // namespace inr

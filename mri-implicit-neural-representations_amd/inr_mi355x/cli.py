@@ -59,12 +59,14 @@ def parse_cli(val_and_samples: bool = True, argv=None):
                          "<output_path>/checkpoints, and print the per-coil table after each validation line")
     from .bands import add_band_report_flag
     add_band_report_flag(ap, "with --val" if val_and_samples else "after the fit")
+    from .coils import add_virtual_coils_flag, apply_virtual_coils_flag
+    add_virtual_coils_flag(ap)
     opts = ap.parse_args(argv)
     if val_and_samples and opts.save_images and not opts.val:
         ap.error("--save-images needs --val (the pictures are those of the validation epoch)")
     if opts.band_report is not None and val_and_samples and not opts.val:
         ap.error("--band-report needs --val (the report is made from the validation epoch's prediction)")
-    return opts, apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts)
+    return opts, apply_virtual_coils_flag(apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts), opts)
 
 
 def expand_data_samples(config: dict, samples) -> list:
@@ -96,12 +98,34 @@ def cli_data(opts, config: dict, normalization: str, image_space: bool = False):
     """(image, coords, shape) of a fit: --synthetic C,H,W (``normalization``: the default where the config names none),
     or the scan named by config['data_root'/'data'/'set'/'sample'/'slice'] or 'custom_file_or_path' (train.py:271-287,
     train_kspace_multiscale.py:57-72)."""
+    return cli_fit_data(opts, config, normalization, image_space)[:3]
+
+
+def cli_fit_data(opts, config: dict, normalization: str, image_space: bool = False, matrix=None):
+    """cli_data plus the coil compression the data came through (None without config['virtual_coils']): (image, coords,
+    shape, CoilCompression or None).  With the switch on, --synthetic generates without normalisation, compresses on the
+    device (k-space in, k-space out; image space with ``image_space``), then applies datasets.normalize_kspace /
+    normalize_image -- compression always comes before normalisation.  ``matrix``: a stored CoilCompression to apply
+    instead of computing one (reconstruct --compare)."""
+    from .coils import check_virtual_coils
+    K = check_virtual_coils(config.get("virtual_coils"))
+    if matrix is not None:
+        K = matrix.coils_out
     if opts.synthetic:
-        from .synthetic import make_kspace
+        from .synthetic import create_coords, make_kspace
         C, H, W = (int(v) for v in opts.synthetic.split(","))
-        return make_kspace(C, H, W, normalization=config.get("normalization", normalization), image_space=image_space)
+        norm = config.get("normalization", normalization)
+        if not K:
+            return (*make_kspace(C, H, W, normalization=norm, image_space=image_space), None)
+        from .datasets import compress_coils, normalize_image, normalize_kspace
+        check_virtual_coils(K, C)  # before anything is generated
+        raw = make_kspace(C, H, W, normalization=None, image_space=image_space)[0].reshape(C, H, W, 2).to("cuda")
+        data, rec = compress_coils(raw, K, image_space, matrix)
+        data = normalize_image(data) if image_space else normalize_kspace(data, norm)
+        return data.reshape(K * H * W, 2).contiguous(), create_coords(K, H, W), (K, H, W), rec
     from .datasets import from_config, trainer_inputs
-    return trainer_inputs(from_config(config, "cuda"))
+    ds = from_config(config, "cuda", coil_matrix=matrix)
+    return (*trainer_inputs(ds), ds.coil_compression)
 
 
 def cli_folders(tr, opts):
@@ -164,6 +188,8 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
     torch.cuda.synchronize()
     res = {"steps": tr.global_step, "seconds": time.time() - t0, "psnr": tr.evaluate(),
            "shuffle": tr.shuffle, "shuffle_seed": tr.shuffle_seed if tr.shuffle else None}
+    if tr.coil_compression is not None:
+        res["coil_compression"] = tr.coil_compression.summary()
     if extra:
         res.update(extra)
     if opts.val:

@@ -155,18 +155,38 @@ def normalize_kspace(k: torch.Tensor, type: Optional[str] = "max", eps: float = 
     return k
 
 
+def compress_coils(data: torch.Tensor, virtual_coils: int, in_image_space: bool, coil_matrix=None):
+    """[C,H,W,2] before normalisation -> ([K,H,W,2], CoilCompression) through coils.compress, or through the stored
+    record ``coil_matrix``, which is returned as it is (nothing is recomputed)."""
+    from . import coils
+    if coil_matrix is None:
+        return coils.compress(data.contiguous(), virtual_coils, in_image_space)
+    if int(data.shape[0]) != coil_matrix.coils_in:
+        raise ValueError(f"the stored coil compression takes {coil_matrix.coils_in} coils, the scan has {int(data.shape[0])}")
+    return coil_matrix.apply(data.contiguous()), coil_matrix
+
+
 def preprocess_slice(kspace_slice, crop_size, transform: bool, centercrop: bool = True, normalization="max",
-                     full_norm: bool = False, device="cpu") -> torch.Tensor:
+                     full_norm: bool = False, device="cpu", virtual_coils=None, coil_matrix=None):
     """One raw slice [C,H,W] complex -> the normalised [C,H',W',2] fp32 tensor the loops fit
     (nerp_datasets.py:60-76): ifft2c, centre crop in image space, then either normalize_image (image mode) or
-    fft2c + normalize_kspace (k-space mode)."""
+    fft2c + normalize_kspace (k-space mode).
+    ``virtual_coils`` = K (coils.py; None or 0: off, the code above and its return value, unchanged): after the centre
+    crop the coils are compressed IN IMAGE SPACE (the transform is linear and commutes with the FFT, and the cropped coil
+    images are what both modes have at hand), then normalised; returns (data [K,H',W',2], CoilCompression).
+    ``coil_matrix``: a stored CoilCompression to apply instead of computing one."""
     z = torch.as_tensor(np.ascontiguousarray(kspace_slice)).to(torch.complex64).to(device)
     data = ifft2c(torch.view_as_real(z))
     if centercrop:
         data = complex_center_crop(data, crop_size)
+    rec = None
+    if virtual_coils or coil_matrix is not None:
+        data, rec = compress_coils(data, virtual_coils, True, coil_matrix)
     if transform:
-        return normalize_image(data, full_norm).contiguous()
-    return normalize_kspace(fft2c(data), normalization).contiguous()
+        out = normalize_image(data, full_norm).contiguous()
+    else:
+        out = normalize_kspace(fft2c(data), normalization).contiguous()
+    return out if rec is None else (out, rec)
 
 
 class MRIDataset:
@@ -175,7 +195,7 @@ class MRIDataset:
 
     def __init__(self, data_class="brain", data_root="data", challenge="multicoil", set="train", transform=True,
                  sample=0, slice=0, full_norm=False, custom_file_or_path=None, per_coil_stats=True, centercrop=True,
-                 normalization="max", device="cuda"):
+                 normalization="max", device="cuda", virtual_coils=None, coil_matrix=None):
         self.challenge, self.transform, self.data_class = challenge, transform, data_class
         self.data_root, self.set, self.device = data_root, set, torch.device(device)
         if custom_file_or_path is None or custom_file_or_path == "":
@@ -183,7 +203,14 @@ class MRIDataset:
         else:
             self.root = custom_file_or_path
         kspace, crop_size, self.file_name = load_kspace_file(self.root, sample)
-        data = preprocess_slice(kspace[slice], crop_size, transform, centercrop, normalization, full_norm, self.device)
+        from .coils import check_virtual_coils
+        K = check_virtual_coils(virtual_coils, int(kspace.shape[1]))  # ValueError before anything runs
+        self.coil_compression = None  # coils.CoilCompression when config['virtual_coils'] is set
+        if K or coil_matrix is not None:  # shape, coordinates and per-coil statistics are those of the K virtual coils
+            data, self.coil_compression = preprocess_slice(kspace[slice], crop_size, transform, centercrop, normalization,
+                                                           full_norm, self.device, K, coil_matrix)
+        else:
+            data = preprocess_slice(kspace[slice], crop_size, transform, centercrop, normalization, full_norm, self.device)
         self.shape = tuple(data.shape)  # (C, H, W, 2)
         self.coil_stats = per_coil_statistics(data) if per_coil_stats else None
         self.flatten_image_and_create_coords(data)
@@ -221,10 +248,10 @@ class MRIDatasetUndersampling(MRIDataset):
 
     def __init__(self, data_class="brain", data_root="data", challenge="multicoil", set="train", transform=True,
                  sample=0, slice=0, full_norm=False, custom_file_or_path=None, per_coil_stats=True, centercrop=True,
-                 normalization="max", undersampling=None, device="cuda"):
+                 normalization="max", undersampling=None, device="cuda", virtual_coils=None, coil_matrix=None):
         self.undersampling_argument, self.undersampling_params = parse_undersampling_argument(undersampling)
         super().__init__(data_class, data_root, challenge, set, transform, sample, slice, full_norm,
-                         custom_file_or_path, per_coil_stats, centercrop, normalization, device)
+                         custom_file_or_path, per_coil_stats, centercrop, normalization, device, virtual_coils, coil_matrix)
 
     def flatten_image_and_create_coords(self, data: torch.Tensor) -> None:
         C, H, W, S = data.shape
@@ -251,9 +278,11 @@ class MRIDatasetWithDistances(MRIDatasetUndersampling):
 
     def __init__(self, data_class="brain", data_root="data", challenge="multicoil", set="train", transform=True,
                  sample=0, slice=0, full_norm=False, custom_file_or_path=None, per_coil_stats=True, centercrop=True,
-                 normalization="max", cat_coil=False, cat_dists=False, undersampling=None, device="cuda"):
+                 normalization="max", cat_coil=False, cat_dists=False, undersampling=None, device="cuda",
+                 virtual_coils=None, coil_matrix=None):
         super().__init__(data_class, data_root, challenge, set, transform, sample, slice, full_norm,
-                         custom_file_or_path, per_coil_stats, centercrop, normalization, undersampling, device)
+                         custom_file_or_path, per_coil_stats, centercrop, normalization, undersampling, device,
+                         virtual_coils, coil_matrix)
         self.dist_to_center = torch.sqrt(self.coords[..., 1] ** 2 + self.coords[..., 2] ** 2)
         if cat_dists:
             self.coords = torch.cat((self.coords, self.dist_to_center.unsqueeze(-1)), dim=-1)
@@ -299,7 +328,7 @@ class MRICoilWrapperDataset:
 
 def get_datasets(data, data_root, set, transform=True, sample=0, slice=0, challenge="multicoil", full_norm=False,
                  normalization="max", use_dists="no", undersampling=None, per_coil=False, custom_file_or_path=None,
-                 device="cuda"):
+                 device="cuda", virtual_coils=None):
     """The dataset half of models/utils.py:57-135 ``get_data_loader``: -> (dataset, train_dataset).  ``dataset`` is
     the fully sampled one the validation sweep reads; ``train_dataset`` is the undersampled (and, with ``per_coil``,
     coil-wrapped) one the loop trains on -- the same object as ``dataset`` when nothing is undersampled.  The
@@ -309,11 +338,15 @@ def get_datasets(data, data_root, set, transform=True, sample=0, slice=0, challe
     common = dict(data_class=data, data_root=data_root, challenge=challenge, set=set, transform=transform,
                   sample=sample, slice=slice, full_norm=full_norm, normalization=normalization,
                   custom_file_or_path=custom_file_or_path, device=device)
+    if virtual_coils:  # (absent or 0: the calls below are the ones made without the switch)
+        common["virtual_coils"] = virtual_coils
     none = undersampling is None or str(undersampling).lower() == "none"
     if dists:
         dataset = MRIDatasetWithDistances(undersampling=None, **common)
     else:
         dataset = MRIDataset(**common)
+    if virtual_coils and not none:  # the training view goes through the matrix of the fully sampled one
+        common = dict(common, virtual_coils=None, coil_matrix=dataset.coil_compression)
     if none:
         train = dataset
     elif dists:
@@ -358,10 +391,14 @@ def trainer_inputs(dataset):
     return dataset.image, dataset.coords[:, :3].contiguous(), (C, H, W)
 
 
-def from_config(config: dict, device="cuda"):
+def from_config(config: dict, device="cuda", coil_matrix=None):
     """The fully sampled dataset train.py:271-287 builds from config['data' / 'data_root' / 'set' / 'sample' /
-    'slice' / 'transform' / 'full_norm' / 'normalization'] (+ 'custom_file_or_path')."""
-    return MRIDataset(data_class=config.get("data", "brain"), data_root=config.get("data_root", "data"),
+    'slice' / 'transform' / 'full_norm' / 'normalization'] (+ 'custom_file_or_path'; config['virtual_coils'] or a stored
+    ``coil_matrix``: compressed to virtual coils, coils.py)."""
+    extra = {}
+    if config.get("virtual_coils") or coil_matrix is not None:
+        extra = dict(virtual_coils=config.get("virtual_coils"), coil_matrix=coil_matrix)
+    return MRIDataset(**extra, data_class=config.get("data", "brain"), data_root=config.get("data_root", "data"),
                       set=config.get("set", "train"), transform=bool(config.get("transform", False)),
                       sample=config.get("sample", 0), slice=config.get("slice", 0),
                       full_norm=config.get("full_norm", False), normalization=config.get("normalization", "max"),

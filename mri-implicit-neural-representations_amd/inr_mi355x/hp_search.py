@@ -55,7 +55,7 @@ STAT_KEYS = tuple(INITIAL_STATS)
 # batch_size only shapes the loader there, and the trainers apply 'undersampling' / 'per_coil' to the resident tensors
 # themselves -- they stay in the key so that a source which does look at them is never served a stale entry).
 DATA_KEYS = ("data", "data_root", "set", "sample", "slice", "custom_file_or_path", "transform", "normalization",
-             "full_norm", "undersampling", "per_coil")
+             "full_norm", "undersampling", "per_coil", "virtual_coils")
 CACHE_BUDGET_BYTES = 8 << 30  # resident datasets kept between trials; least recently used ones go first above it
 # Worker processes per search.  The GPU boxes are shared and allow 16 processes with the device open in total: a search
 # takes at most half of them, and at 25 000-row batches 196 of 256 CUs are busy already (README, Switches).
@@ -182,11 +182,14 @@ class DataCache:
         if key in self.entries:
             self.entries.move_to_end(key)
             return self.entries[key]
-        image, coords, shape = self.source(config)
+        got = self.source(config)
+        image, coords, shape = got[:3]
         self.ingests += 1
         if self.device is not None:
             image, coords = image.to(self.device).contiguous(), coords.to(self.device).contiguous()
         entry = (image, coords, tuple(int(v) for v in shape[:3]))
+        if len(got) > 3 and got[3] is not None:  # config['virtual_coils']: the compression the data came through
+            entry = entry + (got[3],)
         self.entries[key] = entry
         while self.entries and sum(self._bytes(e) for e in self.entries.values()) > self.budget:
             self.entries.popitem(last=False)
@@ -196,6 +199,11 @@ class DataCache:
 def synthetic_source(C: int, H: int, W: int) -> Callable:
     """--synthetic C,H,W: make_kspace with the trial's 'normalization' and 'transform', as inr_mi355x.train does."""
     def source(cfg):
+        if cfg.get("virtual_coils"):
+            import argparse
+            from .cli import cli_fit_data
+            return cli_fit_data(argparse.Namespace(synthetic=f"{C},{H},{W}"), cfg, "coil",
+                                image_space=bool(cfg.get("transform", False)))
         from .synthetic import make_kspace
         return make_kspace(C, H, W, normalization=cfg.get("normalization", "coil"),
                            image_space=bool(cfg.get("transform", False)))
@@ -205,15 +213,17 @@ def synthetic_source(C: int, H: int, W: int) -> Callable:
 def dataset_source(cfg):
     """find_best_config.py:56-72: the scan the config names."""
     from .datasets import from_config, trainer_inputs
-    return trainer_inputs(from_config(cfg, "cuda"))
+    ds = from_config(cfg, "cuda")
+    return (*trainer_inputs(ds), ds.coil_compression)
 
 
 # ---- one trial (hp_model_training.py:13-228) --------------------------------------------------------------------------
 def build_trial_trainer(cfg: dict, data, seed: int = 0, device="cuda"):
     """The trainer of a trial: encoder from ``seed``, model from torch.manual_seed(42) (hp_model_training.py:46-49)."""
     from .train import INRTrainer
-    image, coords, shape = data
-    return INRTrainer(cfg, image, coords, shape, device, seed=seed, model_seed=MODEL_SEED)
+    image, coords, shape = data[:3]
+    return INRTrainer(cfg, image, coords, shape, device, seed=seed, model_seed=MODEL_SEED,
+                      coil_compression=data[3] if len(data) > 3 else None)
 
 
 def hp_training_function(config: dict, max_epoch: int, data, *, seed: int = 0, image_directory: Optional[str] = None,
@@ -560,6 +570,8 @@ def main(argv=None) -> int:
                     help="bytes of resident datasets kept between trials (0: ingest for every trial)")
     from .bands import add_band_report_flag, flag_bounds
     add_band_report_flag(ap, "per trial")
+    from .coils import add_virtual_coils_flag, apply_virtual_coils_flag
+    add_virtual_coils_flag(ap)
     opts = ap.parse_args(argv)
     if opts.worker:
         return worker_main()
@@ -568,7 +580,7 @@ def main(argv=None) -> int:
     if not 1 <= opts.jobs <= MAX_JOBS:
         ap.error("--jobs {}: 1..{} (the GPU boxes are shared and allow 16 GPU processes in total)".format(opts.jobs, MAX_JOBS))
     from .train import get_config, set_default_configs
-    config = set_default_configs(get_config(opts.config))
+    config = apply_virtual_coils_flag(set_default_configs(get_config(opts.config)), opts)
     hp_config = get_config(opts.hp_config)
     check_search(config, hp_config)
     output_directory = search_directory(config, hp_config, opts.config, opts.output_path)

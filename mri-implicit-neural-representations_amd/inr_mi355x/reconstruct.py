@@ -14,11 +14,13 @@ which is a lower-resolution image.
 CLI:
     python -m inr_mi355x.reconstruct --config C --checkpoint F (--shape C,H,W | --synthetic C,H,W | the config's scan)
         [--scale S] [--height H] [--width W] [--window y0,y1,x0,x1] [--coils 0,3,5]
-        [--radii r0,r1,...] [--chunk N] [--compare] [--output_path O]
+        [--radii r0,r1,...] [--chunk N] [--compare] [--expand-coils] [--output_path O]
 --shape needs no data at all; with --synthetic or the config's scan the shape comes from the data.  --compare adds PSNR
 and SSIM against the data (native grid, full window, all coils only).  Prints one JSON line: shape, rows, seconds,
 rows_per_s, files (and psnr / ssim with --compare).  Ring-ensemble ``submodel_%d.pt`` files are out of scope: their
-radii are not in the file.
+radii are not in the file.  A checkpoint of a fit on virtual coils (config['virtual_coils'], coils.py) renders those K coils:
+--shape's C must be K, --coils indexes virtual coils, --compare compresses the scan with the matrix stored in the
+checkpoint, and --expand-coils also writes recon_physical.npy, the projection on the physical coils.
 """
 from __future__ import annotations
 
@@ -107,8 +109,25 @@ class Reconstructor:
             checkpoint = torch.load(checkpoint, map_location=self.device)
         if "net" not in checkpoint:
             raise ValueError("not a {'net', 'enc', 'opt'} checkpoint (ring-ensemble submodel files are not supported)")
+        self.coil_compression = None  # coils.CoilCompression of a fit on virtual coils: render() gives those K coils
+        if checkpoint.get("coil_compression") is not None:
+            from .coils import CoilCompression
+            self.coil_compression = CoilCompression.from_state(checkpoint["coil_compression"])
+            if self.shape[0] != self.coil_compression.coils_out:
+                raise ValueError(f"the checkpoint was fitted on {self.coil_compression.coils_out} virtual coils (of "
+                                 f"{self.coil_compression.coils_in} physical ones) but shape has C = {self.shape[0]}")
         load_weights(self.model, self.encoder, checkpoint, self._rebind_encoder)
         self.engine.pack()
+
+    @torch.no_grad()
+    def expand(self, pred: torch.Tensor) -> torch.Tensor:
+        """[coils_in, H', W', 2]: the physical-coil projection of a rendering of ALL virtual coils (inr_coil_apply with the
+        conjugate transpose of the stored matrix)."""
+        if self.coil_compression is None:
+            raise ValueError("the checkpoint carries no coil compression: there is nothing to expand")
+        if pred.dim() != 4 or pred.shape[0] != self.coil_compression.coils_out:
+            raise ValueError(f"expand() takes all {self.coil_compression.coils_out} virtual coils, got {tuple(pred.shape)}")
+        return self.coil_compression.expand(pred.contiguous())
 
     # ---- sampling --------------------------------------------------------------------------------
     def grid(self, height: Optional[int] = None, width: Optional[int] = None, scale: Optional[float] = None,
@@ -238,7 +257,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--window", type=_numbers(float, 4, "--window y0,y1,x0,x1"), default=None,
                     help="y0,y1,x0,x1; the fit's own grid is -1,1,-1,1")
-    ap.add_argument("--coils", type=_numbers(int, None, "--coils"), default=None, help="coil indices, in output order")
+    ap.add_argument("--coils", type=_numbers(int, None, "--coils"), default=None,
+                    help="coil indices, in output order (virtual coils for a checkpoint that carries coil compression)")
+    ap.add_argument("--expand-coils", action="store_true",
+                    help="a checkpoint fitted on virtual coils: also write the physical-coil projection (recon_physical.npy)")
     ap.add_argument("--radii", type=_numbers(float, None, "--radii"), default=None,
                     help="ring radii of a multiscale fit (its training command's JSON line)")
     ap.add_argument("--chunk", type=int, default=None, help="rows per forward call")
@@ -277,6 +299,8 @@ def parse_args(argv=None):
         if any(getattr(opts, k) is not None for k in ("scale", "height", "width", "window", "coils")):
             ap.error("--compare is valid on the native grid, full window, all coils only "
                      "(drop --scale / --height / --width / --window / --coils)")
+    if opts.expand_coils and opts.coils is not None:
+        ap.error("--expand-coils needs all virtual coils (drop --coils)")
     if opts.band_report is not None:
         if not opts.compare:
             ap.error("--band-report needs --compare (the report is the prediction's error against the data)")
@@ -285,18 +309,26 @@ def parse_args(argv=None):
 
 def main(argv=None) -> None:
     opts = parse_args(argv)
-    from .cli import cli_data, get_config
+    from .cli import cli_fit_data, get_config
+    from .coils import CoilCompression
     from .trainer_base import set_default_configs
     config = set_default_configs(get_config(opts.config))
     multiscale = config["model"] in MULTISCALE_MODELS
     image = None
+    checkpoint = torch.load(opts.checkpoint, map_location="cuda")
+    stored = checkpoint.get("coil_compression") if isinstance(checkpoint, dict) else None
+    stored = None if stored is None else CoilCompression.from_state(stored)
+    if opts.expand_coils and stored is None:
+        raise SystemExit("--expand-coils: the checkpoint carries no coil compression")
     if opts.shape is not None:
         shape = tuple(opts.shape)
     else:
+        # the data go through the STORED matrix (or through none): a compression is never recomputed here
         data_opts = argparse.Namespace(synthetic=None if opts.synthetic is None else ",".join(str(v) for v in opts.synthetic))
-        image, _, shape = cli_data(data_opts, config, "max" if multiscale else "coil",
-                                   image_space=bool(config.get("transform", False)) and not multiscale)
-    rec = Reconstructor(config, opts.checkpoint, shape, "cuda", radii=opts.radii)
+        image, _, shape, _ = cli_fit_data(data_opts, dict(config, virtual_coils=0), "max" if multiscale else "coil",
+                                          image_space=bool(config.get("transform", False)) and not multiscale,
+                                          matrix=stored)
+    rec = Reconstructor(config, checkpoint, shape, "cuda", radii=opts.radii)
     torch.cuda.synchronize()
     t0 = time.time()
     pred = rec.render(opts.height, opts.width, opts.scale, opts.window, opts.coils, opts.chunk)
@@ -309,7 +341,12 @@ def main(argv=None) -> None:
         res.update(rec.compare(pred, image, bands=flag_bounds(opts.band_report)))
         if "bands" in res:
             print(format_band_table(res["bands"]), flush=True)
+    if rec.coil_compression is not None:
+        res["coil_compression"] = rec.coil_compression.summary()
     res["files"] = rec.save(opts.output_path, pred)
+    if opts.expand_coils:
+        res["files"].append(os.path.join(opts.output_path, "recon_physical.npy"))
+        np.save(res["files"][-1], rec.expand(pred).cpu().numpy())
     print(json.dumps(res))
 
 

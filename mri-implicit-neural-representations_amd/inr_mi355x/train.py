@@ -12,7 +12,7 @@ config values raise instead of falling through.
 
 CLI (same flags as the reference, train.py:255-258):
     python -m inr_mi355x.train --config cfg.yaml [--output_path out] [--synthetic C,H,W] [--val]
-                               [--shuffle] [--shuffle-seed S] [--save-images] [--band-report [N]]
+                               [--shuffle] [--shuffle-seed S] [--save-images] [--band-report [N]] [--virtual-coils K]
                                [--data_samples samples.yaml]
 --val runs the reference's validation epoch every config['val_epoch'] epochs (its line is printed) and saves a
 checkpoint every config['image_save_epoch'] epochs.  --save-images (with --val) also writes the reference's pictures
@@ -29,8 +29,8 @@ from typing import Optional
 import torch
 
 from . import _lib as L
-from .cli import (add_shuffle_flags, apply_shuffle_flags, cli_data, cli_fits, expand_data_samples,  # noqa: F401
-                  get_config, parse_cli, run_cli)
+from .cli import (add_shuffle_flags, apply_shuffle_flags, cli_data, cli_fit_data, cli_fits,  # noqa: F401
+                  expand_data_samples, get_config, parse_cli, run_cli)
 from .engine import LossSpec
 from .mfn import FourierNet, GaborNet, KGaborNet
 from .networks import FFN, SIREN, WIRE, WIRE2D
@@ -136,8 +136,8 @@ class INRTrainer(ResidentFit):
     def __init__(self, config: dict, image: torch.Tensor, coords: torch.Tensor, shape, device,
                  seed: int = 0, mask: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1,
                  process_group=None, mask_seed: Optional[int] = None, graph_steps: bool = False,
-                 model_seed: Optional[int] = None):
-        config = self._init_fit(config, shape, device, seed, rank, world, process_group, graph_steps)
+                 model_seed: Optional[int] = None, coil_compression=None):
+        config = self._init_fit(config, shape, device, seed, rank, world, process_group, graph_steps, coil_compression)
         self.in_image_space = bool(config.get("transform", False))
         if config["model"] not in MODELS:
             raise NotImplementedError(f"model {config['model']!r} has no MI355X kernel yet (have {sorted(MODELS)})")
@@ -371,8 +371,8 @@ class INRTrainer(ResidentFit):
 def main():
     opts, config = parse_cli()
     for cfg, fit_opts in cli_fits(config, opts):
-        image, coords, shape = cli_data(opts, cfg, "coil", image_space=bool(cfg.get("transform", False)))
-        run_cli(INRTrainer(cfg, image, coords, shape, "cuda"), cfg, fit_opts)
+        image, coords, shape, cc = cli_fit_data(opts, cfg, "coil", image_space=bool(cfg.get("transform", False)))
+        run_cli(INRTrainer(cfg, image, coords, shape, "cuda", coil_compression=cc), cfg, fit_opts)
 
 
 if __name__ == "__main__":

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .cli import cli_data, cli_fits, parse_cli, run_cli
+from .cli import cli_data, cli_fit_data, cli_fits, parse_cli, run_cli  # noqa: F401
 from .engine import ConsistencySpec, LossSpec
 from .mfn import MultiscaleBoundedFourier, MultiscaleKFourier
 from .train import exchange_and_update, wants_sharded_update
@@ -32,8 +32,10 @@ def create_pairs(values: Sequence[float], multiplication_factor: int):
 class MultiscaleTrainer(ResidentFit):
     def __init__(self, config: dict, image: torch.Tensor, coords: torch.Tensor, dist: torch.Tensor,
                  radii: Optional[Sequence[float]], shape, device, seed: int = 0, rank: int = 0, world: int = 1,
-                 process_group=None, mask: Optional[torch.Tensor] = None, mask_seed: Optional[int] = None):
-        config = self._init_fit(config, shape, device, seed, rank, world, process_group)
+                 process_group=None, mask: Optional[torch.Tensor] = None, mask_seed: Optional[int] = None,
+                 coil_compression=None):
+        config = self._init_fit(config, shape, device, seed, rank, world, process_group,
+                                coil_compression=coil_compression)
         if radii is None:  # train_kspace_multiscale.py:73-84
             from .clustering import partition_and_stats
             C, H, W = int(shape[0]), int(shape[1]), int(shape[2])
@@ -169,14 +171,14 @@ class MultiscaleTrainer(ResidentFit):
 def main():
     """CLI with the reference's flags (train_kspace_multiscale.py:50-52): --config, --output_path, --data_samples; the scan
     comes from datasets.py, or a synthetic k-space with --synthetic C,H,W.  --val / --save-images /
-    --band-report [N] as inr_mi355x.train."""
+    --band-report [N] / --virtual-coils K as inr_mi355x.train."""
     opts, config = parse_cli()
     if config["model"] not in ("BoundedFourier",):
         config["model"] = "MultiscaleKFourier"  # train_kspace_multiscale.py:93-98: anything else is the unbounded net
     for cfg, fit_opts in cli_fits(config, opts):  # one fit, or one per (sample, slice) of --data_samples
-        image, coords, shape = cli_data(opts, cfg, "max")
+        image, coords, shape, cc = cli_fit_data(opts, cfg, "max")
         dist = torch.sqrt(coords[:, 1] ** 2 + coords[:, 2] ** 2)
-        tr = MultiscaleTrainer(cfg, image, coords, dist, None, shape, "cuda")
+        tr = MultiscaleTrainer(cfg, image, coords, dist, None, shape, "cuda", coil_compression=cc)
         run_cli(tr, cfg, fit_opts, extra={"radii": tr.radii})
 
 

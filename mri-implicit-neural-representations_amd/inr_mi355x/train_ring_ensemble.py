@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .cli import cli_band_report, cli_data, cli_folders, cli_validation_images, parse_cli, print_band_tables
+from .cli import cli_band_report, cli_data, cli_fit_data, cli_folders, cli_validation_images, parse_cli, print_band_tables
 from .engine import LossSpec
 from .train import MODELS, MFN_MODELS
 from .trainer_base import ResidentFit
@@ -46,8 +46,9 @@ class RingEnsembleTrainer(ResidentFit):
 
     def __init__(self, config: dict, image: torch.Tensor, coords: torch.Tensor, shape, device,
                  radii: Optional[Sequence[float]] = None, seed: int = 0, rank: int = 0, world: int = 1,
-                 process_group=None, jitter: float = 0.0):
-        config = self._init_fit(config, shape, device, seed, rank, world, process_group)
+                 process_group=None, jitter: float = 0.0, coil_compression=None):
+        config = self._init_fit(config, shape, device, seed, rank, world, process_group,
+                                coil_compression=coil_compression)
         self.in_image_space = bool(config.get("transform", False))
         if config["model"] not in MODELS or config["model"] in MFN_MODELS:
             raise NotImplementedError(f"ring ensembles are built from SIREN / FFN / WIRE / WIRE2D, not {config['model']!r}")
@@ -172,12 +173,16 @@ class RingEnsembleTrainer(ResidentFit):
 
     def checkpoints(self) -> dict:
         """{ring: {'net', 'enc'}} of the owned rings (submodel_%d files of train_clustering.py:243-249)."""
-        return {i: {"net": self.models[i].state_dict(), "enc": self.encoder.B} for i in self.owned}
+        out = {i: {"net": self.models[i].state_dict(), "enc": self.encoder.B} for i in self.owned}
+        if self.coil_compression is not None:
+            for sd in out.values():
+                sd["coil_compression"] = self.coil_compression.state()
+        return out
 
 
 def main():
     """python -m inr_mi355x.train_ring_ensemble --config cfg.yaml [--output_path out] [--synthetic C,H,W]
-    [--max_steps N] [--shuffle] [--shuffle-seed S] [--save-images] [--band-report [N]]: fit the rings (radii from
+    [--max_steps N] [--shuffle] [--shuffle-seed S] [--save-images] [--band-report [N]] [--virtual-coils K]: fit the rings (radii from
     config['partition']), print
     one JSON line with the assembled reconstruction's PSNR / SSIM and save the submodel_%d files of
     train_clustering.py:243-249.  --save-images writes train.png / train_kspace.png and the final metrics()' pictures
@@ -189,8 +194,8 @@ def main():
     import time
 
     opts, config = parse_cli(val_and_samples=False)
-    image, coords, shape = cli_data(opts, config, "coil", image_space=bool(config.get("transform", False)))
-    tr = RingEnsembleTrainer(config, image, coords, shape, "cuda")
+    image, coords, shape, cc = cli_fit_data(opts, config, "coil", image_space=bool(config.get("transform", False)))
+    tr = RingEnsembleTrainer(config, image, coords, shape, "cuda", coil_compression=cc)
     ckpt_dir, image_dir = cli_folders(tr, opts)
     cli_band_report(tr, opts)
     t0 = time.time()

@@ -26,6 +26,7 @@ def set_default_configs(config: dict) -> dict:
     if "regularization" not in config:
         config["regularization"] = {"type": "none"}
     config.setdefault("undersampling", None)
+    config.setdefault("virtual_coils", 0)  # coils.py: K virtual coils instead of the scan's physical ones; 0 = off
     return config
 
 
@@ -92,11 +93,23 @@ class ResidentFit(ValidationMixin):
 
     # ---- set-up ----------------------------------------------------------------------------------
     def _init_fit(self, config: dict, shape, device, seed: int, rank: int, world: int, process_group,
-                  graph_steps: bool = False) -> dict:
-        """Defaults, the shuffle settings (which refuse shuffle with graph steps before anything is allocated) and where
-        the fit runs.  Returns the trainer's own copy of the config."""
+                  graph_steps: bool = False, coil_compression=None) -> dict:
+        """Defaults, the shuffle settings (which refuse shuffle with graph steps before anything is allocated), the coil
+        compression the data came through (config['virtual_coils'] = K needs the record of a K-coil compression and
+        K-coil data, and the other way round: ValueError before anything is allocated) and where the fit runs.  Returns
+        the trainer's own copy of the config."""
         config = set_default_configs(dict(config))
         self.config = config
+        from .coils import check_virtual_coils
+        K = check_virtual_coils(config["virtual_coils"])
+        if K and coil_compression is None:
+            raise ValueError(f"config['virtual_coils'] = {K} but the data ({int(shape[0])} coils) came without a coil "
+                             "compression: compress it first (cli.cli_fit_data, datasets.MRIDataset(virtual_coils=K) or "
+                             "coils.compress) and pass coil_compression=")
+        if coil_compression is not None and (K != coil_compression.coils_out or int(shape[0]) != K):
+            raise ValueError(f"config['virtual_coils'] = {K}, the data has {int(shape[0])} coils and the compression "
+                             f"record says {coil_compression.coils_in} -> {coil_compression.coils_out}")
+        self.coil_compression = coil_compression
         self.shuffle, self.shuffle_seed = shuffle_settings(config, seed, graph_steps)
         self.device = torch.device(device)
         self.rank, self.world, self.pg = rank, world, process_group
@@ -247,6 +260,8 @@ class ResidentFit(ValidationMixin):
         m = self._device_metrics(self.image_full, self.predict_all(), self.in_image_space)
         psnr_, ssim_ = m[:2].cpu().tolist()
         rec = {"psnr": psnr_, "ssim": ssim_}
+        if self.coil_compression is not None:
+            rec["coil_compression"] = self.coil_compression.summary()
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         return rec
@@ -255,7 +270,10 @@ class ResidentFit(ValidationMixin):
     def checkpoint(self) -> dict:
         """Same dict as train.py:247-250 ('opt' in torch.optim.Adam.state_dict() layout)."""
         from .checkpoint import save_dict
-        return save_dict(self.model, self.encoder, self.engine, self.config)
+        ckpt = save_dict(self.model, self.encoder, self.engine, self.config)
+        if self.coil_compression is not None:  # the reference's three entries stay as they are
+            ckpt["coil_compression"] = self.coil_compression.state()
+        return ckpt
 
     def _rebind_encoder(self, enc) -> None:
         """a checkpoint replaced encoder.B: the fused kernels hold their own contiguous copy"""
@@ -265,4 +283,9 @@ class ResidentFit(ValidationMixin):
     def load_checkpoint(self, ckpt: dict) -> None:
         """train.py:117-121 (config['pretrain']): weights, Adam moments / step count and the encoder matrix."""
         from .checkpoint import load_dict
+        from .coils import same_compression
+        mine = None if self.coil_compression is None else self.coil_compression.state()
+        differs = same_compression(ckpt.get("coil_compression"), mine)
+        if differs is not None:
+            raise ValueError(f"checkpoint and trainer disagree: {differs} (checkpoint first)")
         load_dict(self.model, self.encoder, self.engine, ckpt, self._rebind_encoder)

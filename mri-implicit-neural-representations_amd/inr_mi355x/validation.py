@@ -179,6 +179,8 @@ class ValidationMixin:
         test_loss = None if loss_sum is None else float(host[2]) / n_train_batches
         self.update_best(epoch, psnr, ssim)
         rec = {"epoch": epoch, "test_loss": test_loss, "psnr": psnr, "ssim": ssim}
+        if getattr(self, "coil_compression", None) is not None:  # scored against the K virtual-coil targets
+            rec["coil_compression"] = self.coil_compression.summary()
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         self.val_history.append(rec)
