@@ -50,7 +50,8 @@ extern "C" {
  *    inr_coil_stats and their scratch queries (the pictures and the per-coil table of the validation epoch); inr_grid_rows
  *    (rows of a coordinate grid, made on the device: reconstruction from a checkpoint on any grid); inr_band_stats and its
  *    scratch query (per-band counts, energies, errors and extrema of a field against radius); inr_coil_gram, its scratch
- *    query and inr_coil_apply (software coil compression: the coil Gram matrix in one pass, the product with a small matrix).
+ *    query and inr_coil_apply (software coil compression: the coil Gram matrix in one pass, the product with a small matrix);
+ *    inr_nudft and its scratch query (the continuous k-space of coil images at off-grid positions).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -524,6 +525,25 @@ int inr_coil_gram_scratch(int32_t C, int64_t N, int64_t* scratch_doubles);
 int inr_coil_gram(const float* data, int32_t C, int64_t N, double* gram, double* scratch, int64_t scratch_doubles,
                   void* stream);
 int inr_coil_apply(const float* in, const float* A, int32_t M, int32_t K, int64_t N, float* out, void* stream);
+
+/* (v7 addition) Off-grid samples of the continuous k-space of coil images (no reference counterpart; DESIGN.md section
+ * 4.19).  img [C][H][W][2]: complex fp32 coil images, centred as an inverse centred FFT leaves them; pos [M][2]: fp64
+ * (u_y, u_x) in index units, any finite value (the transform is periodic); out [C][M][2] fp32,
+ *   out[c][m] = 1/sqrt(H W) sum_y sum_x img[c][y][x] exp(-2 pi i ((u_y - c_y)(y - c_y)/H + (u_x - c_x)(x - c_x)/W)),
+ * c_y = H/2, c_x = W/2 (integer division): at integer positions the centred FFT of the image.  The phase is reduced in
+ * fp64 (its fractional part is taken before the multiplication by 2 pi), phasors and sums are fp32, the order of the
+ * sums is fixed (no atomics): two calls give the same bits.  `scratch` (device, 16-byte aligned) holds at least what
+ * inr_nudft_scratch gives for (C, H, W, M) -- a function of its arguments alone (the phasor tables: 2 (W' + H') M' floats
+ * with W' = W rounded up to 16, H' to 64 and M' = M to INR_NUDFT_TILE); `scratch_floats` is what the caller's buffer
+ * holds.  Two launches on `stream`, nothing allocated, nothing read back.
+ * inr_mi355x/trajectory.py::nudft_numpy restates it in fp64.
+ * INR_ERR_INVALID before any launch: a null pointer; C outside 1..INR_COIL_MAX; H or W < 1; H * W >= 2^31; M < 1 or
+ * M >= 2^31; img / pos / out not 8-byte or scratch not 16-byte aligned; scratch short of the query; out overlapping img
+ * or pos; scratch overlapping any of them. */
+#define INR_NUDFT_TILE 64
+int inr_nudft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats);
+int inr_nudft(const float* img, int32_t C, int64_t H, int64_t W, const double* pos, int64_t M, float* out,
+              float* scratch, int64_t scratch_floats, void* stream);
 
 #ifdef __cplusplus
 }

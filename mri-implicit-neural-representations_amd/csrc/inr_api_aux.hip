@@ -1,5 +1,5 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network: encoders, losses, TV, Adam,
-// image metrics, display, shuffle, grid rows, band statistics, coil compression.  Each checks its arguments, fills an argument struct,
+// image metrics, display, shuffle, grid rows, band statistics, coil compression, off-grid sampling.  Each checks its arguments, fills an argument struct,
 // launches and maps the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -474,6 +474,46 @@ int inr_coil_apply(const float* in, const float* A, int32_t M, int32_t K, int64_
   if (ranges_overlap(out, out_bytes, A, a_bytes)) return fail(INR_ERR_INVALID, "inr_coil_apply: out overlaps A");
   hipError_t e = inr::launch_coil_apply(in, A, M, K, N, out, (hipStream_t)stream);
   return hip_done(e, "inr_coil_apply");
+}
+
+// ---- off-grid samples of the continuous k-space (inr_nudft.hip) ----
+static_assert(INR_NUDFT_TILE == inr::NUDFT_TILE, "inr_abi.h and inr_aux.h disagree");
+
+static int nudft_check(int32_t C, int64_t H, int64_t W, int64_t M, const char* who) {
+  if (int rc = coil_count_check(C, "C", who)) return rc;
+  if (H < 1 || W < 1 || H >= (1LL << 31) || W >= (1LL << 31) || H * W >= (1LL << 31))
+    return fail(INR_ERR_INVALID, "%s: H = %lld, W = %lld (each >= 1, H * W < 2^31)", who, (long long)H, (long long)W);
+  if (M < 1 || M >= (1LL << 31)) return fail(INR_ERR_INVALID, "%s: M = %lld (1 <= M < 2^31 samples per call)", who, (long long)M);
+  return INR_OK;
+}
+
+int inr_nudft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats) {
+  if (scratch_floats == nullptr) return fail(INR_ERR_INVALID, "inr_nudft_scratch: null argument");
+  if (int rc = nudft_check(C, H, W, M, "inr_nudft_scratch")) return rc;
+  *scratch_floats = inr::nudft_scratch_floats(H, W, M);
+  return INR_OK;
+}
+
+int inr_nudft(const float* img, int32_t C, int64_t H, int64_t W, const double* pos, int64_t M, float* out,
+              float* scratch, int64_t scratch_floats, void* stream) {
+  if (img == nullptr || pos == nullptr || out == nullptr || scratch == nullptr)
+    return fail(INR_ERR_INVALID, "inr_nudft: null argument");
+  if (int rc = nudft_check(C, H, W, M, "inr_nudft")) return rc;
+  if ((((uintptr_t)img | (uintptr_t)pos | (uintptr_t)out) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_nudft: img / pos / out is not 8-byte aligned");
+  if (((uintptr_t)scratch & 15u) != 0) return fail(INR_ERR_INVALID, "inr_nudft: scratch is not 16-byte aligned");
+  const int64_t need = inr::nudft_scratch_floats(H, W, M);
+  if (scratch_floats < need)
+    return fail(INR_ERR_INVALID, "inr_nudft: scratch holds %lld floats, H = %lld, W = %lld, M = %lld need %lld",
+                (long long)scratch_floats, (long long)H, (long long)W, (long long)M, (long long)need);
+  const int64_t img_bytes = (int64_t)C * H * W * 8, pos_bytes = M * 16, out_bytes = (int64_t)C * M * 8;
+  if (ranges_overlap(out, out_bytes, img, img_bytes)) return fail(INR_ERR_INVALID, "inr_nudft: out overlaps img");
+  if (ranges_overlap(out, out_bytes, pos, pos_bytes)) return fail(INR_ERR_INVALID, "inr_nudft: out overlaps pos");
+  if (ranges_overlap(scratch, need * 4, out, out_bytes) || ranges_overlap(scratch, need * 4, img, img_bytes) ||
+      ranges_overlap(scratch, need * 4, pos, pos_bytes))
+    return fail(INR_ERR_INVALID, "inr_nudft: scratch overlaps img, pos or out");
+  hipError_t e = inr::launch_nudft(img, C, (int)H, (int)W, pos, M, out, scratch, (hipStream_t)stream);
+  return hip_done(e, "inr_nudft");
 }
 
 int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* host_out) {

@@ -170,4 +170,11 @@ long long coil_gram_scratch_doubles(int C, long long N);
 hipError_t launch_coil_gram(const float* data, int C, long long N, double* gram, double* scratch, hipStream_t st);
 hipError_t launch_coil_apply(const float* in, const float* A, int M, int K, long long N, float* out, hipStream_t st);
 
+// off-grid samples of the continuous k-space (inr_nudft.hip): phasor tables in scratch, then the
+// contraction on the fp32 matrix pipe
+constexpr int NUDFT_TILE = 64;  // INR_NUDFT_TILE: samples per workgroup
+long long nudft_scratch_floats(long long H, long long W, long long M);
+hipError_t launch_nudft(const float* img, int C, int H, int W, const double* pos, long long M, float* out,
+                        float* scratch, hipStream_t st);
+
 }  // namespace inr

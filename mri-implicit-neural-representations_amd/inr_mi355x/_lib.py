@@ -122,7 +122,10 @@ SYMBOLS = {
     "inr_coil_gram_scratch": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_coil_gram": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
     "inr_coil_apply": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P]),
+    "inr_nudft_scratch": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "inr_nudft": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P]),
 }
+NUDFT_TILE = 64  # INR_NUDFT_TILE
 COIL_MAX, COIL_TILE_PIXELS = 32, 128  # INR_COIL_MAX, INR_COIL_TILE_PIXELS
 BAND_MAX, BAND_FIELDS, BAND_TILE_ROWS = 64, 7, 1024  # INR_BAND_MAX, INR_BAND_FIELDS, INR_BAND_TILE_ROWS
 METRICS_WORDS = 8  # inr_image_metrics' metrics_out: psnr, ssim, sse, max_ref, min_ref, max_rec, min_rec, data_range

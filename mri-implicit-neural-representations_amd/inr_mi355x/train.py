@@ -13,6 +13,7 @@ config values raise instead of falling through.
 CLI (same flags as the reference, train.py:255-258):
     python -m inr_mi355x.train --config cfg.yaml [--output_path out] [--synthetic C,H,W] [--val]
                                [--shuffle] [--shuffle-seed S] [--save-images] [--band-report [N]] [--virtual-coils K]
+                               [--trajectory ARG]
                                [--data_samples samples.yaml]
 --val runs the reference's validation epoch every config['val_epoch'] epochs (its line is printed) and saves a
 checkpoint every config['image_save_epoch'] epochs.  --save-images (with --val) also writes the reference's pictures
@@ -137,8 +138,11 @@ class INRTrainer(ResidentFit):
                  seed: int = 0, mask: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1,
                  process_group=None, mask_seed: Optional[int] = None, graph_steps: bool = False,
                  model_seed: Optional[int] = None, coil_compression=None):
-        config = self._init_fit(config, shape, device, seed, rank, world, process_group, graph_steps, coil_compression)
+        config = self._init_fit(config, shape, device, seed, rank, world, process_group, graph_steps, coil_compression,
+                                trajectory_ok=True)
         self.in_image_space = bool(config.get("transform", False))
+        if self.trajectory is not None:
+            self._check_trajectory(config, mask, graph_steps, world)
         if config["model"] not in MODELS:
             raise NotImplementedError(f"model {config['model']!r} has no MI355X kernel yet (have {sorted(MODELS)})")
         if config.get("optimizer", "Adam") != "Adam":
@@ -203,6 +207,7 @@ class INRTrainer(ResidentFit):
                 raise NotImplementedError("loss 'LSL' (CenterLoss): single-rank SIREN / FFN / WIRE fits on plain batches")
         self._hdr_A = {}  # the HDR / Center scalar A per batch of the unshuffled data, and of the epoch buffers
         self._hdr_A_epoch = []
+        self._hdr_A_train = {}  # ... and per batch of the off-grid training rows (config['trajectory'])
         # graph_steps: every batch of the epoch becomes one captured HIP graph (fused kernel, weight-gradient GEMM,
         # reduction, Adam, step advance) replayed from then on -- the batches are fixed views of the resident data
         # (sequential sampler, models/utils.py:126-130), the step count and learning rate live in device memory.
@@ -215,6 +220,26 @@ class INRTrainer(ResidentFit):
         self.one_call_steps = (os.environ.get("INR_ONE_CALL_STEPS", "1") != "0" and not self.is_mfn and not self.use_tv
                                and self.loss.kind != L.LOSS_CENTER and not self._cplx_reg)
         self._finish_init()
+
+    @staticmethod
+    def _check_trajectory(config: dict, mask, graph_steps: bool, world: int) -> None:
+        """What an off-grid fit (config['trajectory']) cannot be combined with -- refused before anything
+        is allocated."""
+        from .undersampling import parse_undersampling_argument
+        t = config["trajectory"]
+        if config.get("transform", False):
+            raise ValueError(f"trajectory = {t!r} with transform: true -- the samples are taken in k-space")
+        method = parse_undersampling_argument(config["undersampling"])[0]
+        if (method is not None and method.lower() != "none") or mask is not None:
+            raise ValueError(f"trajectory = {t!r} with an undersampling pattern or a mask: the trajectory IS the sampling")
+        if config["per_coil"] or config["use_tv"]:
+            raise ValueError(f"trajectory = {t!r} with per_coil / use_tv: off-grid rows do not form a coil grid")
+        if config.get("loss") == "LSL":
+            raise NotImplementedError(f"trajectory = {t!r} with loss 'LSL' (CenterLoss)")
+        if graph_steps:
+            raise NotImplementedError(f"trajectory = {t!r} with graph_steps")
+        if world > 1:
+            raise NotImplementedError(f"trajectory = {t!r} on more than one rank")
 
     # ---- one optimizer step on batch `it` of epoch `epoch` --------------------------------------
     def _inputs(self, lo: int, hi: int, train: bool = False):
@@ -232,6 +257,16 @@ class INRTrainer(ResidentFit):
         if it not in self._hdr_A:
             self._hdr_A[it] = float(torch.mean(hdr_weight(self.coords[lo:hi], self.loss.sigma)))
         return self._hdr_A[it]
+
+    def _train_hdr_A(self, it: int, lo: int, hi: int) -> float:
+        """A of TRAINING batch ``it``: the grid batch's unless the fit trains on off-grid rows"""
+        if self.trajectory is None:
+            return self._batch_hdr_A(it, lo, hi)
+        if self.loss.kind not in (L.LOSS_HDR, L.LOSS_CENTER):
+            return 0.0
+        if it not in self._hdr_A_train:
+            self._hdr_A_train[it] = float(torch.mean(hdr_weight(self._t_coords[lo:hi], self.loss.sigma)))
+        return self._hdr_A_train[it]
 
     def _refilled(self) -> None:
         """The HDR / Center scalar A of every batch of the epoch buffers: one batched op over the epoch's coordinates and
@@ -263,7 +298,7 @@ class INRTrainer(ResidentFit):
             it = self._begin_shuffled(epoch, it)
         lo, hi = self._range(it)
         count = self._count(lo, hi)
-        A = self._hdr_A_epoch[it] if self._epoch_buf is not None and self._hdr_A_epoch else self._batch_hdr_A(it, lo, hi)
+        A = self._hdr_A_epoch[it] if self._epoch_buf is not None and self._hdr_A_epoch else self._train_hdr_A(it, lo, hi)
         cfg, lr = self.config, self._lr(epoch)
         # the loss the reference logs includes the penalty VALUE at the parameters the step starts from
         # (train.py:185-192); its gradient is formed inside the Adam kernel.  Every rank holds the same parameters.

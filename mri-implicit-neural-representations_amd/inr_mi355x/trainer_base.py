@@ -27,6 +27,7 @@ def set_default_configs(config: dict) -> dict:
         config["regularization"] = {"type": "none"}
     config.setdefault("undersampling", None)
     config.setdefault("virtual_coils", 0)  # coils.py: K virtual coils instead of the scan's physical ones; 0 = off
+    config.setdefault("trajectory", "none")  # trajectory.py: train on off-grid k-space samples; "none" = off
     return config
 
 
@@ -93,13 +94,20 @@ class ResidentFit(ValidationMixin):
 
     # ---- set-up ----------------------------------------------------------------------------------
     def _init_fit(self, config: dict, shape, device, seed: int, rank: int, world: int, process_group,
-                  graph_steps: bool = False, coil_compression=None) -> dict:
+                  graph_steps: bool = False, coil_compression=None, trajectory_ok: bool = False) -> dict:
         """Defaults, the shuffle settings (which refuse shuffle with graph steps before anything is allocated), the coil
         compression the data came through (config['virtual_coils'] = K needs the record of a K-coil compression and
-        K-coil data, and the other way round: ValueError before anything is allocated) and where the fit runs.  Returns
-        the trainer's own copy of the config."""
+        K-coil data, and the other way round: ValueError before anything is allocated), the trajectory of an off-grid fit
+        (config['trajectory']; drivers that do not pass ``trajectory_ok`` refuse it) and where the fit runs.  Returns the
+        trainer's own copy of the config."""
         config = set_default_configs(dict(config))
         self.config = config
+        from .trajectory import describe, parse_trajectory
+        self.trajectory = parse_trajectory(config["trajectory"])
+        if self.trajectory is not None and not trajectory_ok:
+            raise NotImplementedError(f"config['trajectory'] = {config['trajectory']!r}: off-grid fits run in INRTrainer "
+                                      "(python -m inr_mi355x.train) only")
+        self.trajectory_info = describe(self.trajectory, int(shape[1]), int(shape[2]))
         from .coils import check_virtual_coils
         K = check_virtual_coils(config["virtual_coils"])
         if K and coil_compression is None:
@@ -148,7 +156,15 @@ class ResidentFit(ValidationMixin):
         self.mask = mask.to(torch.uint8).to(self.device).contiguous() if mask is not None else None
         self.per_coil = bool(per_coil)
         self.bs = H * W if self.per_coil else int(self.config["batch_size"])
-        self.steps_per_epoch = math.ceil(self.n / self.bs)
+        # config['trajectory']: the training rows are the C*M off-grid samples of the resident k-space (one inr_nudft
+        # call); batches, counts and the epoch buffers refer to them, validation keeps reading the grid and the full data
+        self.train_coords, self.train_values, self.n_train = self.coords, self.image, self.n
+        if self.trajectory is not None:
+            from .trajectory import positions, sample_kspace
+            values, rows = sample_kspace(self.image_full, self.shape, positions(self.trajectory, H, W))
+            self.train_coords, self.train_values = rows.to(self.device).contiguous(), values.contiguous()
+            self.n_train = self.train_coords.shape[0]
+        self.steps_per_epoch = math.ceil(self.n_train / self.bs)
         self.global_step = 0
         # config['shuffle']: plain batches are views of a second set of resident buffers, refilled by one kernel call per
         # epoch (shuffle.EpochBuffers); per-coil batches stay views of the grid and are visited in a permuted order.
@@ -159,8 +175,11 @@ class ResidentFit(ValidationMixin):
         if self.shuffle and self.per_coil:
             self._coil_order = CoilOrder(self.steps_per_epoch, self.shuffle_seed)
         elif self.shuffle:
-            t = self._epoch_buf = EpochBuffers(self.shuffle_seed, self.bs, self.coords, self.image, dist=dist, mask=self.mask)
+            t = self._epoch_buf = EpochBuffers(self.shuffle_seed, self.bs, self.train_coords, self.train_values, dist=dist,
+                                               mask=self.mask)
         self._t_coords, self._t_image, self._t_dist, self._t_mask = t.coords, t.image, t.dist, t.mask
+        if t is self:
+            self._t_coords, self._t_image = self.train_coords, self.train_values
 
     def _finish_init(self) -> None:
         if "pretrain" in self.config:  # train.py:117-121
@@ -169,8 +188,8 @@ class ResidentFit(ValidationMixin):
 
     # ---- batches ---------------------------------------------------------------------------------
     def _range(self, it: int):
-        """rows [lo, hi) of batch ``it`` (the last batch is short)"""
-        return it * self.bs, min((it + 1) * self.bs, self.n)
+        """rows [lo, hi) of training batch ``it`` (the last batch is short)"""
+        return it * self.bs, min((it + 1) * self.bs, self.n_train)
 
     def _count(self, lo: int, hi: int) -> int:
         """sampled rows of the training batch [lo, hi) (all of them without a mask)"""
@@ -243,8 +262,8 @@ class ResidentFit(ValidationMixin):
         loss_sum = None
         if not self.per_coil:
             loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
-            for it in range(self.steps_per_epoch):
-                lo, hi = self._range(it)
+            for it in range(math.ceil(self.n / self.bs)):  # the grid's batches (the training batches, unless off-grid)
+                lo, hi = it * self.bs, min((it + 1) * self.bs, self.n)
                 A = self._batch_hdr_A(it, lo, hi)  # HDR / tanh take the batch's kcoords (train.py:214-217)
                 loss, _ = self.engine.loss_grad(self.loss, pred[lo:hi], self.image_full[lo:hi], hi - lo, hdr_A=A)
                 loss_sum += loss * self.scale
@@ -262,6 +281,8 @@ class ResidentFit(ValidationMixin):
         rec = {"psnr": psnr_, "ssim": ssim_}
         if self.coil_compression is not None:
             rec["coil_compression"] = self.coil_compression.summary()
+        if self.trajectory_info is not None:
+            rec["trajectory"] = self.trajectory_info
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         return rec

@@ -181,6 +181,8 @@ class ValidationMixin:
         rec = {"epoch": epoch, "test_loss": test_loss, "psnr": psnr, "ssim": ssim}
         if getattr(self, "coil_compression", None) is not None:  # scored against the K virtual-coil targets
             rec["coil_compression"] = self.coil_compression.summary()
+        if getattr(self, "trajectory_info", None) is not None:  # trained on off-grid rows, scored on the grid
+            rec["trajectory"] = self.trajectory_info
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         self.val_history.append(rec)
