@@ -248,7 +248,8 @@ int inr_backward(const inr_plan* plan, const float* params, const float* packed,
 /* Replaces the loss modules + their autograd (train.py:178-182; metrics/losses.py): writes
  * dout [B,2] = d(loss)/d(out) and accumulates the scalar loss into loss_out[0] (device).
  * `mask` (may be NULL) is one byte per row: rows with 0 do not enter the loss (train.py:172-177).
- * `kcoords` [B,3] is only read for INR_LOSS_HDR. */
+ * `kcoords` is never read and may be NULL (the HDR weight's batch mean travels in loss->hdr_A); the argument stays
+ * for the ABI's sake. */
 int inr_loss_grad(const inr_loss_desc* loss, const float* out, const float* gt, const float* kcoords,
                   const uint8_t* mask, int64_t B, float* loss_out, float* dout, void* stream);
 

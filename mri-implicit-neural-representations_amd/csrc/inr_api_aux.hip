@@ -101,7 +101,7 @@ int inr_loss_grad(const inr_loss_desc* loss, const float* out, const float* gt, 
   if (B <= 0) return fail(INR_ERR_INVALID, "inr_loss_grad: B = %lld", (long long)B);
   LossDesc ld;
   to_loss_desc(loss, &ld);
-  hipError_t e = inr::launch_loss_grad(ld, out, gt, kcoords, mask, B, loss_out, dout, (hipStream_t)stream);
+  hipError_t e = inr::launch_loss_grad(ld, out, gt, mask, B, loss_out, dout, (hipStream_t)stream);
   return hip_done(e, "inr_loss_grad");
 }
 
@@ -288,18 +288,10 @@ int inr_coil_stats(const float* coils, int64_t C, int64_t H, int64_t W, double* 
 }
 
 // key schedule of the epoch permutation (inr_mi355x/shuffle.py round_keys is the same text in Python)
-static uint32_t shuffle_mix(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
-
 static inr::ShuffleKeys shuffle_keys(int64_t n, uint64_t seed, uint32_t epoch) {
   const uint32_t gold = 0x9E3779B9u;
   inr::ShuffleKeys sk;
+  using inr::shuffle_mix;
   const uint32_t base = shuffle_mix(shuffle_mix(shuffle_mix((uint32_t)seed + gold) ^ (uint32_t)(seed >> 32)) + epoch);
   for (int r = 0; r < SHUFFLE_ROUNDS; ++r) sk.k[r] = shuffle_mix(base + (uint32_t)(r + 1) * gold);
   int k = 8;  // smallest even k >= 8 with 2^k >= n

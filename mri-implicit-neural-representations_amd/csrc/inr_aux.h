@@ -5,9 +5,10 @@
 
 namespace inr {
 
+// ---- the tail of a training step (inr_params.hip): slab reduction, Adam + re-pack, penalty gradients ----
 struct AdamArgs {
   int do_update;      // 0: pack only
-  int all_real;       // set by the launcher: every layer is LT_REAL (fast scatter path)
+  int all_real;       // set by the launcher: every layer is LT_REAL or LT_GABOR_MU (fast scatter path)
   int has_dead;       // set by the launcher (adam_dead_ranges): some layer has live == 0 ...
   int n_dead;         // ... and its flat entries are these merged ranges [dead_lo, dead_hi); -1: more than fit, walk the layers
   int dead_lo[8], dead_hi[8];
@@ -22,7 +23,6 @@ struct AdamArgs {
   const int* step_dev;  // steps taken so far
   int n_sched;
 };
-
 
 // entries of the layers in `mask` (bit l = L[l]) and the flat gradient entries [lo, hi) are summed over the n2 slabs
 // that FOLLOW the n_blocks slabs of the fused kernel (partial sums of the batch-level weight-gradient GEMM);
@@ -47,12 +47,14 @@ hipError_t launch_adam_shard(const NetDesc& nd, float* params, const float* grad
                              int hi, const AdamArgs& aa, hipStream_t st);
 hipError_t launch_adam_pack(const NetDesc& nd, float* params, const float* grads, float* m1, float* m2,
                             float* packed, const AdamArgs& aa, hipStream_t st);
+// ---- the stand-alone positional encoders (inr_encode.hip) ----
 hipError_t launch_encode_logf(const float* coords, const float* bands, long long B, int nb, float* out,
                               hipStream_t st);
 hipError_t launch_encode_gauss(const float* coords, const float* encB, long long B, int E, float* out,
                                hipStream_t st);
-hipError_t launch_loss_grad(const LossDesc& ld, const float* out, const float* gt, const float* kcoords,
-                            const uint8_t* mask, long long B, float* loss_out, float* dout, hipStream_t st);
+// ---- losses on the network output and their gradients (inr_loss.hip) ----
+hipError_t launch_loss_grad(const LossDesc& ld, const float* out, const float* gt, const uint8_t* mask, long long B,
+                            float* loss_out, float* dout, hipStream_t st);
 hipError_t launch_loss_grad_multi(const LossDesc& ld, const float* outs, const float* gt, const float* dist,
                                   const uint8_t* mask, int NH, long long B, float* loss_out, float* douts,
                                   hipStream_t st);
@@ -129,13 +131,22 @@ hipError_t launch_gray8(const float* img, int H, int W, int take_abs, int has_ra
 long long coil_stats_scratch_doubles(long long C, long long H, long long W);
 hipError_t launch_coil_stats(const float* coils, int C, int H, int W, double* stats, double* scratch, hipStream_t st);
 
-// shuffled epochs (inr_aux.hip): round keys of (seed, epoch) and the half width of the Feistel domain,
-// both made on the host (inr_api_aux.hip shuffle_keys)
+// shuffled epochs (inr_shuffle.hip): round keys of (seed, epoch) and the half width of the Feistel
+// domain, both made on the host (inr_api_aux.hip shuffle_keys)
 #define SHUFFLE_ROUNDS 6
 struct ShuffleKeys {
   unsigned k[SHUFFLE_ROUNDS];
   int h;
 };
+// the mixer of the key schedule (host) and of the round function (device): inr_mi355x/shuffle.py::_mix
+__host__ __device__ inline unsigned shuffle_mix(unsigned x) {
+  x ^= x >> 16;
+  x *= 0x7FEB352Du;
+  x ^= x >> 15;
+  x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
 hipError_t launch_shuffle_epoch(const ShuffleKeys& sk, long long n, long long bs, const float* coords, const float* gt,
                                 const float* dist, const uint8_t* mask, float* coords_out, float* gt_out, float* dist_out,
                                 uint8_t* mask_out, int* batch_counts, long long* order_out, hipStream_t st);

@@ -203,6 +203,7 @@ __global__ __launch_bounds__(BD_THREADS) void band_final_kernel(const double* __
 #pragma unroll
   for (int f = 0; f < BAND_FIELDS; ++f) red[f][t] = v[f];
   __syncthreads();
+  // seven fields, sums and extrema, per step: block_reduce (inr_reduce.h) would take seven trees and their barriers
   for (int s = BD_THREADS / 2; s > 0; s >>= 1) {
     if (t < s) {
 #pragma unroll

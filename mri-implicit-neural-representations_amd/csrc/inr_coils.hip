@@ -19,6 +19,7 @@
 // im += ar xi + ai xr; every input byte is read once, every output byte written once.
 #include <hip/hip_runtime.h>
 #include "inr_aux.h"
+#include "inr_reduce.h"
 
 namespace inr {
 
@@ -135,31 +136,27 @@ __global__ __launch_bounds__(CG_THREADS) void coil_gram_partial_kernel(const flo
   }
 }
 
+struct Cplx {
+  double re, im;
+};
+__device__ inline Cplx operator+(Cplx a, Cplx b) { return {a.re + b.re, a.im + b.im}; }
+
 // one block per pair: G[i][j] and its mirror from part[blocks][P][2]
 __global__ __launch_bounds__(CG_THREADS) void coil_gram_final_kernel(const double* __restrict__ part, const int blocks,
                                                                       const int C, double* __restrict__ gram) {
-  __shared__ double red[2][CG_THREADS];
+  __shared__ Cplx red[CG_THREADS];
   const int P = gridDim.x, q = blockIdx.x, t = threadIdx.x;
-  double r = 0.0, m = 0.0;
+  Cplx v = {0.0, 0.0};
   for (int g = t; g < blocks; g += CG_THREADS) {
     const double* p = part + 2 * ((size_t)g * P + q);
-    r += p[0];
-    m += p[1];
+    v.re += p[0];
+    v.im += p[1];
   }
-  red[0][t] = r;
-  red[1][t] = m;
-  __syncthreads();
-  for (int h = CG_THREADS / 2; h > 0; h >>= 1) {
-    if (t < h) {
-      red[0][t] += red[0][t + h];
-      red[1][t] += red[1][t + h];
-    }
-    __syncthreads();
-  }
+  v = block_reduce_once<CG_THREADS>(v, red, Sum());
   if (t == 0) {
     int i, j;
     pair_of(q, i, j);
-    const double gr = red[0][0], gi = i == j ? 0.0 : red[1][0];
+    const double gr = v.re, gi = i == j ? 0.0 : v.im;
     gram[2 * (i * C + j)] = gr;
     gram[2 * (i * C + j) + 1] = gi;
     if (i != j) {

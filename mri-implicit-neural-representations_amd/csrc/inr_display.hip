@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "inr_aux.h"
+#include "inr_reduce.h"
 
 namespace inr {
 
@@ -31,30 +32,6 @@ inline int dp_blocks(long long n, int cap) {
   return (int)(b < cap ? b : cap);
 }
 
-// fixed-order tree over the 256 lanes of a block; every lane gets the result (`red` may be reused afterwards)
-template <typename T, typename Op>
-__device__ T block_reduce(T v, T* red, Op op) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = DP_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] = op(red[t], red[t + s]);
-    __syncthreads();
-  }
-  const T r = red[0];
-  __syncthreads();
-  return r;
-}
-
-struct SumD {
-  __device__ double operator()(double a, double b) const { return a + b; }
-};
-struct MaxF {
-  __device__ float operator()(float a, float b) const { return fmaxf(a, b); }
-};
-struct MinF {
-  __device__ float operator()(float a, float b) const { return fminf(a, b); }
-};
 // torch.max: a NaN anywhere is the result
 struct NanMaxF {
   __device__ float operator()(float a, float b) const { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
@@ -65,7 +42,7 @@ template <typename Op>
 __device__ float fold_partials(const float* __restrict__ part, int G, float init, float* red, Op op) {
   float v = init;
   for (int i = threadIdx.x; i < G; i += DP_THREADS) v = op(v, part[i]);
-  return block_reduce(v, red, op);
+  return block_reduce<DP_THREADS>(v, red, op);
 }
 
 // ---- k-space display ------------------------------------------------------------------------------------------------
@@ -92,7 +69,7 @@ __global__ __launch_bounds__(DP_THREADS) void display_rss_kernel(const float2* _
     out[p] = r;
     mx = nmax(mx, r);
   }
-  mx = block_reduce(mx, red, nmax);
+  mx = block_reduce<DP_THREADS>(mx, red, nmax);
   if (threadIdx.x == 0) part[blockIdx.x] = mx;
 }
 
@@ -110,7 +87,7 @@ __global__ __launch_bounds__(DP_THREADS) void display_log_kernel(float* __restri
     out[p] = v;
     mx = nmax(mx, v);
   }
-  mx = block_reduce(mx, red, nmax);
+  mx = block_reduce<DP_THREADS>(mx, red, nmax);
   if (threadIdx.x == 0) part_out[blockIdx.x] = mx;
 }
 
@@ -139,8 +116,8 @@ __global__ __launch_bounds__(DP_THREADS) void gray_extrema_kernel(const float* _
       mx = fmaxf(mx, x);
     }
   }
-  mn = block_reduce(mn, red, MinF());
-  mx = block_reduce(mx, red, MaxF());
+  mn = block_reduce<DP_THREADS>(mn, red, MinF());
+  mx = block_reduce<DP_THREADS>(mx, red, MaxF());
   if (threadIdx.x == 0) {
     part[blockIdx.x] = mn;
     part[gridDim.x + blockIdx.x] = mx;
@@ -190,14 +167,14 @@ __global__ __launch_bounds__(DP_THREADS) void coil_sum_kernel(const float2* __re
     s += (double)z.x;
     s += (double)z.y;
   }
-  s = block_reduce(s, red, SumD());
+  s = block_reduce<DP_THREADS>(s, red, Sum());
   if (threadIdx.x == 0) part_sum[(long long)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
 __device__ double coil_mean(const double* __restrict__ part_sum, int G, long long n2, double* red) {
   double s = 0.0;
   for (int i = threadIdx.x; i < G; i += DP_THREADS) s += part_sum[i];
-  return block_reduce(s, red, SumD()) / (2.0 * (double)n2);
+  return block_reduce<DP_THREADS>(s, red, Sum()) / (2.0 * (double)n2);
 }
 
 // part_dev [3][C][G] = sum of squared deviations from the coil's mean, max, min
@@ -220,9 +197,9 @@ __global__ __launch_bounds__(DP_THREADS) void coil_dev_kernel(const float2* __re
     mx = fmaxf(mx, fmaxf(z.x, z.y));
     mn = fminf(mn, fminf(z.x, z.y));
   }
-  m2 = block_reduce(m2, red, SumD());
-  mx = block_reduce(mx, fred, MaxF());
-  mn = block_reduce(mn, fred, MinF());
+  m2 = block_reduce<DP_THREADS>(m2, red, Sum());
+  mx = block_reduce<DP_THREADS>(mx, fred, MaxF());
+  mn = block_reduce<DP_THREADS>(mn, fred, MinF());
   if (threadIdx.x == 0) {
     const long long o = (long long)c * G + blockIdx.x, cg = (long long)C * G;
     part_dev[o] = m2;
@@ -247,9 +224,9 @@ __global__ __launch_bounds__(DP_THREADS) void coil_final_kernel(const double* __
     mx = fmaxf(mx, (float)part_dev[cg + o + i]);
     mn = fminf(mn, (float)part_dev[2 * cg + o + i]);
   }
-  m2 = block_reduce(m2, red, SumD());
-  mx = block_reduce(mx, fred, MaxF());
-  mn = block_reduce(mn, fred, MinF());
+  m2 = block_reduce<DP_THREADS>(m2, red, Sum());
+  mx = block_reduce<DP_THREADS>(mx, fred, MaxF());
+  mn = block_reduce<DP_THREADS>(mn, fred, MinF());
   if (threadIdx.x == 0) {
     stats[4 * c + 0] = mean;
     stats[4 * c + 1] = sqrt(m2 / (2.0 * (double)n2 - 1.0));

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "inr_aux.h"
+#include "inr_reduce.h"
 
 namespace inr {
 
@@ -33,46 +34,6 @@ inline int p1_blocks(long long n) {
 }
 inline int p2_gx(long long W) { return (int)((W - 2 * EV_HALO + EV_TW - 1) / EV_TW); }
 inline int p2_gy(long long H) { return (int)((H - 2 * EV_HALO + EV_TH - 1) / EV_TH); }
-
-// fixed-order tree reductions over the 256 lanes of a block (the caller syncs before reusing `red`)
-__device__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = EV_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] = red[t] + red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
-__device__ float block_max(float v, float* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = EV_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] = fmaxf(red[t], red[t + s]);
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
-
-__device__ float block_min(float v, float* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = EV_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] = fminf(red[t], red[t + s]);
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
 
 // part1 layout: [5][G1] doubles = sse, max_ref, min_ref, max_rec, min_rec of each pass-1 block
 __global__ __launch_bounds__(EV_THREADS) void eval_rss_kernel(const float2* __restrict__ coils, int C, long long n,
@@ -104,11 +65,11 @@ __global__ __launch_bounds__(EV_THREADS) void eval_rss_kernel(const float2* __re
   }
   if (part1 == nullptr) return;  // RSS only (uniform over the grid: no lane leaves a barrier below)
   const int G = gridDim.x, b = blockIdx.x;
-  sse = block_sum(sse, dred);
-  mxx = block_max(mxx, fred);
-  mnx = block_min(mnx, fred);
-  mxr = block_max(mxr, fred);
-  mnr = block_min(mnr, fred);
+  sse = block_reduce<EV_THREADS>(sse, dred, Sum());
+  mxx = block_reduce<EV_THREADS>(mxx, fred, MaxF());
+  mnx = block_reduce<EV_THREADS>(mnx, fred, MinF());
+  mxr = block_reduce<EV_THREADS>(mxr, fred, MaxF());
+  mnr = block_reduce<EV_THREADS>(mnr, fred, MinF());
   if (threadIdx.x == 0) {
     part1[0 * G + b] = sse;
     part1[1 * G + b] = mxx;
@@ -127,10 +88,10 @@ __device__ void fold_extrema(const double* __restrict__ part1, int G1, float* fr
     c = fmaxf(c, (float)part1[3 * G1 + i]);
     d = fminf(d, (float)part1[4 * G1 + i]);
   }
-  ext[0] = block_max(a, fred);
-  ext[1] = block_min(b, fred);
-  ext[2] = block_max(c, fred);
-  ext[3] = block_min(d, fred);
+  ext[0] = block_reduce<EV_THREADS>(a, fred, MaxF());
+  ext[1] = block_reduce<EV_THREADS>(b, fred, MinF());
+  ext[2] = block_reduce<EV_THREADS>(c, fred, MaxF());
+  ext[3] = block_reduce<EV_THREADS>(d, fred, MinF());
 }
 
 // np.maximum(x.max(), xhat.max()) - np.minimum(x.min(), xhat.min()) on float32 scalars
@@ -205,7 +166,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_ssim_kernel(const float* __re
     const double B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
     acc += (A1 * A2) / (B1 * B2);
   }
-  acc = block_sum(acc, dred);
+  acc = block_reduce<EV_THREADS>(acc, dred, Sum());
   if (tid == 0) part2[blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
 
@@ -218,8 +179,8 @@ __global__ __launch_bounds__(EV_THREADS) void eval_finalize_kernel(const double*
   double sse = 0.0, ss = 0.0;
   for (int i = threadIdx.x; i < G1; i += EV_THREADS) sse += part1[i];
   for (int i = threadIdx.x; i < G2; i += EV_THREADS) ss += part2[i];
-  sse = block_sum(sse, dred);
-  ss = block_sum(ss, dred);
+  sse = block_reduce<EV_THREADS>(sse, dred, Sum());
+  ss = block_reduce<EV_THREADS>(ss, dred, Sum());
   float ext[4];
   fold_extrema(part1, G1, fred, ext);
   if (threadIdx.x == 0) {

@@ -1,11 +1,11 @@
-// inr_aux.hip -- HBM-bound helper kernels of the INR engine (gfx950): slab reduction,
-// Adam + weight re-packing, gauss encoder, pointwise losses.  All are coalesced streaming
-// kernels; none reshapes its work into a GEMM.
+// inr_params.hip -- the tail of every training step (gfx950): slab reduction, Adam fused with the re-pack of the weight
+// images, penalty gradients.  Coalesced streaming kernels, HBM-bound; every sum runs in a fixed order.
 #include <algorithm>
 #include <cstdlib>
 #include "inr_device.h"
 #include "inr_aux.h"
 #include "inr_w2.h"
+#include "inr_reduce.h"
 
 namespace inr {
 
@@ -70,21 +70,15 @@ __device__ __forceinline__ bool locate(const NetDesc& nd, int i, int& l, Virtual
 __device__ __forceinline__ void loss_words_sum(const float* __restrict__ slabs, int n, size_t stride, int off,
                                                float* __restrict__ loss_out) {
   __shared__ float red[256];
-  const int t = threadIdx.x;
   float s = 0.f;
-  for (int b = t; b < n; b += 256) s += slabs[(size_t)b * stride + off];
-  red[t] = s;
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (t < w) red[t] += red[t + w];
-    __syncthreads();
-  }
-  if (t == 0) loss_out[0] = red[0];
+  for (int b = threadIdx.x; b < n; b += 256) s += slabs[(size_t)b * stride + off];
+  s = block_reduce_once<256>(s, red, Sum());
+  if (threadIdx.x == 0) loss_out[0] = s;
 }
 
 // ---------------------------------------------------------------------------------------------
 // grads[i] = sum over blocks (in block order: deterministic) of the slab entries that flat
-// element i owns; the loss word is summed by thread 0.
+// element i owns; the loss words are summed by the grid's extra last workgroup (loss_words_sum).
 // ---------------------------------------------------------------------------------------------
 // sum of n slab entries `stride` floats apart, 16 independent loads in flight, added in slab order
 __device__ __forceinline__ float slab_sum(const float* __restrict__ p, size_t stride, int n) {
@@ -149,15 +143,13 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const NetDesc nd, con
 // Fast path when a slab has the flat-parameter layout (every layer LT_REAL).  A workgroup owns 256
 // consecutive gradient entries (64 lanes x 16 B); its four waves each sum a contiguous quarter of
 // the slabs (8 independent 16-byte loads in flight per lane) and the quarters are combined through
-// LDS in wave order -- a fixed summation tree, so results are bitwise reproducible.
-__global__ __launch_bounds__(256) void reduce_slabs_real_kernel(const float* __restrict__ slabs_all, int n_blocks_all,
-                                                                int slab_floats, int P, int loss_off,
-                                                                float* __restrict__ grads,
-                                                                float* __restrict__ loss_out, SlabSplit split) {
-  __shared__ f32x4 part[4][64];
+// LDS in wave order -- a fixed summation tree, so results are bitwise reproducible.  Returns, in every
+// wave, the sum of the lane's entries i4 .. i4 + 3 (i4 = 4 * (64 * block + lane)); `part` is the caller's.
+// split.lo / split.hi (lo3 / hi3) are multiples of 4 (slabs_flat): a lane's four entries share a slab set.
+__device__ __forceinline__ f32x4 flat_slab_sum(const float* __restrict__ slabs_all, int n_blocks_all, int slab_floats,
+                                               int P, const SlabSplit& split, f32x4 (*part)[64]) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int i4 = (blockIdx.x * 64 + lane) * 4;
-  // split.lo / split.hi are multiples of 4 (checked by the launcher): a lane's four entries share a slab set
   const bool second = split.n2 > 0 && i4 >= split.lo && i4 < split.hi;
   const float* __restrict__ slabs = second ? slabs_all + (size_t)n_blocks_all * slab_floats : slabs_all;
   const int n_blocks = second ? (split.n3 > 0 && i4 >= split.lo3 && i4 < split.hi3 ? split.n3 : split.n2) : n_blocks_all;
@@ -177,10 +169,19 @@ __global__ __launch_bounds__(256) void reduce_slabs_real_kernel(const float* __r
   }
   part[w][lane] = s;
   __syncthreads();
-  if (w == 0 && i4 < P) {
-    const f32x4 t = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+  return ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+}
+
+// the flat-layout reduction: flat_slab_sum, wave 0 stores the lane's four entries
+__global__ __launch_bounds__(256) void reduce_slabs_real_kernel(const float* __restrict__ slabs_all, int n_blocks_all,
+                                                                int slab_floats, int P, int loss_off,
+                                                                float* __restrict__ grads,
+                                                                float* __restrict__ loss_out, SlabSplit split) {
+  __shared__ f32x4 part[4][64];
+  const int i4 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+  const f32x4 t = flat_slab_sum(slabs_all, n_blocks_all, slab_floats, P, split, part);
+  if (threadIdx.x < 64 && i4 < P)
     for (int j = 0; j < 4 && i4 + j < P; ++j) grads[i4 + j] = t[j];
-  }
   if (loss_out != nullptr && blockIdx.x == gridDim.x - 1) loss_words_sum(slabs_all, n_blocks_all, (size_t)slab_floats, loss_off, loss_out);
 }
 
@@ -225,20 +226,33 @@ __global__ __launch_bounds__(64) void gabor_m2_kernel(const NetDesc nd, const fl
   if (lane == 0) packed[L.pbias_off + nd.NB * 32 + j] = s;
 }
 
+// every layer is LT_REAL (with_mu: or a Gabor centre layer, whose entries are real too)
+static bool layers_real(const NetDesc& nd, bool with_mu) {
+  for (int l = 0; l < nd.ND; ++l)
+    if (nd.L[l].ltype != LT_REAL && !(with_mu && nd.L[l].ltype == LT_GABOR_MU)) return false;
+  return true;
+}
+
+// slab layout == flat layout for this split: real layers at their flat offsets (not the case for MFN: L[] order != flat
+// order; slab_floats % 64 == 0 keeps every slab 16-byte aligned), no per-layer slab set, and the bounds of the slab sets
+// in use at multiples of 4 (a lane's four entries share a slab set)
+static bool slabs_flat(const NetDesc& nd, const SlabSplit& split) {
+  for (int l = 0; l < nd.ND; ++l)
+    if (nd.L[l].gw_off != nd.L[l].w_off) return false;
+  return layers_real(nd, false) && split.mask == 0 && ((split.lo | split.hi) & 3) == 0 &&
+         (split.n3 == 0 || ((split.lo3 | split.hi3) & 3) == 0);
+}
+
 hipError_t launch_reduce_slabs(const NetDesc& nd, const float* slabs, int n_blocks, float* grads, float* loss_out,
                                const float* params, const float* packed, hipStream_t st, SlabSplit split) {
-  bool all_real = true;  // ... and slab layout == flat layout (not the case for MFN: L[] order != flat order)
-  for (int l = 0; l < nd.ND; ++l) all_real = all_real && nd.L[l].ltype == LT_REAL && nd.L[l].gw_off == nd.L[l].w_off;
-  if (split.n3 > 0 && !(all_real && ((split.lo | split.hi | split.lo3 | split.hi3) & 3) == 0 && split.mask == 0))
-    return hipErrorInvalidValue;  // a third slab count is the flat-layout reduction's only
-  if (all_real && ((split.lo | split.hi) & 3) == 0 && split.mask == 0) {  // slab offsets == flat offsets; slab_floats % 64 == 0 keeps every slab 16-byte aligned
-    const int grid = (nd.P + 255) / 256;
+  const bool flat = slabs_flat(nd, split);
+  if (split.n3 > 0 && !flat) return hipErrorInvalidValue;  // a third slab count is the flat-layout reduction's only
+  const int grid = (nd.P + 255) / 256;
+  if (flat)
     hipLaunchKernelGGL(reduce_slabs_real_kernel, dim3(grid + 1), dim3(256), 0, st, slabs, n_blocks, nd.slab_floats, nd.P,
                        nd.slab_loss_off, grads, loss_out, split);
-  } else {
-    const int grid = (nd.P + 255) / 256;
+  else
     hipLaunchKernelGGL(reduce_slabs_kernel, dim3(grid + 1), dim3(256), 0, st, nd, slabs, n_blocks, grads, loss_out, split);
-  }
   if (nd.gabor)
     hipLaunchKernelGGL(gabor_finish_kernel, dim3(nd.L[nd.mu0].M, nd.mfn_n + 1), dim3(64), 0, st, nd, slabs, n_blocks,
                        params, packed, grads);
@@ -409,8 +423,8 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(const NetDesc nd, float*
 }
 
 // reduce_slabs_real_kernel + adam_pack_kernel in one launch (single-rank steps: nothing sits between the reduction and
-// the update).  Same summation tree, same update arithmetic: bit-identical to the two launches; the gradient is still
-// written (callers read it).  The four waves of a workgroup each take one of a lane's four entries for the update.
+// the update).  Same summation (flat_slab_sum), same update arithmetic: bit-identical to the two launches; the gradient
+// is still written (callers read it).  The four waves of a workgroup each take one of a lane's four entries for the update.
 __global__ __launch_bounds__(256) void reduce_adam_real_kernel(const NetDesc nd, const float* __restrict__ slabs_all,
                                                                int n_blocks_all, float* __restrict__ grads,
                                                                float* __restrict__ loss_out, SlabSplit split,
@@ -418,36 +432,16 @@ __global__ __launch_bounds__(256) void reduce_adam_real_kernel(const NetDesc nd,
                                                                float* __restrict__ m2, float* __restrict__ packed,
                                                                AdamArgs aa) {
   __shared__ f32x4 part[4][64];
-  const int slab_floats = nd.slab_floats, P = nd.P;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i4 = (blockIdx.x * 64 + lane) * 4;
-  const bool second = split.n2 > 0 && i4 >= split.lo && i4 < split.hi;
-  const float* __restrict__ slabs = second ? slabs_all + (size_t)n_blocks_all * slab_floats : slabs_all;
-  const int n_blocks = second ? (split.n3 > 0 && i4 >= split.lo3 && i4 < split.hi3 ? split.n3 : split.n2) : n_blocks_all;
-  const int per = (n_blocks + 3) / 4;
-  const int b0 = w * per, b1 = (b0 + per < n_blocks) ? b0 + per : n_blocks;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  const int P = nd.P, w = threadIdx.x >> 6;
+  const int i4 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+  const f32x4 t = flat_slab_sum(slabs_all, n_blocks_all, nd.slab_floats, P, split, part);
   if (i4 < P) {
-    int b = b0;
-    for (; b + 8 <= b1; b += 8) {
-      f32x4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4*>(slabs + (size_t)(b + u) * slab_floats + i4);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; b < b1; ++b) s += *reinterpret_cast<const f32x4*>(slabs + (size_t)b * slab_floats + i4);
-  }
-  part[w][lane] = s;
-  __syncthreads();
-  if (i4 < P) {
-    const f32x4 t = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
     if (w == 0)
       for (int j = 0; j < 4 && i4 + j < P; ++j) grads[i4 + j] = t[j];
     if (i4 + w < P) adam_pack_entry(nd, i4 + w, t[w], params, m1, m2, packed, aa);
   }
   if (loss_out != nullptr && blockIdx.x == gridDim.x - 1)
-    loss_words_sum(slabs_all, n_blocks_all, (size_t)slab_floats, nd.slab_loss_off, loss_out);
+    loss_words_sum(slabs_all, n_blocks_all, (size_t)nd.slab_floats, nd.slab_loss_off, loss_out);
 }
 
 // Sharded data-parallel update: the entries [lo, hi) of the flat vector, gradient = this rank's chunk of the
@@ -590,8 +584,7 @@ static void adam_dead_ranges(const NetDesc& nd, AdamArgs& aa) {
 hipError_t launch_adam_pack(const NetDesc& nd, float* params, const float* grads, float* m1, float* m2,
                             float* packed, const AdamArgs& aa_in, hipStream_t st) {
   AdamArgs aa = aa_in;
-  aa.all_real = 1;
-  for (int l = 0; l < nd.ND; ++l) aa.all_real = aa.all_real && (nd.L[l].ltype == LT_REAL || nd.L[l].ltype == LT_GABOR_MU);
+  aa.all_real = layers_real(nd, true);
   adam_dead_ranges(nd, aa);
   // large plain-layer networks (BASELINE config 4: 4.47 M entries): the update elementwise, then the images in image order
   // (INR_PACK_BY_IMAGE=0 / 1 forces the choice where both exist: the tests hold one against the other)
@@ -642,9 +635,7 @@ hipError_t launch_adam_shard(const NetDesc& nd, float* params, const float* grad
 hipError_t launch_reduce_slabs_adam(const NetDesc& nd, const float* slabs, int n_blocks, float* grads, float* loss_out,
                                     float* params, float* m1, float* m2, float* packed, const AdamArgs& aa_in,
                                     hipStream_t st, SlabSplit split) {
-  bool flat = ((split.lo | split.hi | split.lo3 | split.hi3) & 3) == 0 && split.mask == 0 && !nd.gabor;
-  for (int l = 0; l < nd.ND; ++l) flat = flat && nd.L[l].ltype == LT_REAL && nd.L[l].gw_off == nd.L[l].w_off;
-  if (!flat) {
+  if (!(slabs_flat(nd, split) && ((split.lo3 | split.hi3) & 3) == 0 && !nd.gabor)) {
     hipError_t e = launch_reduce_slabs(nd, slabs, n_blocks, grads, loss_out, params, packed, st, split);
     if (e != hipSuccess) return e;
     return launch_adam_pack(nd, params, grads, m1, m2, packed, aa_in, st);
@@ -655,460 +646,6 @@ hipError_t launch_reduce_slabs_adam(const NetDesc& nd, const float* slabs, int n
   const int grid = (nd.P + 255) / 256;
   hipLaunchKernelGGL(reduce_adam_real_kernel, dim3(grid + 1), dim3(256), 0, st, nd, slabs, n_blocks, grads, loss_out, split,
                      params, m1, m2, packed, aa);
-  return hipGetLastError();
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Positional_Encoder.embedding 'gauss' (networks.py:30-33): out[r] = [sin(p) | cos(p)],
-// p = (2*pi*x_r) @ B^T.  One thread per (row, frequency); writes are coalesced along s.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void encode_gauss_kernel(const float* __restrict__ coords,
-                                                           const float* __restrict__ encB, long long B, int E,
-                                                           float* __restrict__ out) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= B * E) return;
-  const long long r = idx / E;
-  const int s = (int)(idx - r * E);
-  const float two_pi = 6.283185307179586f;
-  const float x0 = two_pi * coords[3 * r + 0], x1 = two_pi * coords[3 * r + 1], x2 = two_pi * coords[3 * r + 2];
-  const float ph = fmaf(x2, encB[3 * s + 2], fmaf(x1, encB[3 * s + 1], x0 * encB[3 * s + 0]));
-  float sn, cs;
-  sincosf(ph, &sn, &cs);
-  out[r * 2 * E + s] = sn;
-  out[r * 2 * E + E + s] = cs;
-}
-
-// Positional_Encoder.embedding 'LogF' (networks.py:16,24-29): per axis a = 0..2,
-// [sin(2 pi x_a b) | cos(2 pi x_a b)] over the nb log-spaced bands b, concatenated: out [B, 6 nb].
-__global__ __launch_bounds__(256) void encode_logf_kernel(const float* __restrict__ coords,
-                                                          const float* __restrict__ bands, long long B, int nb,
-                                                          float* __restrict__ out) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= B * 3 * nb) return;
-  const long long r = idx / (3 * nb);
-  const int t = (int)(idx - r * 3 * nb), a = t / nb, s = t - a * nb;
-  const float ph = (6.283185307179586f * coords[3 * r + a]) * bands[s];  // (2 pi x_a) @ B^T with K = 1
-  float sn, cs;
-  sincosf(ph, &sn, &cs);
-  float* o = out + r * 6 * nb + a * 2 * nb;
-  o[s] = sn;
-  o[nb + s] = cs;
-}
-
-hipError_t launch_encode_logf(const float* coords, const float* bands, long long B, int nb, float* out,
-                              hipStream_t st) {
-  const long long n = B * 3 * nb;
-  hipLaunchKernelGGL(encode_logf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, coords, bands, B, nb, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_encode_gauss(const float* coords, const float* encB, long long B, int E, float* out,
-                               hipStream_t st) {
-  const long long n = B * E;
-  const int grid = (int)((n + 255) / 256);
-  hipLaunchKernelGGL(encode_gauss_kernel, dim3(grid), dim3(256), 0, st, coords, encB, B, E, out);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// Pointwise losses + their gradient w.r.t. the network output (tier 1; metrics/losses.py and
-// train.py:172-182).  64 blocks write ordered partial sums to loss_out[1..64]; a single thread
-// then folds them into loss_out[0] (deterministic).
-// ---------------------------------------------------------------------------------------------
-#define LOSS_BLOCKS 64
-
-__global__ __launch_bounds__(256) void loss_grad_kernel(const LossDesc ld, const float* __restrict__ out,
-                                                        const float* __restrict__ gt,
-                                                        const uint8_t* __restrict__ mask, long long B,
-                                                        float* __restrict__ loss_out, float* __restrict__ dout) {
-  __shared__ float red[256];
-  // contiguous row range per block, rows visited in order by a fixed thread -> fixed sum order
-  const long long per = (B + LOSS_BLOCKS - 1) / LOSS_BLOCKS;
-  const long long lo = (long long)blockIdx.x * per;
-  const long long hi = lo + per < B ? lo + per : B;
-  float acc = 0.f;
-  for (long long r = lo + threadIdx.x; r < hi; r += 256) {
-    float g[2] = {0.f, 0.f};
-    if (mask == nullptr || mask[r] != 0) {
-      const float y[2] = {out[2 * r], out[2 * r + 1]};
-      const float t[2] = {gt[2 * r], gt[2 * r + 1]};
-      acc += loss_row(ld, 2, y, t, g);
-    }
-    dout[2 * r] = g[0];
-    dout[2 * r + 1] = g[1];
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_out[1 + blockIdx.x] = red[0];
-}
-
-__global__ void loss_fold_kernel(float* loss_out) {
-  float s = 0.f;
-  for (int b = 0; b < LOSS_BLOCKS; ++b) s += loss_out[1 + b];
-  loss_out[0] = s;
-}
-
-hipError_t launch_loss_grad(const LossDesc& ld_in, const float* out, const float* gt, const float* kcoords,
-                            const uint8_t* mask, long long B, float* loss_out, float* dout, hipStream_t st) {
-  LossDesc ld = ld_in;
-  hipLaunchKernelGGL(loss_grad_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, st, ld, out, gt, mask, B, loss_out, dout);
-  hipLaunchKernelGGL(loss_fold_kernel, dim3(1), dim3(1), 0, st, loss_out);
-  (void)kcoords;
-  return hipGetLastError();
-}
-
-// Multi-head version (tier 1 of the multiscale loop, train_kspace_multiscale.py:176-195): outs / douts [NH][B][2],
-// pointwise terms on sampled rows, ConsistencyLoss on every row (mfn_loss_row).
-__global__ __launch_bounds__(256) void loss_grad_multi_kernel(const LossDesc ld, const float* __restrict__ outs,
-                                                              const float* __restrict__ gt,
-                                                              const float* __restrict__ dist,
-                                                              const uint8_t* __restrict__ mask, int NH, long long B,
-                                                              float* __restrict__ loss_out, float* __restrict__ douts) {
-  __shared__ float red[256];
-  const long long per = (B + LOSS_BLOCKS - 1) / LOSS_BLOCKS;
-  const long long lo = (long long)blockIdx.x * per;
-  const long long hi = lo + per < B ? lo + per : B;
-  float acc = 0.f;
-  for (long long r = lo + threadIdx.x; r < hi; r += 256) {
-    float y[INR_MAX_HEADS][4], g[INR_MAX_HEADS][4];
-#pragma unroll
-    for (int k = 0; k < INR_MAX_HEADS; ++k)
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        y[k][o] = (k < NH && o < 2) ? outs[((size_t)k * B + r) * 2 + o] : 0.f;
-        g[k][o] = 0.f;
-      }
-    const float t[4] = {gt[2 * r], gt[2 * r + 1], 0.f, 0.f};
-    acc += mfn_loss_row(ld, NH, 2, y, t, dist != nullptr ? dist[r] : 0.f, g, mask == nullptr || mask[r] != 0);
-#pragma unroll
-    for (int k = 0; k < INR_MAX_HEADS; ++k)
-      if (k < NH) {
-        douts[((size_t)k * B + r) * 2] = g[k][0];
-        douts[((size_t)k * B + r) * 2 + 1] = g[k][1];
-      }
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_out[1 + blockIdx.x] = red[0];
-}
-
-hipError_t launch_loss_grad_multi(const LossDesc& ld_in, const float* outs, const float* gt, const float* dist,
-                                  const uint8_t* mask, int NH, long long B, float* loss_out, float* douts,
-                                  hipStream_t st) {
-  LossDesc ld = ld_in;
-  hipLaunchKernelGGL(loss_grad_multi_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, st, ld, outs, gt, dist, mask, NH, B,
-                     loss_out, douts);
-  hipLaunchKernelGGL(loss_fold_kernel, dim3(1), dim3(1), 0, st, loss_out);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// Total-variation regulariser on one coil's predicted k-space image (metrics/losses.py tv_loss;
-// train.py:172-175):  w * ( mean|img[:, :-1] - img[:, 1:]| + mean|img[:-1] - img[1:]| ) over
-// img [H][W][2].  `out` holds rows [y0, y0 + R) of the image; the first R_own rows are this
-// caller's (a trailing halo row lets the vertical pair (y0+R_own-1, y0+R_own) be evaluated by the
-// rank that owns its upper row).  Gather form: every element sums the sign terms of the <= 4 pairs
-// it belongs to, so there are no atomics and the result is deterministic.  Adds into dout and
-// loss_out[0].
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sgn(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
-
-__global__ __launch_bounds__(256) void tv_grad_kernel(const float* __restrict__ out, long long R, long long R_own,
-                                                      long long W, float cw, float ch,
-                                                      float* __restrict__ loss_out, float* __restrict__ dout) {
-  __shared__ float red[256];
-  const long long n = R * W * 2;
-  const long long per = (n + LOSS_BLOCKS - 1) / LOSS_BLOCKS;
-  const long long lo = (long long)blockIdx.x * per;
-  const long long hi = lo + per < n ? lo + per : n;
-  const long long rs = W * 2;  // row stride
-  float acc = 0.f;
-  for (long long i = lo + threadIdx.x; i < hi; i += 256) {
-    const long long r = i / rs;
-    const long long x = (i - r * rs) >> 1;
-    const float v = out[i];
-    float g = 0.f;
-    if (r < R_own) {
-      if (x + 1 < W) {
-        const float d = v - out[i + 2];
-        acc += fabsf(d) * cw;
-        g += cw * sgn(d);
-      }
-      if (x > 0) g -= cw * sgn(out[i - 2] - v);
-      if (r + 1 < R) {
-        const float d = v - out[i + rs];
-        acc += fabsf(d) * ch;
-        g += ch * sgn(d);
-      }
-    }
-    if (r > 0 && r - 1 < R_own) g -= ch * sgn(out[i - rs] - v);
-    dout[i] += g;
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_out[1 + blockIdx.x] = red[0];
-}
-
-__global__ void loss_fold_add_kernel(float* loss_out) {
-  float s = 0.f;
-  for (int b = 0; b < LOSS_BLOCKS; ++b) s += loss_out[1 + b];
-  loss_out[0] += s;
-}
-
-hipError_t launch_tv_grad(const float* out, long long R, long long R_own, long long W, float cw, float ch,
-                          float* loss_out, float* dout, hipStream_t st) {
-  hipLaunchKernelGGL(tv_grad_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, st, out, R, R_own, W, cw, ch, loss_out, dout);
-  hipLaunchKernelGGL(loss_fold_add_kernel, dim3(1), dim3(1), 0, st, loss_out);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// inr_loss_grad + inr_tv_grad of one coil's rows in ONE pass (the per-coil step of train.py:163-189 with use_tv): a thread
-// per coordinate, 256 workgroups over the R x W grid (the two kernels above are 64 workgroups each for 6 MB of traffic:
-// 18 + 40 us of a 0.58 ms step, plus two single-thread folds and the copy that zeroed the halo rows' mask).  Pointwise loss
-// on the sampled rows the caller OWNS (r < R_own: a data-parallel rank's halo row below its slab stays with its owner),
-// TV as tv_grad_kernel.  dout is WRITTEN (not added to).  Partial sums: loss_out[1 + block], fixed order within a thread
-// (its coordinates in order), fixed tree within a block; loss_tv_fold_kernel sums the 256 partials by a fixed tree.
-// ---------------------------------------------------------------------------------------------
-#define LOSS_TV_BLOCKS 256
-
-__global__ __launch_bounds__(256) void loss_tv_grad_kernel(const LossDesc ld, const float* __restrict__ out,
-                                                           const float* __restrict__ gt, const uint8_t* __restrict__ mask,
-                                                           long long R, long long R_own, long long W, float cw, float ch,
-                                                           float* __restrict__ loss_out, float* __restrict__ dout) {
-  __shared__ float red[256];
-  const long long n = R * W;
-  const long long per = (n + LOSS_TV_BLOCKS - 1) / LOSS_TV_BLOCKS;
-  const long long lo = (long long)blockIdx.x * per;
-  const long long hi = lo + per < n ? lo + per : n;
-  const float2* __restrict__ o2 = reinterpret_cast<const float2*>(out);
-  float acc = 0.f;
-  for (long long c = lo + threadIdx.x; c < hi; c += 256) {
-    const long long r = c / W, x = c - r * W;
-    const float2 v = o2[c];
-    float g[2] = {0.f, 0.f};
-    if (r < R_own && (mask == nullptr || mask[c] != 0)) {
-      const float y[2] = {v.x, v.y};
-      const float2 tt = reinterpret_cast<const float2*>(gt)[c];
-      const float t[2] = {tt.x, tt.y};
-      acc += loss_row(ld, 2, y, t, g);
-    }
-    if (r < R_own) {
-      if (x + 1 < W) {
-        const float2 e = o2[c + 1];
-        const float d0 = v.x - e.x, d1 = v.y - e.y;
-        acc += (fabsf(d0) + fabsf(d1)) * cw;
-        g[0] += cw * sgn(d0);
-        g[1] += cw * sgn(d1);
-      }
-      if (x > 0) {
-        const float2 e = o2[c - 1];
-        g[0] -= cw * sgn(e.x - v.x);
-        g[1] -= cw * sgn(e.y - v.y);
-      }
-      if (r + 1 < R) {
-        const float2 e = o2[c + W];
-        const float d0 = v.x - e.x, d1 = v.y - e.y;
-        acc += (fabsf(d0) + fabsf(d1)) * ch;
-        g[0] += ch * sgn(d0);
-        g[1] += ch * sgn(d1);
-      }
-    }
-    if (r > 0 && r - 1 < R_own) {
-      const float2 e = o2[c - W];
-      g[0] -= ch * sgn(e.x - v.x);
-      g[1] -= ch * sgn(e.y - v.y);
-    }
-    reinterpret_cast<float2*>(dout)[c] = float2{g[0], g[1]};
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_out[1 + blockIdx.x] = red[0];
-}
-
-__global__ __launch_bounds__(256) void loss_tv_fold_kernel(float* loss_out) {
-  __shared__ float red[256];
-  red[threadIdx.x] = loss_out[1 + threadIdx.x];
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_out[0] = red[0];
-}
-
-hipError_t launch_loss_tv_grad(const LossDesc& ld_in, const float* out, const float* gt, const uint8_t* mask, long long R,
-                               long long R_own, long long W, float cw, float ch, float* loss_out, float* dout,
-                               hipStream_t st) {
-  LossDesc ld = ld_in;
-  hipLaunchKernelGGL(loss_tv_grad_kernel, dim3(LOSS_TV_BLOCKS), dim3(256), 0, st, ld, out, gt, mask, R, R_own, W, cw, ch,
-                     loss_out, dout);
-  hipLaunchKernelGGL(loss_tv_fold_kernel, dim3(1), dim3(256), 0, st, loss_out);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// CenterLoss, random-pair term of one band (metrics/losses.py:175-199): for pairs p < n of rows (a_p, b_p) -- drawn by the
-// caller with torch.randperm exactly as the reference draws them -- r_p = (|t_a| - |t_b|) - (|y_a| - |y_b|), the band adds
-// w * sum_p r_p^2 (w = 0.1 / n) to the loss and  -2 w r_p y_a / |y_a|  to dout[a_p],  +2 w r_p y_b / |y_b|  to dout[b_p].
-// The a rows of a band are distinct, so are the b rows, and no row is in both (they come from disjoint radial masks): plain
-// read-modify-write, no atomics; bands are separate launches on one stream.  Rows outside [0, B) are ignored.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void center_pairs_kernel(const float* __restrict__ out, const float* __restrict__ gt,
-                                                           const long long* __restrict__ ia, const long long* __restrict__ ib,
-                                                           long long n, long long B, float w, float* __restrict__ loss_out,
-                                                           float* __restrict__ dout) {
-  __shared__ float red[256];
-  const long long per = (n + LOSS_BLOCKS - 1) / LOSS_BLOCKS;
-  const long long lo = (long long)blockIdx.x * per;
-  const long long hi = lo + per < n ? lo + per : n;
-  float acc = 0.f;
-  for (long long p = lo + threadIdx.x; p < hi; p += 256) {
-    const long long a = ia[p], b = ib[p];
-    if (a < 0 || a >= B || b < 0 || b >= B) continue;
-    const float yar = out[2 * a], yai = out[2 * a + 1], ybr = out[2 * b], ybi = out[2 * b + 1];
-    const float na = sqrtf(yar * yar + yai * yai), nb = sqrtf(ybr * ybr + ybi * ybi);
-    const float ta = sqrtf(gt[2 * a] * gt[2 * a] + gt[2 * a + 1] * gt[2 * a + 1]);
-    const float tb = sqrtf(gt[2 * b] * gt[2 * b] + gt[2 * b + 1] * gt[2 * b + 1]);
-    const float r = (ta - tb) - (na - nb);
-    acc += w * r * r;
-    const float ca = na > 0.f ? -2.f * w * r / na : 0.f;  // d|y|/dy = y / |y| (0 at the origin, as torch.abs)
-    const float cb = nb > 0.f ? 2.f * w * r / nb : 0.f;
-    dout[2 * a] += ca * yar;
-    dout[2 * a + 1] += ca * yai;
-    dout[2 * b] += cb * ybr;
-    dout[2 * b + 1] += cb * ybi;
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_out[1 + blockIdx.x] = red[0];
-}
-
-hipError_t launch_center_pairs(const float* out, const float* gt, const long long* ia, const long long* ib, long long n,
-                               long long B, float w, float* loss_out, float* dout, hipStream_t st) {
-  hipLaunchKernelGGL(center_pairs_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, st, out, gt, ia, ib, n, B, w, loss_out, dout);
-  hipLaunchKernelGGL(loss_fold_add_kernel, dim3(1), dim3(1), 0, st, loss_out);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// Shuffled epochs: output row j of the epoch is input row order(j), a keyed bijection of [0, 2^(2h))
-// -- a balanced Feistel network of SHUFFLE_ROUNDS rounds over two h-bit halves, round function
-// (MIX(R ^ K_r) >> 16) & (2^h - 1) -- walked until it lands in [0, n).  32-bit integer arithmetic only, so
-// inr_mi355x/shuffle.py::epoch_order gives the same integers.  One thread per output row: the writes of a wave are
-// contiguous (12 / 8 / 4 / 1 / 8 bytes per lane), the reads are single rows anywhere in the source.
-// batch_counts (zeroed by the launcher on the same stream) takes one integer atomic per wave whose 64 rows lie in one
-// batch, one per lane in the wave that straddles a batch end: integer sums, exact in any order.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned shuffle_mix(unsigned x) {
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
-
-__device__ __forceinline__ unsigned shuffle_order(const ShuffleKeys& sk, unsigned j, unsigned n) {
-  const unsigned half = (1u << sk.h) - 1u;
-  unsigned x = j;
-  do {
-    unsigned l = x >> sk.h, r = x & half;
-#pragma unroll
-    for (int i = 0; i < SHUFFLE_ROUNDS; ++i) {
-      const unsigned t = l ^ ((shuffle_mix(r ^ sk.k[i]) >> 16) & half);
-      l = r;
-      r = t;
-    }
-    x = (l << sk.h) | r;
-  } while (x >= n);
-  return x;
-}
-
-__global__ __launch_bounds__(256) void shuffle_epoch_kernel(const ShuffleKeys sk, unsigned n, unsigned bs,
-                                                            const float* __restrict__ coords,
-                                                            const float* __restrict__ gt,
-                                                            const float* __restrict__ dist,
-                                                            const uint8_t* __restrict__ mask,
-                                                            float* __restrict__ coords_out, float* __restrict__ gt_out,
-                                                            float* __restrict__ dist_out, uint8_t* __restrict__ mask_out,
-                                                            int* __restrict__ batch_counts,
-                                                            long long* __restrict__ order_out) {
-  const unsigned long long jj = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
-  const bool live = jj < n;
-  const unsigned j = (unsigned)jj;
-  int sampled = 0;
-  if (live) {
-    const size_t i = shuffle_order(sk, j, n);  // < n by construction
-    const size_t o = j;
-    if (coords_out != nullptr) {
-      const float c0 = coords[3 * i], c1 = coords[3 * i + 1], c2 = coords[3 * i + 2];
-      coords_out[3 * o] = c0;
-      coords_out[3 * o + 1] = c1;
-      coords_out[3 * o + 2] = c2;
-    }
-    if (gt_out != nullptr)
-      reinterpret_cast<float2*>(gt_out)[o] = reinterpret_cast<const float2*>(gt)[i];
-    if (dist_out != nullptr) dist_out[o] = dist[i];
-    sampled = 1;
-    if (mask != nullptr) {
-      const uint8_t m = mask[i];
-      if (mask_out != nullptr) mask_out[o] = m;
-      sampled = m != 0 ? 1 : 0;
-    }
-    if (order_out != nullptr) order_out[o] = (long long)i;
-  }
-  if (batch_counts != nullptr) {
-    // a wave's rows are [w0, w0 + 64): one batch unless a batch end falls inside (wave-uniform test)
-    const unsigned long long w0 = jj - (threadIdx.x & 63);
-    const unsigned long long wl = (w0 + 63 < n ? w0 + 63 : (unsigned long long)n - 1);
-    if (w0 < n) {
-      const unsigned b0 = (unsigned)(w0 / bs), b1 = (unsigned)(wl / bs);
-      if (b0 == b1) {
-        const int cnt = __popcll(__ballot(sampled != 0));
-        if ((threadIdx.x & 63) == 0 && cnt != 0) atomicAdd(batch_counts + b0, cnt);
-      } else if (live && sampled) {
-        atomicAdd(batch_counts + j / bs, 1);
-      }
-    }
-  }
-}
-
-hipError_t launch_shuffle_epoch(const ShuffleKeys& sk, long long n, long long bs, const float* coords, const float* gt,
-                                const float* dist, const uint8_t* mask, float* coords_out, float* gt_out, float* dist_out,
-                                uint8_t* mask_out, int* batch_counts, long long* order_out, hipStream_t st) {
-  if (batch_counts != nullptr) {
-    const long long nb = (n + bs - 1) / bs;
-    const hipError_t e = hipMemsetAsync(batch_counts, 0, (size_t)nb * sizeof(int), st);
-    if (e != hipSuccess) return e;
-  } else {
-    bs = 1;
-  }
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(shuffle_epoch_kernel, dim3(grid), dim3(256), 0, st, sk, (unsigned)n,
-                     (unsigned)(bs > n ? n : bs), coords, gt, dist, mask, coords_out, gt_out, dist_out, mask_out,
-                     batch_counts, order_out);
   return hipGetLastError();
 }
 

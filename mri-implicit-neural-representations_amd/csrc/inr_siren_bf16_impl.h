@@ -466,7 +466,7 @@ struct SirenTile {
         float fprev = 0.f, fph = 0.f;
         // Element j of K-step s of chunk ch into dst.  A lane half holds the sine AND the cosine of four frequencies per
         // K-step -- elements (2i, 2i+1) = (sin, cos) of frequency 8 s + 4 half + i of the chunk (the weight panels are packed
-        // in that k order, inr_aux.hip put_w2) -- so ONE phase chain serves two elements (both halves used to run the same
+        // in that k order, inr_params.hip put_w2) -- so ONE phase chain serves two elements (both halves used to run the same
         // eight chains, the cosine half from a start of 1/4 turn).  The frequency's row of the encoder matrix was read from
         // LDS two slots earlier; the next one's (of chunk chn: the same chunk, or the next behind its last element) here.
         f32x4 nbr = {0.f, 0.f, 0.f, 0.f};

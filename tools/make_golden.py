@@ -822,12 +822,27 @@ def host_layout():
     print("host_layout:", len(out["plans"]), "plans,", len(out["plans"]) * len(T.B_VALUES) * len(T.SWITCHES), "records")
 
 
+def aux_bits():
+    """tests/golden/aux_bits.json (tests/aux_bits_cases.py, tests/test_gpu_aux_bits.py): SHA-256 of what the helper kernels
+    of ONE commit's library write, on a GPU.  Not a default part: it reads no reference code.  The library is named by
+    AUX_BITS_PRODUCER=<commit>:<path of the libinr_mi355x.so built from it> and loaded through INR_LIB_PATH in fresh
+    processes, twice.  (tests/aux_bits_cases.py::record is the whole of it, for machines without the reference tree.)"""
+    root = os.path.dirname(os.path.dirname(OUT))
+    sys.path.append(os.path.join(root, "tests"))
+    import aux_bits_cases as A
+    commit, _, lib = os.environ.get("AUX_BITS_PRODUCER", "").partition(":")
+    if len(commit) != 40 or not os.path.exists(lib):
+        raise SystemExit("aux_bits: set AUX_BITS_PRODUCER=<40-digit commit>:<library built from it>")
+    cases, unstable = A.record(lib, commit, os.path.join(OUT, "aux_bits.json"))
+    print("aux_bits:", len(cases), "cases from", commit[:7], "-- not deterministic:", unstable or "none")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     parts = dict(ingest=ingest_vectors, clustering=clustering_vectors, undersampling=undersampling_vectors, init=init_hashes,
                  models=model_vectors, losses=loss_vectors, center=center_vectors, trajectory=trajectory,
                  multiscale=multiscale_trajectory, extra=extra_trajectories, hp_search=hp_search_vectors)
-    on_request = dict(host_layout=host_layout)
+    on_request = dict(host_layout=host_layout, aux_bits=aux_bits)
     for name in (sys.argv[1:] or list(parts)):  # python tools/make_golden.py [part ...]; default: every reference-made part
         {**parts, **on_request}[name]()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
