@@ -51,7 +51,8 @@ extern "C" {
  *    (rows of a coordinate grid, made on the device: reconstruction from a checkpoint on any grid); inr_band_stats and its
  *    scratch query (per-band counts, energies, errors and extrema of a field against radius); inr_coil_gram, its scratch
  *    query and inr_coil_apply (software coil compression: the coil Gram matrix in one pass, the product with a small matrix);
- *    inr_nudft and its scratch query (the continuous k-space of coil images at off-grid positions).
+ *    inr_nudft and its scratch query (the continuous k-space of coil images at off-grid positions); inr_adjoint_nudft and
+ *    its scratch query (its conjugate transpose: off-grid samples back onto the image grid).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -545,6 +546,23 @@ int inr_coil_apply(const float* in, const float* A, int32_t M, int32_t K, int64_
 int inr_nudft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats);
 int inr_nudft(const float* img, int32_t C, int64_t H, int64_t W, const double* pos, int64_t M, float* out,
               float* scratch, int64_t scratch_floats, void* stream);
+
+/* (v7 addition) The conjugate transpose of inr_nudft: off-grid k-space samples back onto the image grid (no reference
+ * counterpart).  val [C][M][2]: complex fp32 samples; pos [M][2]: fp64 (u_y, u_x) as for
+ * inr_nudft; w [M]: fp32 weights (a density compensation), or null for all ones; out [C][H][W][2] fp32,
+ *   out[c][y][x] = 1/sqrt(H W) sum_m w[m] val[c][m] exp(+2 pi i ((u_y - c_y)(y - c_y)/H + (u_x - c_x)(x - c_x)/W)),
+ * c_y = H/2, c_x = W/2: with every integer grid point as a position and w null, the inverse centred FFT.  It reads the
+ * phasor tables inr_nudft reads (fp64 phase reduction, fp32 entries), so the two calls are transposes of each other up
+ * to the rounding of their fp32 sums; the order of the sums is fixed (no atomics): two calls give the same bits.
+ * `scratch` (device, 16-byte aligned) holds at least what inr_adjoint_nudft_scratch gives for (C, H, W, M): 2 (W' + H') M'
+ * floats with W' and H' rounded up to 64 and M' = M to 64.  Two launches on `stream`, nothing allocated, nothing read
+ * back.  inr_mi355x/trajectory.py::nudft_adjoint_numpy restates it in fp64.
+ * INR_ERR_INVALID before any launch: a null pointer other than w; C outside 1..INR_COIL_MAX; H or W < 1 or > 2^31 - 64;
+ * H * W >= 2^31; M < 1 or M >= 2^31; val / pos / out not 8-byte, w not 4-byte or scratch not 16-byte aligned; scratch
+ * short of the query; out overlapping val, pos or w; scratch overlapping any of them. */
+int inr_adjoint_nudft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats);
+int inr_adjoint_nudft(const float* val, const double* pos, const float* w, int32_t C, int64_t H, int64_t W, int64_t M,
+                      float* out, float* scratch, int64_t scratch_floats, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network: encoders, losses, TV, Adam,
-// image metrics, display, shuffle, grid rows, band statistics, coil compression, off-grid sampling.  Each checks its arguments, fills an argument struct,
+// image metrics, display, shuffle, grid rows, band statistics, coil compression, off-grid sampling and its adjoint.  Each checks its arguments, fills an argument struct,
 // launches and maps the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -506,6 +506,47 @@ int inr_nudft(const float* img, int32_t C, int64_t H, int64_t W, const double* p
     return fail(INR_ERR_INVALID, "inr_nudft: scratch overlaps img, pos or out");
   hipError_t e = inr::launch_nudft(img, C, (int)H, (int)W, pos, M, out, scratch, (hipStream_t)stream);
   return hip_done(e, "inr_nudft");
+}
+
+// ---- ... and back onto the grid: the conjugate transpose (inr_nudft_adjoint.hip) ----
+static int adjoint_nudft_check(int32_t C, int64_t H, int64_t W, int64_t M, const char* who) {
+  if (int rc = nudft_check(C, H, W, M, who)) return rc;
+  if (H > (1LL << 31) - 64 || W > (1LL << 31) - 64)  // the tables pad both axes to 64
+    return fail(INR_ERR_INVALID, "%s: H = %lld, W = %lld (each <= 2^31 - 64)", who, (long long)H, (long long)W);
+  return INR_OK;
+}
+
+int inr_adjoint_nudft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats) {
+  if (scratch_floats == nullptr) return fail(INR_ERR_INVALID, "inr_adjoint_nudft_scratch: null argument");
+  if (int rc = adjoint_nudft_check(C, H, W, M, "inr_adjoint_nudft_scratch")) return rc;
+  *scratch_floats = inr::adjoint_nudft_scratch_floats(H, W, M);
+  return INR_OK;
+}
+
+int inr_adjoint_nudft(const float* val, const double* pos, const float* w, int32_t C, int64_t H, int64_t W, int64_t M,
+                      float* out, float* scratch, int64_t scratch_floats, void* stream) {
+  if (val == nullptr || pos == nullptr || out == nullptr || scratch == nullptr)
+    return fail(INR_ERR_INVALID, "inr_adjoint_nudft: null argument");
+  if (int rc = adjoint_nudft_check(C, H, W, M, "inr_adjoint_nudft")) return rc;
+  if ((((uintptr_t)val | (uintptr_t)pos | (uintptr_t)out) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_adjoint_nudft: val / pos / out is not 8-byte aligned");
+  if (((uintptr_t)w & 3u) != 0) return fail(INR_ERR_INVALID, "inr_adjoint_nudft: w is not 4-byte aligned");
+  if (((uintptr_t)scratch & 15u) != 0) return fail(INR_ERR_INVALID, "inr_adjoint_nudft: scratch is not 16-byte aligned");
+  const int64_t need = inr::adjoint_nudft_scratch_floats(H, W, M);
+  if (scratch_floats < need)
+    return fail(INR_ERR_INVALID, "inr_adjoint_nudft: scratch holds %lld floats, H = %lld, W = %lld, M = %lld need %lld",
+                (long long)scratch_floats, (long long)H, (long long)W, (long long)M, (long long)need);
+  const int64_t val_bytes = (int64_t)C * M * 8, pos_bytes = M * 16, w_bytes = w != nullptr ? M * 4 : 0,
+                out_bytes = (int64_t)C * H * W * 8;
+  if (ranges_overlap(out, out_bytes, val, val_bytes)) return fail(INR_ERR_INVALID, "inr_adjoint_nudft: out overlaps val");
+  if (ranges_overlap(out, out_bytes, pos, pos_bytes)) return fail(INR_ERR_INVALID, "inr_adjoint_nudft: out overlaps pos");
+  if (w != nullptr && ranges_overlap(out, out_bytes, w, w_bytes))
+    return fail(INR_ERR_INVALID, "inr_adjoint_nudft: out overlaps w");
+  if (ranges_overlap(scratch, need * 4, out, out_bytes) || ranges_overlap(scratch, need * 4, val, val_bytes) ||
+      ranges_overlap(scratch, need * 4, pos, pos_bytes) || (w != nullptr && ranges_overlap(scratch, need * 4, w, w_bytes)))
+    return fail(INR_ERR_INVALID, "inr_adjoint_nudft: scratch overlaps val, pos, w or out");
+  hipError_t e = inr::launch_adjoint_nudft(val, pos, w, C, (int)H, (int)W, M, out, scratch, (hipStream_t)stream);
+  return hip_done(e, "inr_adjoint_nudft");
 }
 
 int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* host_out) {

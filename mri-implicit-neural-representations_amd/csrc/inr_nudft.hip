@@ -190,12 +190,17 @@ long long nudft_scratch_floats(long long H, long long W, long long M) {
   return 2LL * ((long long)d.Wp + d.Hp) * d.Mp;
 }
 
+void launch_nudft_tables(const double* pos, long long M, long long Mp, int H, int W, int Hp, int Wp, float* tab,
+                         hipStream_t st) {
+  const int rows = Wp + Hp;
+  const dim3 tgrid((unsigned)((Mp + NU_THREADS - 1) / NU_THREADS), (unsigned)(rows < 65535 ? rows : 65535));
+  hipLaunchKernelGGL(nudft_tables_kernel, tgrid, dim3(NU_THREADS), 0, st, pos, M, Mp, H, W, Hp, Wp, tab);
+}
+
 hipError_t launch_nudft(const float* img, int C, int H, int W, const double* pos, long long M, float* out,
                         float* scratch, hipStream_t st) {
   const NudftDims d = nudft_dims(H, W, M);
-  const int rows = d.Wp + d.Hp;
-  const dim3 tgrid((unsigned)((d.Mp + NU_THREADS - 1) / NU_THREADS), (unsigned)(rows < 65535 ? rows : 65535));
-  hipLaunchKernelGGL(nudft_tables_kernel, tgrid, dim3(NU_THREADS), 0, st, pos, M, d.Mp, H, W, d.Hp, d.Wp, scratch);
+  launch_nudft_tables(pos, M, d.Mp, H, W, d.Hp, d.Wp, scratch, st);
   hipLaunchKernelGGL(nudft_kernel, dim3((unsigned)(d.Mp / NU_TM), (unsigned)C), dim3(NU_THREADS), 0, st, img, scratch, M,
                      d.Mp, H, W, d.Hp, d.Wp, out);
   return hipGetLastError();

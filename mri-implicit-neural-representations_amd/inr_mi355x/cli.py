@@ -61,15 +61,16 @@ def parse_cli(val_and_samples: bool = True, argv=None):
     add_band_report_flag(ap, "with --val" if val_and_samples else "after the fit")
     from .coils import add_virtual_coils_flag, apply_virtual_coils_flag
     add_virtual_coils_flag(ap)
-    from .trajectory import add_trajectory_flag, apply_trajectory_flag
+    from .trajectory import add_baseline_flags, add_trajectory_flag, apply_baseline_flags, apply_trajectory_flag
     add_trajectory_flag(ap)
+    add_baseline_flags(ap)
     opts = ap.parse_args(argv)
     if val_and_samples and opts.save_images and not opts.val:
         ap.error("--save-images needs --val (the pictures are those of the validation epoch)")
     if opts.band_report is not None and val_and_samples and not opts.val:
         ap.error("--band-report needs --val (the report is made from the validation epoch's prediction)")
     config = apply_virtual_coils_flag(apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts), opts)
-    return opts, apply_trajectory_flag(config, opts)
+    return opts, apply_baseline_flags(apply_trajectory_flag(config, opts), opts)
 
 
 def expand_data_samples(config: dict, samples) -> list:
@@ -141,6 +142,8 @@ def cli_folders(tr, opts):
     ckpt_dir, image_dir = prepare_sub_folder(opts.output_path)
     tr.enable_validation_images()
     tr.save_training_images(image_dir)
+    if getattr(tr, "gridding", None) is not None:
+        tr.save_gridding_image(image_dir)
     return ckpt_dir, image_dir
 
 
@@ -195,6 +198,8 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
         res["coil_compression"] = tr.coil_compression.summary()
     if getattr(tr, "trajectory_info", None) is not None:
         res["trajectory"] = tr.trajectory_info
+    if getattr(tr, "gridding", None) is not None:
+        res["gridding"] = tr.gridding
     if extra:
         res.update(extra)
     if opts.val:

@@ -7,16 +7,17 @@ drivers lives in their hooks, never in a switch here.
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import numpy as np
 import torch
 
-from .evalchain import psnr, reconstruct
+from .evalchain import image_metrics, psnr, reconstruct
 from .networks import Positional_Encoder
 from .shuffle import CoilOrder, EpochBuffers, shuffle_settings
 from .undersampling import Undersampler, parse_undersampling_argument
-from .validation import ValidationMixin
+from .validation import ValidationMixin, coil_images
 
 
 def set_default_configs(config: dict) -> dict:
@@ -28,6 +29,8 @@ def set_default_configs(config: dict) -> dict:
     config.setdefault("undersampling", None)
     config.setdefault("virtual_coils", 0)  # coils.py: K virtual coils instead of the scan's physical ones; 0 = off
     config.setdefault("trajectory", "none")  # trajectory.py: train on off-grid k-space samples; "none" = off
+    config.setdefault("trajectory_baseline", "none")  # ... and reconstruct them conventionally too: adjoint | cg-N
+    config.setdefault("trajectory_density", None)  # the baseline's density weights; None: ramp (spokes) / uniform (file)
     return config
 
 
@@ -108,6 +111,17 @@ class ResidentFit(ValidationMixin):
             raise NotImplementedError(f"config['trajectory'] = {config['trajectory']!r}: off-grid fits run in INRTrainer "
                                       "(python -m inr_mi355x.train) only")
         self.trajectory_info = describe(self.trajectory, int(shape[1]), int(shape[2]))
+        # config['trajectory_baseline'] / ['trajectory_density'] belong to an off-grid fit
+        from .trajectory import parse_baseline, parse_density
+        self.trajectory_baseline = parse_baseline(config["trajectory_baseline"])
+        self.trajectory_density = self.gridding = self.gridding_image = None
+        if self.trajectory is None and (self.trajectory_baseline is not None or config["trajectory_density"] is not None):
+            raise ValueError(f"config['trajectory_baseline'] = {config['trajectory_baseline']!r} / ['trajectory_density'] = "
+                             f"{config['trajectory_density']!r} without config['trajectory']: there are no off-grid "
+                             "samples to reconstruct")
+        if self.trajectory is not None and (self.trajectory_baseline is not None or config["trajectory_density"] is not None):
+            self.trajectory_density = parse_density(config["trajectory_density"], self.trajectory, int(shape[1]),
+                                                    int(shape[2]))
         from .coils import check_virtual_coils
         K = check_virtual_coils(config["virtual_coils"])
         if K and coil_compression is None:
@@ -185,6 +199,42 @@ class ResidentFit(ValidationMixin):
         if "pretrain" in self.config:  # train.py:117-121
             self.load_checkpoint(torch.load(self.config["pretrain"], map_location=self.device))
         self._init_validation()
+        if self.trajectory_baseline is not None:
+            self._gridding_baseline()
+
+    @torch.no_grad()
+    def _gridding_baseline(self) -> None:
+        """config['trajectory_baseline']: the conventional reconstruction of the samples the fit trains
+        on -- the density-weighted adjoint or N conjugate-gradient iterations (trajectory.cg_baseline) -- made once, scored
+        as validation scores the fit (RSS, then PSNR / SSIM against the full data, on the device).  Leaves the record in
+        self.gridding and the coil images [C,H,W,2] in self.gridding_image; reads no random numbers and no parameter."""
+        import time
+        from .trajectory import cg_baseline, positions
+        C, H, W = (int(v) for v in self.shape[:3])
+        mode, iters = self.trajectory_baseline
+        name, w = self.trajectory_density
+        torch.cuda.synchronize(self.device)
+        t0 = time.time()
+        iterates, objective = cg_baseline(self.train_values, positions(self.trajectory, H, W), (C, H, W), w, iters)
+        self.gridding_image = iterates[-1].contiguous()
+        torch.cuda.synchronize(self.device)
+        seconds = time.time() - t0
+        if self._ref_rss is None:
+            self._ref_rss = image_metrics(None, coil_images(self.image_full, self.shape, self.in_image_space))[0]
+        self._gridding_rss, m = image_metrics(self._ref_rss, self.gridding_image)[:2]
+        psnr_, ssim_ = m[:2].cpu().tolist()
+        self.gridding = {"mode": mode, "iters": iters, "density": name, "psnr": psnr_, "ssim": ssim_,
+                         "objective": [float(v) for v in objective], "seconds": seconds}
+
+    @torch.no_grad()
+    def save_gridding_image(self, directory: str, prefix: str = "") -> str:
+        """gridding_{psnr}_psnr_{ssim}_ssim.png: the baseline's RSS image through the display kernels"""
+        if self.gridding is None:
+            raise RuntimeError("save_gridding_image: the fit has no config['trajectory_baseline']")
+        D, b = self._display()
+        os.makedirs(directory, exist_ok=True)
+        name = prefix + "gridding_{:.4g}_psnr_{:.4g}_ssim.png".format(self.gridding["psnr"], self.gridding["ssim"])
+        return self._write_gray(D, b, os.path.join(directory, name), self._gridding_rss, True)
 
     # ---- batches ---------------------------------------------------------------------------------
     def _range(self, it: int):
@@ -283,6 +333,8 @@ class ResidentFit(ValidationMixin):
             rec["coil_compression"] = self.coil_compression.summary()
         if self.trajectory_info is not None:
             rec["trajectory"] = self.trajectory_info
+        if self.gridding is not None:
+            rec["gridding"] = self.gridding
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         return rec

@@ -14,6 +14,10 @@ one ulp); the coil coordinate is linspace(-1, 1, C)[c], as on the grid.
 
 ``nudft_numpy`` is the definition in fp64 and needs no GPU; ``nudft`` is the device call, which reduces the phase in fp64
 and forms phasors and sums in fp32.
+
+``nudft_adjoint`` (inr_adjoint_nudft, csrc/inr_nudft_adjoint.hip) is the conjugate transpose, with optional
+density weights; ``cg_baseline`` builds the conventional density-weighted conjugate-gradient reconstruction from the two,
+which config['trajectory_baseline'] prints next to the fit's score.
 """
 from __future__ import annotations
 
@@ -198,6 +202,241 @@ def sample_kspace(kspace: torch.Tensor, shape, pos) -> Tuple[torch.Tensor, torch
     return nudft(img, pos).reshape(-1, 2), trajectory_coords(pos, C_, H, W)
 
 
+# ---- the adjoint: samples back onto the grid (inr_adjoint_nudft, csrc/inr_nudft_adjoint.hip; DESIGN.md 4.20) ----------
+def _samples_complex(val) -> np.ndarray:
+    """[C, M] complex128 of [C, M, 2] pairs (array or CPU tensor) or a complex [C, M] / [M] array"""
+    if isinstance(val, torch.Tensor):
+        val = val.detach().cpu().numpy()
+    v = np.asarray(val)
+    if not np.iscomplexobj(v):
+        if v.ndim < 2 or v.shape[-1] != 2:
+            raise ValueError(f"samples: expected [C, M, 2] pairs or a complex [C, M] array, got {v.dtype} {v.shape}")
+        v = v[..., 0].astype(np.float64) + 1j * v[..., 1].astype(np.float64)
+    v = v.astype(np.complex128)
+    return v[None] if v.ndim == 1 else v
+
+
+def _weights_numpy(weights, M: int) -> np.ndarray:
+    if weights is None:
+        return np.ones(M, dtype=np.float64)
+    if isinstance(weights, torch.Tensor):
+        weights = weights.detach().cpu().numpy()
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape != (M,):
+        raise ValueError(f"weights: expected [{M}], got {w.shape}")
+    return w
+
+
+def nudft_adjoint_numpy(val, pos, H: int, W: int, weights=None) -> np.ndarray:
+    """[C, H, W] complex128: the conjugate transpose of nudft_numpy applied to weights * val,
+    out[c][y][x] = 1/sqrt(H W) sum_m w[m] val[c][m] exp(+2 pi i ((u_y - c_y)(y - c_y)/H + (u_x - c_x)(x - c_x)/W)).
+    ``val``: [C, M, 2] pairs or complex [C, M]; ``pos``: [M, 2]; ``weights``: [M] or None (all ones)."""
+    v = _samples_complex(val)
+    pos = check_positions(np.asarray(pos, dtype=np.float64))
+    H, W = int(H), int(W)
+    if v.shape[1] != pos.shape[0]:
+        raise ValueError(f"samples {v.shape} and positions {pos.shape} disagree")
+    v = v * _weights_numpy(weights, pos.shape[0])[None, :]
+    ey, ex = np.conj(_phasors(pos[:, 0], H)), np.conj(_phasors(pos[:, 1], W))  # [M, H], [M, W]
+    out = np.empty((v.shape[0], H, W), dtype=np.complex128)
+    for c in range(v.shape[0]):
+        out[c] = (ey * v[c][:, None]).T @ ex  # sum_m conj(Ey[m][y]) v[m] conj(Ex[m][x])
+    return out / math.sqrt(H * W)
+
+
+def adjoint_error_bound(val, weights, H: int, W: int) -> np.ndarray:
+    """[C] fp64: (M + 32) 2^-24 sum_m |w_m val_c[m]| / sqrt(H W) -- the worst-case fp32 bound of
+    |nudft_adjoint - nudft_adjoint_numpy| per pixel: M accumulated terms, each formed with a few roundings after an
+    fp64-reduced phase (the form of error_bound)"""
+    v = _samples_complex(val)
+    M = v.shape[1]
+    return (M + 32) * 2.0 ** -24 * (np.abs(v) * np.abs(_weights_numpy(weights, M))[None, :]).sum(axis=1) / math.sqrt(H * W)
+
+
+def adjoint_scratch_floats(coils: int, H: int, W: int, M: int) -> int:
+    out = C.c_int64(0)
+    L.check(L.load().inr_adjoint_nudft_scratch(int(coils), int(H), int(W), int(M), C.byref(out)))
+    return int(out.value)
+
+
+def _device_positions(pos, device) -> torch.Tensor:
+    if isinstance(pos, torch.Tensor):
+        if pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 2:
+            raise ValueError(f"pos: expected [M, 2] float64, got {pos.dtype} {tuple(pos.shape)}")
+        return pos.to(device).contiguous()
+    return torch.from_numpy(check_positions(pos)).to(device)
+
+
+def _device_weights(weights, M: int, device) -> Optional[torch.Tensor]:
+    if weights is None:
+        return None
+    w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.asarray(weights, dtype=np.float64))
+    if tuple(w.shape) != (M,):
+        raise ValueError(f"weights: expected [{M}], got {tuple(w.shape)}")
+    return w.to(device=device, dtype=torch.float32).contiguous()
+
+
+def nudft_adjoint(val: torch.Tensor, pos, shape, weights=None, scratch: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[C, H, W, 2] fp32 on the device: the samples ``val`` [C, M, 2] (device, fp32) at ``pos`` [M, 2] (fp64, numpy or
+    device tensor), times ``weights`` [M] (any float array or tensor, used in fp32; None: ones), back on the H x W grid of
+    ``shape`` = (H, W) or (C, H, W).  One inr_adjoint_nudft call on the current stream; ``scratch``: a float32 device
+    buffer of at least adjoint_scratch_floats(C, H, W, M) entries (default: allocated here)."""
+    if not isinstance(val, torch.Tensor) or not val.is_cuda:
+        raise RuntimeError("nudft_adjoint only runs on an MI355X (no CPU fallback; nudft_adjoint_numpy is the host-side "
+                           "definition)")
+    if val.dtype != torch.float32 or val.dim() != 3 or val.shape[-1] != 2:
+        raise RuntimeError(f"val must be float32 [C, M, 2] (got {val.dtype} {tuple(val.shape)})")
+    val = val.contiguous()
+    coils, M = int(val.shape[0]), int(val.shape[1])
+    H, W = (int(v) for v in tuple(shape)[-2:])
+    p = _device_positions(pos, val.device)
+    if int(p.shape[0]) != M:
+        raise ValueError(f"val has {M} samples per coil, pos {int(p.shape[0])}")
+    w = _device_weights(weights, M, val.device)
+    if scratch is None:
+        scratch = torch.empty(adjoint_scratch_floats(coils, H, W, M), device=val.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(coils, H, W, 2, device=val.device, dtype=torch.float32)
+    with torch.cuda.device(val.device):
+        L.check(L.load().inr_adjoint_nudft(val.data_ptr(), p.data_ptr(), None if w is None else w.data_ptr(), coils, H, W,
+                                           M, out.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                           torch.cuda.current_stream(val.device).cuda_stream))
+    return out
+
+
+# ---- density compensation ----------------------------------------------------------------------------------------------
+def normalise_density(w, H: int, W: int) -> np.ndarray:
+    """``w`` scaled so that sum w = H W: with the 1/sqrt(H W) of both operators the point-spread function A^H W A then
+    has peak 1"""
+    w = np.asarray(w, dtype=np.float64)
+    return w * (float(H) * float(W) / w.sum())
+
+
+def density_ramp(n_spokes: int, readout: int, H: Optional[int] = None, W: Optional[int] = None) -> np.ndarray:
+    """fp64 [n_spokes * readout], spoke-major: |j - R // 2| for sample j of a spoke and 1/4 for the centre sample (the
+    disc of radius half a step, area pi / 4 against the ring's 2 pi |j| / n_spokes per step -- the 1/n_spokes both share
+    drops out in the scaling); with H and W, scaled by normalise_density"""
+    n_spokes, R = int(n_spokes), int(readout)
+    if n_spokes < 1 or R < 2:
+        raise ValueError(f"density_ramp: n_spokes = {n_spokes}, readout = {R} (n_spokes >= 1, readout >= 2)")
+    w = np.abs(np.arange(R, dtype=np.float64) - R // 2)
+    w[R // 2] = 0.25
+    w = np.tile(w, n_spokes)
+    return w if H is None else normalise_density(w, H, W)
+
+
+def parse_density(arg, parsed, H: int, W: int):
+    """config['trajectory_density'] -> (name, weights fp64 [M] with sum H W) for the parsed trajectory on an H x W grid.
+    None / "default": "ramp" for spokes, "uniform" for a file trajectory; "ramp" (spokes only), "uniform", or the path of
+    a .npy file of [M] finite positive float64.  ValueError for anything else."""
+    if parsed is None:
+        raise ValueError("trajectory_density needs a trajectory")
+    M = int(positions(parsed, H, W).shape[0])
+    if arg is None or (isinstance(arg, str) and arg.lower() in ("default", "none")):
+        arg = "ramp" if parsed[0] == "spokes" else "uniform"
+    if not isinstance(arg, str):
+        raise ValueError(f"trajectory_density = {arg!r}: 'ramp', 'uniform' or the path of a .npy file")
+    if arg == "ramp":
+        if parsed[0] != "spokes":
+            raise ValueError("trajectory_density = 'ramp' needs a spokes trajectory (a file trajectory has no spoke "
+                             "structure: give its weights as a .npy file)")
+        return "ramp", density_ramp(parsed[1], M // parsed[1], H, W)
+    if arg == "uniform":
+        return "uniform", normalise_density(np.ones(M, dtype=np.float64), H, W)
+    if arg.endswith(".npy"):
+        if not os.path.isfile(arg):
+            raise ValueError(f"trajectory_density = {arg!r}: no such file")
+        w = np.load(arg, allow_pickle=False)
+        if w.dtype != np.float64 or w.shape != (M,) or not np.isfinite(w).all() or not (w > 0).all():
+            raise ValueError(f"trajectory_density = {arg!r}: expected [{M}] finite positive float64, got {w.dtype} {w.shape}")
+        return arg, normalise_density(w, H, W)
+    raise ValueError(f"trajectory_density = {arg!r}: 'ramp', 'uniform' or the path of a .npy file")
+
+
+def parse_baseline(arg):
+    """config['trajectory_baseline'] -> None (off), ("adjoint", 0) or ("cg", N), 1 <= N <= 64.  Accepts None / "none",
+    "adjoint" and "cg-N"; ValueError for anything else."""
+    if arg is None:
+        return None
+    if isinstance(arg, str):
+        if arg.lower() == "none":
+            return None
+        if arg == "adjoint":
+            return ("adjoint", 0)
+        m = re.fullmatch(r"cg-(\d+)", arg)
+        if m and 1 <= int(m.group(1)) <= 64:
+            return ("cg", int(m.group(1)))
+    raise ValueError(f"trajectory_baseline = {arg!r}: 'none', 'adjoint' or 'cg-N' with 1 <= N <= 64")
+
+
+# ---- the conventional reconstruction: conjugate gradients on A^H W A x = A^H W y -----------------------------------------
+def _cg(y, w_sum, apply_a, apply_ahw, dot, axpy, iters: int):
+    """The iteration both versions run.  ``w_sum(a)``: sum_m w |a|^2; ``dot(a)``: sum |a|^2, both Python floats formed in
+    fp64; one alpha and one beta per iteration over all coils.  Returns (iterates, objective)."""
+    b = apply_ahw(y)
+    if iters == 0:
+        return [b], [w_sum(apply_a(b) - y)]
+    objective = [w_sum(y)]  # x_0 = 0
+    x, s = None, None  # the iterate and A x
+    r, p = b, b
+    rr = dot(r)
+    iterates = []
+    for _ in range(iters):
+        q = apply_a(p)
+        pnp = w_sum(q)  # <p, A^H W A p>
+        alpha = rr / pnp if pnp > 0.0 else 0.0
+        x = axpy(alpha, p, x)
+        s = axpy(alpha, q, s)
+        r = axpy(-alpha, apply_ahw(q), r)
+        rr_new = dot(r)
+        p = axpy(rr_new / rr if rr > 0.0 else 0.0, p, r)
+        rr = rr_new
+        iterates.append(x)
+        objective.append(w_sum(s - y))
+    return iterates, objective
+
+
+def cg_baseline_numpy(values, pos, shape, weights, iters: int):
+    """cg_baseline in fp64 on the host: (iterates [C, H, W] complex128, objective)"""
+    y = _samples_complex(values)
+    H, W = (int(v) for v in tuple(shape)[-2:])
+    pos = check_positions(np.asarray(pos, dtype=np.float64))
+    w = _weights_numpy(weights, pos.shape[0])
+    return _cg(y, lambda a: float((w[None, :] * np.abs(a) ** 2).sum()), lambda x: nudft_numpy(x, pos),
+               lambda a: nudft_adjoint_numpy(a, pos, H, W, w), lambda a: float((np.abs(a) ** 2).sum()),
+               lambda k, a, b: k * a if b is None else b + k * a, int(iters))
+
+
+def cg_baseline(values: torch.Tensor, pos, shape, weights, iters: int):
+    """The density-weighted conjugate-gradient reconstruction of off-grid samples: ``iters`` iterations on
+    A^H W A x = A^H W y from x_0 = 0, A = nudft, all coils at once with one alpha and one beta per iteration; the inner
+    products are taken with torch on the device, accumulated in fp64, and read back (two scalars per iteration).
+    ``values``: [C, M, 2] or [(C*M), 2] fp32 on the device; ``shape`` = (C, H, W); ``weights``: [M] or None.
+    Returns (iterates, objective): the image [C, H, W, 2] after each iteration and sum_m w |A x - y|^2 of x_0 = 0 and of
+    every iterate (iters + 1 entries, A x carried along the recurrence).  iters = 0: the plain density-weighted adjoint
+    A^H W y and its objective.  The two scratch buffers are allocated once."""
+    if not isinstance(values, torch.Tensor) or not values.is_cuda:
+        raise RuntimeError("cg_baseline only runs on an MI355X (no CPU fallback; cg_baseline_numpy is the host-side version)")
+    C_, H, W = (int(v) for v in shape[:3])
+    y = values.reshape(C_, -1, 2).contiguous()
+    M = int(y.shape[1])
+    dev = y.device
+    p_dev = _device_positions(pos, dev)
+    w32 = _device_weights(weights, M, dev)
+    w64 = None if w32 is None else w32.double()
+    fwd = torch.empty(scratch_floats(C_, H, W, M), device=dev, dtype=torch.float32)
+    adj = torch.empty(adjoint_scratch_floats(C_, H, W, M), device=dev, dtype=torch.float32)
+
+    def w_sum(a):
+        e = (a.double() ** 2).sum(dim=-1)  # [C, M]
+        return float((e if w64 is None else e * w64[None, :]).sum())
+
+    return _cg(y, w_sum, lambda x: nudft(x, p_dev, scratch=fwd),
+               lambda a: nudft_adjoint(a, p_dev, (H, W), w32, scratch=adj), lambda a: float((a.double() ** 2).sum()),
+               lambda k, a, b: a * k if b is None else torch.add(b, a, alpha=k), int(iters))
+
+
 # ---- the switch --------------------------------------------------------------------------------------------------------
 def add_trajectory_flag(ap) -> None:
     ap.add_argument("--trajectory", type=str, default=None, metavar="ARG",
@@ -208,4 +447,22 @@ def add_trajectory_flag(ap) -> None:
 def apply_trajectory_flag(config: dict, opts) -> dict:
     if getattr(opts, "trajectory", None) is not None:
         config["trajectory"] = opts.trajectory
+    return config
+
+
+def add_baseline_flags(ap) -> None:
+    ap.add_argument("--trajectory-baseline", type=str, default=None, metavar="ARG",
+                    help="with --trajectory: also reconstruct the same samples conventionally and report it as "
+                         "'gridding': adjoint (density-weighted adjoint) or cg-N (N conjugate-gradient iterations, "
+                         "1..64) (config['trajectory_baseline']; none: off)")
+    ap.add_argument("--trajectory-density", type=str, default=None, metavar="ARG",
+                    help="the baseline's density compensation: ramp (spokes), uniform or a .npy file of [M] positive "
+                         "float64 (config['trajectory_density']; default: ramp for spokes, uniform for a file)")
+
+
+def apply_baseline_flags(config: dict, opts) -> dict:
+    if getattr(opts, "trajectory_baseline", None) is not None:
+        config["trajectory_baseline"] = opts.trajectory_baseline
+    if getattr(opts, "trajectory_density", None) is not None:
+        config["trajectory_density"] = opts.trajectory_density
     return config

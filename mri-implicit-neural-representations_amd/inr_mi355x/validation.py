@@ -183,6 +183,8 @@ class ValidationMixin:
             rec["coil_compression"] = self.coil_compression.summary()
         if getattr(self, "trajectory_info", None) is not None:  # trained on off-grid rows, scored on the grid
             rec["trajectory"] = self.trajectory_info
+        if getattr(self, "gridding", None) is not None:  # ... next to the conventional reconstruction of the same samples
+            rec["gridding"] = self.gridding
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         self.val_history.append(rec)
