@@ -52,7 +52,8 @@ extern "C" {
  *    scratch query (per-band counts, energies, errors and extrema of a field against radius); inr_coil_gram, its scratch
  *    query and inr_coil_apply (software coil compression: the coil Gram matrix in one pass, the product with a small matrix);
  *    inr_nudft and its scratch query (the continuous k-space of coil images at off-grid positions); inr_adjoint_nudft and
- *    its scratch query (its conjugate transpose: off-grid samples back onto the image grid).
+ *    its scratch query (its conjugate transpose: off-grid samples back onto the image grid); inr_plan_image_sets,
+ *    inr_image_sets_after and inr_image_sets_read (weight images on demand: see inr_pack_params).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -222,6 +223,37 @@ int inr_plan_grad_scale_state(const inr_plan* plan, float* host_out, void* strea
 /* Re-orders flat params into the MFMA A-fragment image the kernels stream (no reference
  * counterpart: it is what `model.to(device)` + ATen's GEMM packing do implicitly). */
 int inr_pack_params(const inr_plan* plan, const float* params, float* packed, void* stream);
+
+/* Weight images on demand (no reference counterpart).  Plans whose fused step has two kernels to choose from per batch
+ * (inr_plan_step_info: row_split) keep one family of weight images in `packed` for each: the forward (INR_IMG_FWD) and
+ * transposed (INR_IMG_TR) images of the kernel behind inr_forward / inr_backward and behind steps with row_split == 0,
+ * and the fragment images (INR_IMG_RS) of the row-split kernel.  With INR_LAZY_PACK=1 in the environment (read per call;
+ * unset or 0: every update writes every set) inr_train_adam_step rewrites only the family its own step read and the plan
+ * remembers the others as stale; any later inr_forward, inr_backward, inr_train_step or
+ * inr_train_adam_step whose kernel reads a stale set first re-packs it from `params`, on its own stream -- so these
+ * entries may WRITE to their `packed` argument, with exactly what inr_pack_params would have put there.  Bias tables
+ * are written by every update.  inr_pack_params, inr_adam_step and inr_adam_step_dev write every set.
+ * The state lives in the plan and is keyed to nothing else: between two inr_pack_params calls a plan serves ONE packed
+ * buffer (and one params vector); hand a plan another buffer only through inr_pack_params.  Like a bf16 plan's scale
+ * state it wants the plan stepped from one stream at a time.
+ * A call made while its stream
+ * is capturing a graph changes no state, re-packs what it finds stale inside the graph, and ends the plan's laziness
+ * for good: a replay runs no host code that could notice a stale set.
+ * inr_plan_image_sets: the sets that hold the current parameters, and whether the next update may leave some out.
+ * inr_image_sets_after / inr_image_sets_read: the rules themselves, as pure functions (tests): the valid sets after
+ * `event` happened to `sets`; the sets a call reads. */
+#define INR_IMG_FWD 1
+#define INR_IMG_TR 2
+#define INR_IMG_RS 4
+#define INR_IMG_EV_PACK 0   /* `sets` were written from the current parameters */
+#define INR_IMG_EV_UPDATE 1 /* the parameters moved and only `sets` were rewritten */
+#define INR_IMG_EV_READ 2   /* a call that reads `sets` re-packed the stale ones among them */
+#define INR_IMG_CALL_FORWARD 0
+#define INR_IMG_CALL_BACKWARD 1
+#define INR_IMG_CALL_STEP 2
+int inr_plan_image_sets(const inr_plan* plan, int32_t* valid, int32_t* lazy);
+int inr_image_sets_after(int32_t valid, int32_t event, int32_t sets);
+int inr_image_sets_read(int32_t call, int32_t row_split);
 
 /* Replaces Positional_Encoder.embedding, 'gauss' (networks.py:30-33): out [B, 2E]. */
 int inr_encode_gauss(const float* coords, const float* enc_B, int64_t B, int32_t E, float* out,

@@ -74,6 +74,23 @@ static int launch(const inr_plan* plan, const LossDesc& ld, const inr::MlpArgs& 
   return hip_done(inr::net_kernel(plan->nd)(plan->nd, ld, a, mode, grid, st), "inr mlp kernel launch");
 }
 
+// Row-split plans: the image sets this call's kernel reads must hold the current parameters.  What an earlier lazy update
+// left stale (inr_host.h: img_valid) is re-packed here, on the call's stream, in front of the kernel -- `packed` is the
+// caller's buffer, const to the kernels, rewritten with what a full pack would have put there.
+static int ensure_images(const inr_plan* plan, const float* params, const float* packed, int reads, hipStream_t st,
+                         const char* who) {
+  const int stale = plan->nd.rs ? reads & ~plan->img_valid : 0;
+  if (stale == 0) return INR_OK;
+  inr::AdamArgs aa;
+  memset(&aa, 0, sizeof(aa));
+  aa.skip_sets = inr::IMG_ALL & ~stale;
+  hipError_t e = inr::launch_adam_pack(plan->nd, const_cast<float*>(params), nullptr, nullptr, nullptr,
+                                       const_cast<float*>(packed), aa, st);
+  if (e != hipSuccess) return hip_fail(e, (std::string(who) + ": re-pack of stale weight images").c_str());
+  images_note(plan, IMG_EV_READ, stale, st);
+  return INR_OK;
+}
+
 // ---- the six network calls: one prologue ----
 // Null pointers, the plan's family and what its input needs, in the order every entry has always reported them: plain
 // entries name the family first, the _multi ones the inputs (`need_dist`: forward / backward of a bounded model).
@@ -138,6 +155,8 @@ int inr_forward(const inr_plan* plan, const float* params, const float* packed, 
   if (int rc = begin_call(plan, B, who, &c)) return rc;
   if (saving)
     if (int rc = check_ws(plan, ws, c.nt, 0, who)) return rc;
+  if (int rc = ensure_images(plan, params, packed, image_sets_read(IMG_CALL_FORWARD, false), (hipStream_t)stream, who))
+    return rc;
   inr::MlpArgs a = net_args(params, packed, x, enc_B, B, c, ws);
   a.out = out;
   a.save_by_block = 0;
@@ -202,6 +221,8 @@ int inr_backward(const inr_plan* plan, const float* params, const float* packed,
   CallLayout c;
   if (int rc = begin_call(plan, B, who, &c)) return rc;
   if (int rc = check_ws(plan, ws, c.nt, c.n_slabs, who)) return rc;
+  if (int rc = ensure_images(plan, params, packed, image_sets_read(IMG_CALL_BACKWARD, false), (hipStream_t)stream, who))
+    return rc;
   inr::MlpArgs a = net_args(params, packed, x, enc_B, B, c, ws);
   a.dout = dout;
   a.slabs = ws->slabs;
@@ -290,13 +311,22 @@ static int train_step_impl(const inr_plan* plan, const inr_loss_desc* loss, cons
   CallLayout c;
   if (int rc = begin_call(plan, B, who, &c)) return rc;
   if (int rc = check_ws(plan, ws, c.save_slots, c.n_slabs, who)) return rc;
+  const int reads = image_sets_read(IMG_CALL_STEP, c.rs);
+  if (int rc = ensure_images(plan, params, packed, reads, (hipStream_t)stream, who)) return rc;
   inr::MlpArgs a = net_args(params, packed, x, enc_B, B, c, ws);
   a.gt = gt;
   a.mask = mask;
   if (int rc = step_args(plan, ws, who, &a)) return rc;
   LossDesc ld;
   to_loss_desc(loss, &ld);
-  return run_fused_step(plan, ld, a, c, grads, loss_out, params, packed, (hipStream_t)stream, who, af);
+  if (af == nullptr || grads == nullptr)
+    return run_fused_step(plan, ld, a, c, grads, loss_out, params, packed, (hipStream_t)stream, who, af);
+  // the update writes the images this step's kernel read -- the ones the next step will read -- and leaves the rest stale
+  AdamFuse lazy = *af;
+  lazy.aa.skip_sets = image_sets_skip(plan, reads, (hipStream_t)stream);
+  int rc = run_fused_step(plan, ld, a, c, grads, loss_out, params, packed, (hipStream_t)stream, who, &lazy);
+  if (rc == INR_OK) images_note(plan, IMG_EV_UPDATE, inr::IMG_ALL & ~lazy.aa.skip_sets, (hipStream_t)stream);
+  return rc;
 }
 
 int inr_train_step(const inr_plan* plan, const inr_loss_desc* loss, const float* params, const float* packed,

@@ -74,6 +74,7 @@ int inr_pack_params(const inr_plan* plan, const float* params, float* packed, vo
   aa.do_update = 0;
   hipError_t e = inr::launch_adam_pack(plan->nd, const_cast<float*>(params), nullptr, nullptr, nullptr, packed, aa,
                                        (hipStream_t)stream);
+  if (e == hipSuccess) images_note(plan, IMG_EV_PACK, inr::IMG_ALL, (hipStream_t)stream);
   return hip_done(e, "inr_pack_params");
 }
 
@@ -569,6 +570,7 @@ int inr_adam_step_dev(const inr_plan* plan, float* params, const float* grads, f
   aa.n_sched = n_sched;
   hipError_t e = inr::launch_adam_pack(plan->nd, params, grads, exp_avg, exp_avg_sq, packed, aa, (hipStream_t)stream);
   if (e == hipSuccess) e = inr::launch_step_advance(step_dev, (hipStream_t)stream);
+  if (e == hipSuccess) images_note(plan, IMG_EV_PACK, inr::IMG_ALL, (hipStream_t)stream);
   return hip_done(e, "inr_adam_step_dev");
 }
 
@@ -583,6 +585,7 @@ int inr_adam_step(const inr_plan* plan, float* params, const float* grads, float
   inr::AdamArgs aa = adam_args(beta1, beta2, eps, weight_decay, l1, l2);
   adam_bias_terms(lr, beta1, beta2, step, &aa.step_size, &aa.bc2_sqrt);
   hipError_t e = inr::launch_adam_pack(plan->nd, params, grads, exp_avg, exp_avg_sq, packed, aa, (hipStream_t)stream);
+  if (e == hipSuccess) images_note(plan, IMG_EV_PACK, inr::IMG_ALL, (hipStream_t)stream);
   return hip_done(e, "inr_adam_step");
 }
 

@@ -6,9 +6,15 @@
 namespace inr {
 
 // ---- the tail of a training step (inr_params.hip): slab reduction, Adam + re-pack, penalty gradients ----
+// The weight images of `packed` as three sets (bits): inr_mlp_kernel's forward and transposed images, and the row-split
+// kernel's fragment images.  Bias tables and the bf16 panel stream belong to no set: every update writes them.
+enum { IMG_FWD = 1, IMG_TR = 2, IMG_RS = 4, IMG_ALL = 7 };
+
 struct AdamArgs {
   int do_update;      // 0: pack only
+  int skip_sets;      // IMG_* sets of a row-split plan's images this launch leaves alone (0: every image is written)
   int all_real;       // set by the launcher: every layer is LT_REAL or LT_GABOR_MU (fast scatter path)
+  int flat_order;     // set by the launcher: ... and the layers lie in the flat vector in L[] order (layer_walk, inr_params.hip)
   int has_dead;       // set by the launcher (adam_dead_ranges): some layer has live == 0 ...
   int n_dead;         // ... and its flat entries are these merged ranges [dead_lo, dead_hi); -1: more than fit, walk the layers
   int dead_lo[8], dead_hi[8];

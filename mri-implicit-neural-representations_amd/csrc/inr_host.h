@@ -55,6 +55,14 @@ struct inr_plan {
   mutable bool dz_ready[2] = {false, false};
   mutable int64_t dz_rows[2] = {0, 0};
   mutable int dz_loss[2] = {-1, -1};
+  // Row-split plans keep two families of weight images in `packed`, one per fused kernel, and a step's update writes only
+  // the family its own kernel reads (inr_train_adam_step under INR_LAZY_PACK=1; otherwise all of them).  img_valid = the IMG_* sets
+  // (inr_aux.h) that hold the current parameters; an entry whose kernel reads a stale set re-packs it first, on its stream
+  // (ensure_images, inr_api.hip).  Keyed to nothing: a plan serves ONE packed buffer between two inr_pack_params calls.
+  // Every other plan has one family: always IMG_ALL.  img_eager: a call of this plan has been captured into a graph --
+  // replays run no host code, so from then on every update writes every set (and a capturing call changes no state).
+  mutable int img_valid = inr::IMG_ALL;
+  mutable bool img_eager = false;
   // bf16 GEMM chunking knobs (tuning aids), read from the environment ONCE, when the plan is created: workspace sizes must
   // not depend on what the environment holds at the time of a later call
   bool gemm_one_class = false;
@@ -103,6 +111,24 @@ struct CallLayout {
 void call_layout(const inr_plan* plan, int64_t B, CallLayout* c);
 // B and, from it, the call's layout: the one place an entry learns its tiles, grids, chunks and workspace
 int begin_call(const inr_plan* plan, int64_t B, const char* who, CallLayout* c);
+
+// ---- validity of the weight-image sets (inr_layout.hip: pure; inr_plan.hip: the plan's state) ----
+enum { IMG_EV_PACK = 0, IMG_EV_UPDATE = 1, IMG_EV_READ = 2 };  // what happened to the sets named with it
+enum { IMG_CALL_FORWARD = 0, IMG_CALL_BACKWARD = 1, IMG_CALL_STEP = 2 };
+// the valid sets after `event`: a pack or a read (= re-pack of what was stale) adds `sets`, an update leaves `sets` alone valid
+int image_sets_after(int valid, int event, int sets);
+// the sets a network call of a row-split plan reads: its fused step those of the kernel that runs it (`row_split`),
+// forward and backward inr_mlp_kernel's
+int image_sets_read(int call, bool row_split);
+// INR_LAZY_PACK=1 in the environment (read per call, like INR_RS)
+bool lazy_pack_enabled();
+// is `st` capturing a graph?  (errors count as no)
+bool stream_capturing(hipStream_t st);
+// the sets an update of this call may leave out, given the sets its step reads; 0 where the plan, the switch or a capture
+// says eager
+int image_sets_skip(const inr_plan* plan, int reads, hipStream_t st);
+// after a launch that wrote (`event` PACK / READ) or left only (`event` UPDATE) `sets`: the plan's new state
+void images_note(const inr_plan* plan, int event, int sets, hipStream_t st);
 
 // ---- shared by inr_api.hip and inr_api_aux.hip (defined in the latter) ----
 void to_loss_desc(const inr_loss_desc* l, LossDesc* o);

@@ -202,6 +202,24 @@ void call_layout(const inr_plan* plan, int64_t B, CallLayout* c) {
   }
 }
 
+// ---- weight-image sets: which are valid after an event, which a call reads (no state here: inr_host.h) ----
+int image_sets_after(int valid, int event, int sets) {
+  sets &= inr::IMG_ALL;
+  if (event == IMG_EV_UPDATE) return sets;  // the parameters moved: what the update did not write is stale
+  return (valid | sets) & inr::IMG_ALL;     // a pack, or the re-pack in front of a read
+}
+
+int image_sets_read(int call, bool row_split) {
+  if (call == IMG_CALL_FORWARD) return inr::IMG_FWD;
+  if (call == IMG_CALL_BACKWARD) return inr::IMG_FWD | inr::IMG_TR;  // (inr_mlp_kernel stages the last layer's forward image in every mode)
+  return row_split ? inr::IMG_RS : (inr::IMG_FWD | inr::IMG_TR);
+}
+
+bool lazy_pack_enabled() {
+  const char* e = getenv("INR_LAZY_PACK");
+  return e != nullptr && e[0] == '1';  // opt-in: see DESIGN 4.2 (a recorded hash of `packed` after a step holds every set)
+}
+
 // B and, from it, the call's layout: the one place an entry learns its tiles, grids, chunks and workspace
 int begin_call(const inr_plan* plan, int64_t B, const char* who, CallLayout* c) {
   if (B <= 0) return fail(INR_ERR_INVALID, "%s: B = %lld", who, (long long)B);
@@ -234,6 +252,18 @@ int inr_plan_step_info(const inr_plan* plan, int64_t B, inr_step_info* out) {
   } else {
     out->grid = (int32_t)c.nb, out->rounds = (int32_t)((c.nt + c.nb - 1) / c.nb);
   }
+  return INR_OK;
+}
+
+int inr_image_sets_after(int32_t valid, int32_t event, int32_t sets) { return image_sets_after(valid, event, sets); }
+
+int inr_image_sets_read(int32_t call, int32_t row_split) { return image_sets_read(call, row_split != 0); }
+
+int inr_plan_image_sets(const inr_plan* plan, int32_t* valid, int32_t* lazy) {
+  if (plan == nullptr || valid == nullptr || lazy == nullptr)
+    return fail(INR_ERR_INVALID, "inr_plan_image_sets: null argument");
+  *valid = plan->img_valid;
+  *lazy = plan->nd.rs && !plan->img_eager && lazy_pack_enabled() ? 1 : 0;
   return INR_OK;
 }
 

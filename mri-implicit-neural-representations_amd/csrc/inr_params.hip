@@ -243,6 +243,17 @@ static bool slabs_flat(const NetDesc& nd, const SlabSplit& split) {
          (split.n3 == 0 || ((split.lo3 | split.hi3) & 3) == 0);
 }
 
+// the layers lie in the flat vector in L[] order, weights then bias, without gaps (AdamArgs::flat_order; not the filter
+// networks: state_dict order != L[] order)
+static bool layers_flat_order(const NetDesc& nd) {
+  int off = 0;
+  for (int l = 0; l < nd.ND; ++l) {
+    if (nd.L[l].w_off != off || nd.L[l].b_off != off + nd.L[l].wn) return false;
+    off += nd.L[l].wn + nd.L[l].bn;
+  }
+  return off == nd.P;
+}
+
 hipError_t launch_reduce_slabs(const NetDesc& nd, const float* slabs, int n_blocks, float* grads, float* loss_out,
                                const float* params, const float* packed, hipStream_t st, SlabSplit split) {
   const bool flat = slabs_flat(nd, split);
@@ -333,10 +344,12 @@ __device__ __forceinline__ void put_w2(const NetDesc& nd, int l, float* packed, 
   }
 }
 
-// one flat entry: the Adam update from gradient `g` (do_update); returns the entry's (new) value
-__device__ __forceinline__ float adam_update_entry(const NetDesc& nd, int i, float g, float* __restrict__ params,
-                                                   float* __restrict__ m1, float* __restrict__ m2, const AdamArgs& aa) {
-  float p = params[i];
+// one flat entry: the Adam update from gradient `g` (do_update); returns the entry's (new) value.  `p`, `m`, `v`: the
+// entry's parameter and moments as loaded by the caller (the fused kernel loads them before the slab reduction: their
+// latency hides behind the slab loads instead of following them)
+__device__ __forceinline__ float adam_update_loaded(const NetDesc& nd, int i, float g, float p, float m, float v,
+                                                    float* __restrict__ params, float* __restrict__ m1,
+                                                    float* __restrict__ m2, const AdamArgs& aa) {
   bool live = true;
   if (aa.has_dead) {
     if (aa.n_dead >= 0) {  // (a handful of ranges in kernel arguments: scalar compares -- the walk over 26 layer descriptors
@@ -359,7 +372,6 @@ __device__ __forceinline__ float adam_update_entry(const NetDesc& nd, int i, flo
       step_size = aa.sched[2 * t];
       bc2_sqrt = aa.sched[2 * t + 1];
     }
-    float m = m1[i], v = m2[i];
     m = m + (g - m) * aa.omb1;                // exp_avg.lerp_(grad, 1 - beta1)
     v = fmaf(g * g, aa.omb2, v * aa.beta2);   // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
     const float denom = sqrtf(v) / bc2_sqrt + aa.eps;
@@ -371,24 +383,47 @@ __device__ __forceinline__ float adam_update_entry(const NetDesc& nd, int i, flo
   return p;
 }
 
-// one flat entry: Adam update (adam_update_entry), then its image entries
-__device__ __forceinline__ void adam_pack_entry(const NetDesc& nd, int i, float g, float* __restrict__ params,
-                                                float* __restrict__ m1, float* __restrict__ m2,
-                                                float* __restrict__ packed, const AdamArgs& aa) {
-  const float p = adam_update_entry(nd, i, g, params, m1, m2, aa);
+__device__ __forceinline__ float adam_update_entry(const NetDesc& nd, int i, float g, float* __restrict__ params,
+                                                   float* __restrict__ m1, float* __restrict__ m2, const AdamArgs& aa) {
+  const bool upd = aa.do_update != 0;  // (pack only: there are no moments)
+  return adam_update_loaded(nd, i, g, params[i], upd ? m1[i] : 0.f, upd ? m2[i] : 0.f, params, m1, m2, aa);
+}
+
+// Where a workgroup's 256 consecutive flat entries start looking for their layer: with the layers in flat order (AdamArgs::
+// flat_order: weights then bias, layer after layer) the walk begins at the first layer that ends behind the workgroup's
+// first entry and stops with the one that holds its last -- one or two layers, found once per workgroup with scalar
+// loads, where every entry used to walk the list from the top.  Otherwise: the whole list.
+struct LayerWalk {
+  int l0, i_last;
+};
+__device__ __forceinline__ LayerWalk layer_walk(const NetDesc& nd, const AdamArgs& aa, int first) {
+  LayerWalk lw = {0, 0x7fffffff};
+  if (aa.flat_order) {
+    while (lw.l0 < nd.ND - 1 && nd.L[lw.l0].b_off + nd.L[lw.l0].bn <= first) ++lw.l0;
+    lw.i_last = first + 255;
+  }
+  return lw;
+}
+
+// the image entries of flat entry i, value p -- those of the sets aa.skip_sets leaves out stay as they are (the host marks
+// them stale: inr_host.h)
+__device__ __forceinline__ void pack_entry(const NetDesc& nd, int i, float p, float* __restrict__ packed, const AdamArgs& aa,
+                                           const LayerWalk& lw) {
+  const int skip = aa.skip_sets;
   if (aa.all_real) {  // SIREN / FFN: one weight entry or one bias entry, no sign, no pair
-    for (int l = 0; l < nd.ND; ++l) {
+    for (int l = lw.l0; l < nd.ND; ++l) {  // (l is wave-uniform: the descriptors stay scalar loads)
       const LayerDesc& L = nd.L[l];
       const int off = i - L.w_off;
       if (off >= 0 && off < L.wn) {
-        const int row = off / L.K, k = off - row * L.K;
+        // K a power of two (every hidden layer of the built widths 32 .. 512, every gauss encoder of 2^n phases): a shift
+        const int row = (L.K & (L.K - 1)) == 0 ? off >> (31 - __clz(L.K)) : off / L.K, k = off - row * L.K;
         if (nd.bf16) {  // bf16 plans keep the panel stream only
           put_w2(nd, l, packed, row, k, p);
           return;
         }
-        put_fwd(nd, L, l, packed, row, k, p);
-        if (L.pb_off >= 0) put_tr(L, packed, row, k, p);
-        if (nd.rs) put_rs(nd, L, l, packed, row, k, p);
+        if (!(skip & IMG_FWD)) put_fwd(nd, L, l, packed, row, k, p);
+        if (!(skip & IMG_TR) && L.pb_off >= 0) put_tr(L, packed, row, k, p);
+        if (!(skip & IMG_RS) && nd.rs) put_rs(nd, L, l, packed, row, k, p);
         return;
       }
       const int ob = i - L.b_off;
@@ -399,6 +434,7 @@ __device__ __forceinline__ void adam_pack_entry(const NetDesc& nd, int i, float 
           packed[L.pbias_off + ob] = p;
         return;
       }
+      if (L.b_off + L.bn > lw.i_last) return;  // (flat order: nothing of this workgroup lies behind this layer)
     }
     return;
   }
@@ -413,18 +449,28 @@ __device__ __forceinline__ void adam_pack_entry(const NetDesc& nd, int i, float 
   if (vp.bias_row >= 0) packed[L.pbias_off + vp.bias_row] = p;
 }
 
+// one flat entry: Adam update (adam_update_entry), then its image entries
+__device__ __forceinline__ void adam_pack_entry(const NetDesc& nd, int i, float g, float* __restrict__ params,
+                                                float* __restrict__ m1, float* __restrict__ m2,
+                                                float* __restrict__ packed, const AdamArgs& aa, const LayerWalk& lw) {
+  pack_entry(nd, i, adam_update_entry(nd, i, g, params, m1, m2, aa), packed, aa, lw);
+}
+
 __global__ __launch_bounds__(256) void adam_pack_kernel(const NetDesc nd, float* __restrict__ params,
                                                         const float* __restrict__ grads, float* __restrict__ m1,
                                                         float* __restrict__ m2, float* __restrict__ packed,
                                                         AdamArgs aa) {
   const int i = blockIdx.x * 256 + threadIdx.x;
+  const LayerWalk lw = layer_walk(nd, aa, blockIdx.x * 256);
   if (i >= nd.P) return;
-  adam_pack_entry(nd, i, aa.do_update ? grads[i] : 0.f, params, m1, m2, packed, aa);
+  adam_pack_entry(nd, i, aa.do_update ? grads[i] : 0.f, params, m1, m2, packed, aa, lw);
 }
 
 // reduce_slabs_real_kernel + adam_pack_kernel in one launch (single-rank steps: nothing sits between the reduction and
 // the update).  Same summation (flat_slab_sum), same update arithmetic: bit-identical to the two launches; the gradient
-// is still written (callers read it).  The four waves of a workgroup each take one of a lane's four entries for the update.
+// is still written (callers read it).  After the reduction wave 0 leaves the lanes' sums in LDS as 256 consecutive floats
+// and thread t takes flat entry 256 * block + t: gradient, parameter and both moments are one coalesced 4-byte access per
+// thread and array (each wave used to take every fourth entry: all four waves touched every cache line of all three).
 __global__ __launch_bounds__(256) void reduce_adam_real_kernel(const NetDesc nd, const float* __restrict__ slabs_all,
                                                                int n_blocks_all, float* __restrict__ grads,
                                                                float* __restrict__ loss_out, SlabSplit split,
@@ -432,13 +478,18 @@ __global__ __launch_bounds__(256) void reduce_adam_real_kernel(const NetDesc nd,
                                                                float* __restrict__ m2, float* __restrict__ packed,
                                                                AdamArgs aa) {
   __shared__ f32x4 part[4][64];
-  const int P = nd.P, w = threadIdx.x >> 6;
-  const int i4 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+  __shared__ f32x4 sum4[64];
+  const int P = nd.P, i = blockIdx.x * 256 + threadIdx.x;
+  float p = 0.f, m = 0.f, v = 0.f;
+  if (i < P) p = params[i], m = m1[i], v = m2[i];  // (in flight beside the slab loads)
   const f32x4 t = flat_slab_sum(slabs_all, n_blocks_all, nd.slab_floats, P, split, part);
-  if (i4 < P) {
-    if (w == 0)
-      for (int j = 0; j < 4 && i4 + j < P; ++j) grads[i4 + j] = t[j];
-    if (i4 + w < P) adam_pack_entry(nd, i4 + w, t[w], params, m1, m2, packed, aa);
+  if (threadIdx.x < 64) sum4[threadIdx.x] = t;
+  const LayerWalk lw = layer_walk(nd, aa, blockIdx.x * 256);
+  __syncthreads();
+  if (i < P) {
+    const float g = reinterpret_cast<const float*>(sum4)[threadIdx.x];
+    grads[i] = g;
+    pack_entry(nd, i, adam_update_loaded(nd, i, g, p, m, v, params, m1, m2, aa), packed, aa, lw);
   }
   if (loss_out != nullptr && blockIdx.x == gridDim.x - 1)
     loss_words_sum(slabs_all, n_blocks_all, (size_t)nd.slab_floats, nd.slab_loss_off, loss_out);
@@ -585,6 +636,7 @@ hipError_t launch_adam_pack(const NetDesc& nd, float* params, const float* grads
                             float* packed, const AdamArgs& aa_in, hipStream_t st) {
   AdamArgs aa = aa_in;
   aa.all_real = layers_real(nd, true);
+  aa.flat_order = aa.all_real && layers_flat_order(nd);
   adam_dead_ranges(nd, aa);
   // large plain-layer networks (BASELINE config 4: 4.47 M entries): the update elementwise, then the images in image order
   // (INR_PACK_BY_IMAGE=0 / 1 forces the choice where both exist: the tests hold one against the other)
@@ -624,7 +676,7 @@ hipError_t launch_adam_shard(const NetDesc& nd, float* params, const float* grad
                              int hi, const AdamArgs& aa_in, hipStream_t st) {
   if (hi <= lo) return hipSuccess;
   AdamArgs aa = aa_in;
-  aa.all_real = 0;
+  aa.all_real = aa.flat_order = 0;
   adam_dead_ranges(nd, aa);
   hipLaunchKernelGGL(adam_shard_kernel, dim3((hi - lo + 255) / 256), dim3(256), 0, st, nd, params, grads_shard, m1, m2, lo,
                      hi, aa);
@@ -642,6 +694,7 @@ hipError_t launch_reduce_slabs_adam(const NetDesc& nd, const float* slabs, int n
   }
   AdamArgs aa = aa_in;
   aa.all_real = 1;
+  aa.flat_order = layers_flat_order(nd);
   adam_dead_ranges(nd, aa);
   const int grid = (nd.P + 255) / 256;
   hipLaunchKernelGGL(reduce_adam_real_kernel, dim3(grid + 1), dim3(256), 0, st, nd, slabs, n_blocks, grads, loss_out, split,

@@ -74,6 +74,30 @@ void dz_mark(const inr_plan* p, int kind, int64_t rows, int loss_kind) {
   p->dz_rows[kind] = rows;
   p->dz_loss[kind] = loss_kind;
 }
+// ---- the plan's weight-image state (inr_host.h) ----
+bool stream_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+int image_sets_skip(const inr_plan* plan, int reads, hipStream_t st) {
+  if (!plan->nd.rs) return 0;
+  if (stream_capturing(st)) {
+    plan->img_eager = true;
+    return 0;
+  }
+  return plan->img_eager || !lazy_pack_enabled() ? 0 : (inr::IMG_ALL & ~reads);
+}
+
+void images_note(const inr_plan* plan, int event, int sets, hipStream_t st) {
+  if (!plan->nd.rs) return;
+  if (stream_capturing(st)) {  // nothing ran: the launch lives in a graph, which writes (or re-packs) on every replay
+    plan->img_eager = true;
+    return;
+  }
+  plan->img_valid = image_sets_after(plan->img_valid, event, sets);
+}
+
 // items and the flat-gradient range [lo, hi) of the layers the batch-level dW GEMM covers -- everything of its arguments
 // that no batch changes; false: the plan keeps its in-kernel dW passes
 static bool dw_gemm_items(const NetDesc& nd, inr::DwGemmArgs* g, inr::SlabSplit* split) {

@@ -14,6 +14,9 @@ LIB_PATH = os.environ.get("INR_LIB_PATH") or os.path.join(os.path.dirname(_HERE)
 # enums (include/inr_abi.h)
 KIND_SIREN, KIND_FFN, KIND_WIRE, KIND_FOURIER, KIND_MSFOURIER, KIND_MSBOUNDED, KIND_GABOR, KIND_KGABOR, KIND_WIRE2D = range(9)
 PRECISION_F32, PRECISION_BF16 = 0, 1
+IMG_FWD, IMG_TR, IMG_RS, IMG_ALL = 1, 2, 4, 7  # weight-image sets of a row-split plan (inr_plan_image_sets)
+IMG_EV_PACK, IMG_EV_UPDATE, IMG_EV_READ = 0, 1, 2
+IMG_CALL_FORWARD, IMG_CALL_BACKWARD, IMG_CALL_STEP = 0, 1, 2
 ACT_ID, ACT_SIN, ACT_TANH, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3, 4
 ACT_CTANH = 7  # WIRE2D last_tanh: complex Tanh before .real
 INPUT_X, INPUT_GAUSS = 0, 1
@@ -75,6 +78,9 @@ SYMBOLS = {
     "inr_plan_step_info": (C.c_int, [_P, C.c_int64, C.POINTER(StepInfo)]),
     "inr_plan_grad_scale_state": (C.c_int, [_P, C.POINTER(C.c_float), _P]),
     "inr_pack_params": (C.c_int, [_P, _P, _P, _P]),
+    "inr_plan_image_sets": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "inr_image_sets_after": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "inr_image_sets_read": (C.c_int, [C.c_int32, C.c_int32]),
     "inr_encode_gauss": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     "inr_encode_logf": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     "inr_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, C.POINTER(Workspace), _P]),
