@@ -53,7 +53,9 @@ extern "C" {
  *    query and inr_coil_apply (software coil compression: the coil Gram matrix in one pass, the product with a small matrix);
  *    inr_nudft and its scratch query (the continuous k-space of coil images at off-grid positions); inr_adjoint_nudft and
  *    its scratch query (its conjugate transpose: off-grid samples back onto the image grid); inr_plan_image_sets,
- *    inr_image_sets_after and inr_image_sets_read (weight images on demand: see inr_pack_params).
+ *    inr_image_sets_after and inr_image_sets_read (weight images on demand: see inr_pack_params); inr_nufft_prepare,
+ *    inr_nufft_interp, inr_nufft_spread, inr_nufft_finish and their scratch query (the same two operators by
+ *    Kaiser-Bessel gridding around the caller's FFT).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -595,6 +597,56 @@ int inr_nudft(const float* img, int32_t C, int64_t H, int64_t W, const double* p
 int inr_adjoint_nudft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats);
 int inr_adjoint_nudft(const float* val, const double* pos, const float* w, int32_t C, int64_t H, int64_t W, int64_t M,
                       float* out, float* scratch, int64_t scratch_floats, void* stream);
+
+/* (v7 addition) Table-based (Kaiser-Bessel) gridding: inr_nudft and inr_adjoint_nudft approximated in O(M J^2) device work
+ * around an FFT of the twice oversampled grid that the CALLER runs between the calls -- the library does not link an FFT
+ * (no reference counterpart).  Fixed parameters: Gy = 2 H, Gx = 2 W; J = INR_NUFFT_TAPS = 6 taps
+ * per axis; kb(t) = I0(beta sqrt(1 - (2 t / J)^2)) / I0(beta) on |t| <= J / 2, beta = pi sqrt((J / 2)^2 (3 / 2)^2 - 0.8).
+ * A sample at pos = (u_y, u_x) sits at g = 2 (u - c) + G / 2 per axis (c = n / 2, integer division; fp64, reduced into
+ * [0, G): the operators are periodic in u); its taps are the cells j0 .. j0 + 5, j0 = ceil(g - 3), modulo G, with
+ * weights kb(g - j) evaluated in fp64 and stored as fp32.  apod_y [H], apod_x [W] (device, fp32): the apodisation
+ * a(nu) = J sinh(s) / (s I0(beta)), s = sqrt(beta^2 - (pi J nu)^2), at nu = (y - c) / G, evaluated by the caller in fp64.
+ *
+ *   forward, the approximation of inr_nudft:
+ *     inr_nufft_prepare  img [C][H][W][2] -> grid [C][Gy][Gx][2]: img[c][y][x] * 2 / (apod_y[y] apod_x[x]) at
+ *                        (y - c_y + H, x - c_x + W), zero elsewhere; every element of grid is written
+ *     (caller)           the centred orthonormal FFT of every [Gy][Gx] plane
+ *     inr_nufft_interp   grid, pos [M][2] -> out [C][M][2]: the 36 taps of every sample, summed in the order ky, kx
+ *   adjoint with weights, the approximation of inr_adjoint_nudft:
+ *     inr_nufft_spread   val [C][M][2], pos, w [M] or null -> grid: grid[c][j] = sum over the samples with a tap on cell j
+ *                        of kb_y kb_x w[m] val[c][m]; a gather over a cell list, no atomics; every element is written
+ *     (caller)           the centred orthonormal inverse FFT of every plane
+ *     inr_nufft_finish   grid -> out [C][H][W][2]: the centre H x W times 2 / (apod_y[y] apod_x[x])
+ * In exact arithmetic the two chains are conjugate transposes of each other (the 2 is sqrt(Gy Gx) / sqrt(H W)).  Sums have
+ * a fixed order: two calls give the same bits.
+ * The cell list of inr_nufft_spread: bins of INR_NUFFT_TILE x INR_NUFFT_TILE grid cells, T = ceil(Gy / 16) ceil(Gx / 16)
+ * of them, bin (floor(g_y) / 16) * ceil(Gx / 16) + floor(g_x) / 16 for a sample; order [M] (int32): the sample indices
+ * sorted by bin, ascending within a bin; bin_start [T + 1] (int32): bin b is order[bin_start[b] .. bin_start[b + 1]).
+ * inr_mi355x/trajectory.py::nufft_bins builds them.  Both are device-readable and TRUSTED: where they are host-visible
+ * (pinned host memory) bin_start is checked -- bin_start[0] = 0, non-decreasing, bin_start[T] = M -- and refused with
+ * INR_ERR_INVALID; otherwise the kernel clamps what it reads of them (entries of bin_start into [0, M]; an order[] entry
+ * outside [0, M) adds zeros), so that malformed arrays lose samples but read nothing out of bounds.
+ * `scratch` (device, 16-byte aligned; interp and spread) holds at least what inr_nufft_scratch gives for (C, H, W, M):
+ * 14 M' floats, M' = M rounded up to 64 -- the taps, which every call writes anew, once for all coils.
+ * prepare, finish: one launch; interp, spread: two.  All on `stream`, nothing allocated, nothing read back.
+ * inr_mi355x/trajectory.py::nufft_numpy / nufft_adjoint_numpy restate the two chains in fp64.
+ * INR_ERR_INVALID before any launch: a null pointer other than w; C outside 1..INR_COIL_MAX; H or W < 3 (six taps must
+ * land on six cells); H * W >= 2^31; M < 1 or M >= 2^31; img / val / pos / out not 8-byte, grid or scratch not 16-byte,
+ * w / apod_y / apod_x / bin_start / order not 4-byte aligned; scratch short of the query; an output (grid, out) that
+ * overlaps an input of the same call; scratch overlapping any of the call's arrays; a host-visible bin_start that fails
+ * the check above. */
+#define INR_NUFFT_TAPS 6
+#define INR_NUFFT_TILE 16
+int inr_nufft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats);
+int inr_nufft_prepare(const float* img, const float* apod_y, const float* apod_x, int32_t C, int64_t H, int64_t W,
+                      float* grid, void* stream);
+int inr_nufft_interp(const float* grid, const double* pos, int32_t C, int64_t H, int64_t W, int64_t M, float* out,
+                     float* scratch, int64_t scratch_floats, void* stream);
+int inr_nufft_spread(const float* val, const double* pos, const float* w, const int32_t* bin_start, const int32_t* order,
+                     int32_t C, int64_t H, int64_t W, int64_t M, float* grid, float* scratch, int64_t scratch_floats,
+                     void* stream);
+int inr_nufft_finish(const float* grid, const float* apod_y, const float* apod_x, int32_t C, int64_t H, int64_t W,
+                     float* out, void* stream);
 
 #ifdef __cplusplus
 }

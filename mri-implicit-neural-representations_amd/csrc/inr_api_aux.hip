@@ -1,5 +1,5 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network: encoders, losses, TV, Adam,
-// image metrics, display, shuffle, grid rows, band statistics, coil compression, off-grid sampling and its adjoint.  Each checks its arguments, fills an argument struct,
+// image metrics, display, shuffle, grid rows, band statistics, coil compression, off-grid sampling, its adjoint and their gridding form.  Each checks its arguments, fills an argument struct,
 // launches and maps the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -548,6 +548,134 @@ int inr_adjoint_nudft(const float* val, const double* pos, const float* w, int32
     return fail(INR_ERR_INVALID, "inr_adjoint_nudft: scratch overlaps val, pos, w or out");
   hipError_t e = inr::launch_adjoint_nudft(val, pos, w, C, (int)H, (int)W, M, out, scratch, (hipStream_t)stream);
   return hip_done(e, "inr_adjoint_nudft");
+}
+
+// ---- the same two operators by Kaiser-Bessel gridding around the caller's FFT (inr_nufft.hip) ----
+static_assert(INR_NUFFT_TILE == inr::NUFFT_TILE && INR_NUFFT_TAPS == inr::NUFFT_TAPS, "inr_abi.h and inr_aux.h disagree");
+
+static int nufft_check(int32_t C, int64_t H, int64_t W, int64_t M, const char* who) {
+  if (int rc = nudft_check(C, H, W, M, who)) return rc;
+  if (H < INR_NUFFT_TAPS / 2 || W < INR_NUFFT_TAPS / 2)  // on 2 n < 6 cells two taps of a sample would share a cell
+    return fail(INR_ERR_INVALID, "%s: H = %lld, W = %lld (each >= %d)", who, (long long)H, (long long)W, INR_NUFFT_TAPS / 2);
+  return INR_OK;
+}
+
+static int nufft_scratch_check(const float* scratch, int64_t scratch_floats, int64_t M, const char* who) {
+  if (((uintptr_t)scratch & 15u) != 0) return fail(INR_ERR_INVALID, "%s: scratch is not 16-byte aligned", who);
+  const int64_t need = inr::nufft_scratch_floats(M);
+  if (scratch_floats < need)
+    return fail(INR_ERR_INVALID, "%s: scratch holds %lld floats, M = %lld needs %lld", who, (long long)scratch_floats,
+                (long long)M, (long long)need);
+  return INR_OK;
+}
+
+// bin_start where the host can read it (pinned host memory): 0 = bin_start[0] <= ... <= bin_start[T] = M
+static int nufft_bins_check(const int32_t* bin_start, int64_t T, int64_t M) {
+  hipPointerAttribute_t attr;
+  memset(&attr, 0, sizeof(attr));
+  if (hipPointerGetAttributes(&attr, bin_start) != hipSuccess) {
+    (void)hipGetLastError();  // a pointer the runtime does not know: nothing to check here
+    return INR_OK;
+  }
+  if (attr.type != hipMemoryTypeHost || attr.hostPointer == nullptr) return INR_OK;
+  const int32_t* b = static_cast<const int32_t*>(attr.hostPointer);
+  bool ok = b[0] == 0 && b[T] == M;
+  for (int64_t i = 0; ok && i < T; ++i) ok = b[i] <= b[i + 1];
+  if (!ok)
+    return fail(INR_ERR_INVALID, "inr_nufft_spread: bin_start is not 0 = b[0] <= ... <= b[%lld] = %lld", (long long)T,
+                (long long)M);
+  return INR_OK;
+}
+
+int inr_nufft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats) {
+  if (scratch_floats == nullptr) return fail(INR_ERR_INVALID, "inr_nufft_scratch: null argument");
+  if (int rc = nufft_check(C, H, W, M, "inr_nufft_scratch")) return rc;
+  *scratch_floats = inr::nufft_scratch_floats(M);
+  return INR_OK;
+}
+
+// prepare and finish: the image [C][H][W][2], the grid [C][2H][2W][2], the two apodisation vectors
+static int nufft_image_grid_check(const float* image, const float* grid, const float* apod_y, const float* apod_x, int32_t C,
+                                  int64_t H, int64_t W, bool grid_is_output, const char* who) {
+  if (image == nullptr || grid == nullptr || apod_y == nullptr || apod_x == nullptr)
+    return fail(INR_ERR_INVALID, "%s: null argument", who);
+  if (int rc = nufft_check(C, H, W, 1, who)) return rc;
+  if (((uintptr_t)image & 7u) != 0) return fail(INR_ERR_INVALID, "%s: %s is not 8-byte aligned", who, grid_is_output ? "img" : "out");
+  if (((uintptr_t)grid & 15u) != 0) return fail(INR_ERR_INVALID, "%s: grid is not 16-byte aligned", who);
+  if ((((uintptr_t)apod_y | (uintptr_t)apod_x) & 3u) != 0)
+    return fail(INR_ERR_INVALID, "%s: apod_y / apod_x is not 4-byte aligned", who);
+  const int64_t image_bytes = (int64_t)C * H * W * 8, grid_bytes = 4 * image_bytes;
+  const void* out = grid_is_output ? grid : image;
+  const int64_t out_bytes = grid_is_output ? grid_bytes : image_bytes;
+  if (ranges_overlap(grid, grid_bytes, image, image_bytes) || ranges_overlap(out, out_bytes, apod_y, H * 4) ||
+      ranges_overlap(out, out_bytes, apod_x, W * 4))
+    return fail(INR_ERR_INVALID, "%s: the output overlaps an input", who);
+  return INR_OK;
+}
+
+int inr_nufft_prepare(const float* img, const float* apod_y, const float* apod_x, int32_t C, int64_t H, int64_t W,
+                      float* grid, void* stream) {
+  if (int rc = nufft_image_grid_check(img, grid, apod_y, apod_x, C, H, W, true, "inr_nufft_prepare")) return rc;
+  hipError_t e = inr::launch_nufft_prepare(img, apod_y, apod_x, C, (int)H, (int)W, grid, (hipStream_t)stream);
+  return hip_done(e, "inr_nufft_prepare");
+}
+
+int inr_nufft_finish(const float* grid, const float* apod_y, const float* apod_x, int32_t C, int64_t H, int64_t W,
+                     float* out, void* stream) {
+  if (int rc = nufft_image_grid_check(out, grid, apod_y, apod_x, C, H, W, false, "inr_nufft_finish")) return rc;
+  hipError_t e = inr::launch_nufft_finish(grid, apod_y, apod_x, C, (int)H, (int)W, out, (hipStream_t)stream);
+  return hip_done(e, "inr_nufft_finish");
+}
+
+int inr_nufft_interp(const float* grid, const double* pos, int32_t C, int64_t H, int64_t W, int64_t M, float* out,
+                     float* scratch, int64_t scratch_floats, void* stream) {
+  if (grid == nullptr || pos == nullptr || out == nullptr || scratch == nullptr)
+    return fail(INR_ERR_INVALID, "inr_nufft_interp: null argument");
+  if (int rc = nufft_check(C, H, W, M, "inr_nufft_interp")) return rc;
+  if ((((uintptr_t)pos | (uintptr_t)out) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_nufft_interp: pos / out is not 8-byte aligned");
+  if (((uintptr_t)grid & 15u) != 0) return fail(INR_ERR_INVALID, "inr_nufft_interp: grid is not 16-byte aligned");
+  if (int rc = nufft_scratch_check(scratch, scratch_floats, M, "inr_nufft_interp")) return rc;
+  const int64_t grid_bytes = (int64_t)C * H * W * 32, pos_bytes = M * 16, out_bytes = (int64_t)C * M * 8,
+                scratch_bytes = inr::nufft_scratch_floats(M) * 4;
+  if (ranges_overlap(out, out_bytes, grid, grid_bytes) || ranges_overlap(out, out_bytes, pos, pos_bytes))
+    return fail(INR_ERR_INVALID, "inr_nufft_interp: out overlaps grid or pos");
+  if (ranges_overlap(scratch, scratch_bytes, out, out_bytes) || ranges_overlap(scratch, scratch_bytes, grid, grid_bytes) ||
+      ranges_overlap(scratch, scratch_bytes, pos, pos_bytes))
+    return fail(INR_ERR_INVALID, "inr_nufft_interp: scratch overlaps grid, pos or out");
+  hipError_t e = inr::launch_nufft_interp(grid, pos, C, (int)H, (int)W, M, out, scratch, (hipStream_t)stream);
+  return hip_done(e, "inr_nufft_interp");
+}
+
+int inr_nufft_spread(const float* val, const double* pos, const float* w, const int32_t* bin_start, const int32_t* order,
+                     int32_t C, int64_t H, int64_t W, int64_t M, float* grid, float* scratch, int64_t scratch_floats,
+                     void* stream) {
+  if (val == nullptr || pos == nullptr || bin_start == nullptr || order == nullptr || grid == nullptr || scratch == nullptr)
+    return fail(INR_ERR_INVALID, "inr_nufft_spread: null argument");
+  if (int rc = nufft_check(C, H, W, M, "inr_nufft_spread")) return rc;
+  if ((((uintptr_t)val | (uintptr_t)pos) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_nufft_spread: val / pos is not 8-byte aligned");
+  if ((((uintptr_t)w | (uintptr_t)bin_start | (uintptr_t)order) & 3u) != 0)
+    return fail(INR_ERR_INVALID, "inr_nufft_spread: w / bin_start / order is not 4-byte aligned");
+  if (((uintptr_t)grid & 15u) != 0) return fail(INR_ERR_INVALID, "inr_nufft_spread: grid is not 16-byte aligned");
+  if (int rc = nufft_scratch_check(scratch, scratch_floats, M, "inr_nufft_spread")) return rc;
+  const int64_t T = inr::nufft_bin_count(H, W);
+  const int64_t grid_bytes = (int64_t)C * H * W * 32, scratch_bytes = inr::nufft_scratch_floats(M) * 4;
+  const void* in[5] = {val, pos, w, bin_start, order};
+  const int64_t in_bytes[5] = {(int64_t)C * M * 8, M * 16, w != nullptr ? M * 4 : 0, (T + 1) * 4, M * 4};
+  for (int i = 0; i < 5; ++i) {
+    if (in[i] == nullptr) continue;
+    if (ranges_overlap(grid, grid_bytes, in[i], in_bytes[i]))
+      return fail(INR_ERR_INVALID, "inr_nufft_spread: grid overlaps val, pos, w, bin_start or order");
+    if (ranges_overlap(scratch, scratch_bytes, in[i], in_bytes[i]))
+      return fail(INR_ERR_INVALID, "inr_nufft_spread: scratch overlaps val, pos, w, bin_start or order");
+  }
+  if (ranges_overlap(scratch, scratch_bytes, grid, grid_bytes))
+    return fail(INR_ERR_INVALID, "inr_nufft_spread: scratch overlaps grid");
+  if (int rc = nufft_bins_check(bin_start, T, M)) return rc;
+  hipError_t e = inr::launch_nufft_spread(val, pos, w, bin_start, order, C, (int)H, (int)W, M, grid, scratch,
+                                          (hipStream_t)stream);
+  return hip_done(e, "inr_nufft_spread");
 }
 
 int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* host_out) {

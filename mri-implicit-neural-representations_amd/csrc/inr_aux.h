@@ -203,4 +203,22 @@ long long adjoint_nudft_scratch_floats(long long H, long long W, long long M);
 hipError_t launch_adjoint_nudft(const float* val, const double* pos, const float* w, int C, int H, int W, long long M,
                                 float* out, float* scratch, hipStream_t st);
 
+// table-based (Kaiser-Bessel) gridding of the same two operators (inr_nufft.hip): oversampling 2, six
+// taps per axis; the FFT between prepare and interp, and between spread and finish, is the caller's
+constexpr int NUFFT_TAPS = 6;   // INR_NUFFT_TAPS
+constexpr int NUFFT_TILE = 16;  // INR_NUFFT_TILE: grid cells per edge of a spread tile and of a bin
+inline long long nufft_bin_count(long long H, long long W) {
+  return ((2 * H + NUFFT_TILE - 1) / NUFFT_TILE) * ((2 * W + NUFFT_TILE - 1) / NUFFT_TILE);
+}
+long long nufft_scratch_floats(long long M);
+hipError_t launch_nufft_prepare(const float* img, const float* apod_y, const float* apod_x, int C, int H, int W,
+                                float* grid, hipStream_t st);
+hipError_t launch_nufft_finish(const float* grid, const float* apod_y, const float* apod_x, int C, int H, int W,
+                               float* out, hipStream_t st);
+hipError_t launch_nufft_interp(const float* grid, const double* pos, int C, int H, int W, long long M, float* out,
+                               float* scratch, hipStream_t st);
+hipError_t launch_nufft_spread(const float* val, const double* pos, const float* w, const int* bin_start,
+                               const int* order, int C, int H, int W, long long M, float* grid, float* scratch,
+                               hipStream_t st);
+
 }  // namespace inr

@@ -132,6 +132,11 @@ SYMBOLS = {
     "inr_nudft": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     "inr_adjoint_nudft_scratch": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_adjoint_nudft": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
+    "inr_nufft_scratch": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "inr_nufft_prepare": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
+    "inr_nufft_interp": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
+    "inr_nufft_spread": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
+    "inr_nufft_finish": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
 }
 NUDFT_TILE = 64  # INR_NUDFT_TILE
 COIL_MAX, COIL_TILE_PIXELS = 32, 128  # INR_COIL_MAX, INR_COIL_TILE_PIXELS

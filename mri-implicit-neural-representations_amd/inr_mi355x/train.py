@@ -14,7 +14,7 @@ CLI (same flags as the reference, train.py:255-258):
     python -m inr_mi355x.train --config cfg.yaml [--output_path out] [--synthetic C,H,W] [--val]
                                [--shuffle] [--shuffle-seed S] [--save-images] [--band-report [N]] [--virtual-coils K]
                                [--trajectory ARG] [--trajectory-baseline ARG] [--trajectory-density ARG]
-                               [--data_samples samples.yaml]
+                               [--trajectory-operator ARG] [--data_samples samples.yaml]
 --val runs the reference's validation epoch every config['val_epoch'] epochs (its line is printed) and saves a
 checkpoint every config['image_save_epoch'] epochs.  --save-images (with --val) also writes the reference's pictures
 (train.png, train_kspace.png, recon_kspace_{e}dB.png, recon_kspace_{e}_error.png, recon_{e}_{psnr}_psnr_{ssim}_ssim.png)

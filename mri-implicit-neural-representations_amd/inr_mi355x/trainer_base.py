@@ -31,6 +31,7 @@ def set_default_configs(config: dict) -> dict:
     config.setdefault("trajectory", "none")  # trajectory.py: train on off-grid k-space samples; "none" = off
     config.setdefault("trajectory_baseline", "none")  # ... and reconstruct them conventionally too: adjoint | cg-N
     config.setdefault("trajectory_density", None)  # the baseline's density weights; None: ramp (spokes) / uniform (file)
+    config.setdefault("trajectory_operator", None)  # the baseline's operator pair: exact | gridding; None: exact, unrecorded
     return config
 
 
@@ -119,6 +120,12 @@ class ResidentFit(ValidationMixin):
             raise ValueError(f"config['trajectory_baseline'] = {config['trajectory_baseline']!r} / ['trajectory_density'] = "
                              f"{config['trajectory_density']!r} without config['trajectory']: there are no off-grid "
                              "samples to reconstruct")
+        # config['trajectory_operator'] belongs to the baseline; the training samples stay exact
+        from .trajectory import parse_operator
+        self.trajectory_operator = parse_operator(config["trajectory_operator"])
+        if self.trajectory_operator is not None and self.trajectory_baseline is None:
+            raise ValueError(f"config['trajectory_operator'] = {config['trajectory_operator']!r} without "
+                             "config['trajectory_baseline']: it selects the operator inside the baseline only")
         if self.trajectory is not None and (self.trajectory_baseline is not None or config["trajectory_density"] is not None):
             self.trajectory_density = parse_density(config["trajectory_density"], self.trajectory, int(shape[1]),
                                                     int(shape[2]))
@@ -206,7 +213,8 @@ class ResidentFit(ValidationMixin):
     def _gridding_baseline(self) -> None:
         """config['trajectory_baseline']: the conventional reconstruction of the samples the fit trains
         on -- the density-weighted adjoint or N conjugate-gradient iterations (trajectory.cg_baseline) -- made once, scored
-        as validation scores the fit (RSS, then PSNR / SSIM against the full data, on the device).  Leaves the record in
+        as validation scores the fit (RSS, then PSNR / SSIM against the full data, on the device), with the exact operator
+        pair or, under config['trajectory_operator'] = "gridding" (DESIGN.md 4.21), the Kaiser-Bessel pair.  Leaves the record in
         self.gridding and the coil images [C,H,W,2] in self.gridding_image; reads no random numbers and no parameter."""
         import time
         from .trajectory import cg_baseline, positions
@@ -215,7 +223,8 @@ class ResidentFit(ValidationMixin):
         name, w = self.trajectory_density
         torch.cuda.synchronize(self.device)
         t0 = time.time()
-        iterates, objective = cg_baseline(self.train_values, positions(self.trajectory, H, W), (C, H, W), w, iters)
+        iterates, objective = cg_baseline(self.train_values, positions(self.trajectory, H, W), (C, H, W), w, iters,
+                                          operator=self.trajectory_operator or "exact")
         self.gridding_image = iterates[-1].contiguous()
         torch.cuda.synchronize(self.device)
         seconds = time.time() - t0
@@ -225,6 +234,8 @@ class ResidentFit(ValidationMixin):
         psnr_, ssim_ = m[:2].cpu().tolist()
         self.gridding = {"mode": mode, "iters": iters, "density": name, "psnr": psnr_, "ssim": ssim_,
                          "objective": [float(v) for v in objective], "seconds": seconds}
+        if self.trajectory_operator is not None:  # the key was given: say which pair made the numbers above
+            self.gridding["operator"] = self.trajectory_operator
 
     @torch.no_grad()
     def save_gridding_image(self, directory: str, prefix: str = "") -> str:

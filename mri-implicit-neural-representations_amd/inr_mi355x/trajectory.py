@@ -18,6 +18,9 @@ and forms phasors and sums in fp32.
 ``nudft_adjoint`` (inr_adjoint_nudft, csrc/inr_nudft_adjoint.hip) is the conjugate transpose, with optional
 density weights; ``cg_baseline`` builds the conventional density-weighted conjugate-gradient reconstruction from the two,
 which config['trajectory_baseline'] prints next to the fit's score.
+
+``nufft`` / ``nufft_adjoint`` (inr_nufft_*, csrc/inr_nufft.hip) approximate the same two operators by
+Kaiser-Bessel gridding around torch.fft; config['trajectory_operator'] = "gridding" puts them inside the baseline.
 """
 from __future__ import annotations
 
@@ -305,6 +308,299 @@ def nudft_adjoint(val: torch.Tensor, pos, shape, weights=None, scratch: Optional
     return out
 
 
+# ---- the same operators by Kaiser-Bessel gridding (inr_nufft_*, csrc/inr_nufft.hip) -------------------
+# Fixed: oversampling 2 (G = 2 n per axis), NUFFT_TAPS = 6 taps per axis, kb(t) = I0(beta sqrt(1 - (2t/J)^2)) / I0(beta)
+# on |t| <= J/2 with Beatty's beta.  A sample at u sits at g = 2 (u - c) + G/2 (fp64, reduced into [0, G)); its taps are
+# the cells j0 .. j0 + 5, j0 = ceil(g - 3), modulo G, with weights kb(g - j) rounded to fp32.
+#   forward:  img * 2 / (a_y a_x), centred in the zero Gy x Gx grid -> centred orthonormal FFT -> 36 taps per sample
+#   adjoint:  w * val spread onto the grid by the same taps -> centred orthonormal inverse FFT -> centre H x W times
+#             2 / (a_y a_x)
+# with a(nu) the continuous Fourier transform of kb at nu = (y - c) / G and 2 = sqrt(Gy Gx) / sqrt(H W).
+NUFFT_TAPS = 6   # INR_NUFFT_TAPS
+NUFFT_TILE = 16  # INR_NUFFT_TILE: grid cells per edge of a spread tile and of a bin
+NUFFT_BETA = math.pi * math.sqrt((NUFFT_TAPS / 2.0) ** 2 * 1.5 ** 2 - 0.8)
+_I0_TERMS = 40  # of the power series: the first neglected term is below 1e-19 of the sum at beta
+
+
+def _i0(x: np.ndarray) -> np.ndarray:
+    """I0 by its power series sum_k (x^2/4)^k / (k!)^2, the text of the kernel's bessel_i0 (0 <= x <= NUFFT_BETA)"""
+    q = 0.25 * np.asarray(x, dtype=np.float64) ** 2
+    term, total = np.ones_like(q), np.ones_like(q)
+    for k in range(1, _I0_TERMS + 1):
+        term = term * (q * (1.0 / (float(k) * float(k))))
+        total = total + term
+    return total
+
+
+def nufft_kernel(t) -> np.ndarray:
+    """kb(t) in fp64; zero outside |t| <= J/2"""
+    t = np.asarray(t, dtype=np.float64) * (2.0 / NUFFT_TAPS)
+    r = np.maximum(0.0, 1.0 - t * t)
+    return np.where(np.abs(t) <= 1.0, _i0(NUFFT_BETA * np.sqrt(r)) * (1.0 / _i0(np.float64(NUFFT_BETA))), 0.0)
+
+
+def nufft_apodisation(n: int) -> np.ndarray:
+    """fp32 [n]: a((y - c) / G) = J sinh(s) / (s I0(beta)), s = sqrt(beta^2 - (pi J nu)^2), evaluated in fp64.  |nu| <= 1/4,
+    so s is real (pi J / 4 < beta)."""
+    n = int(n)
+    nu = (np.arange(n, dtype=np.float64) - n // 2) / (2.0 * n)
+    s = np.sqrt(NUFFT_BETA ** 2 - (math.pi * NUFFT_TAPS * nu) ** 2)
+    return (NUFFT_TAPS * np.sinh(s) / (s * _i0(np.float64(NUFFT_BETA)))).astype(np.float32)
+
+
+def _nufft_grid_position(u: np.ndarray, n: int) -> np.ndarray:
+    """g in [0, G), the operations of the kernel's axis_taps in the same order"""
+    G = 2.0 * n
+    g = 2.0 * (u - float(n // 2)) + float(n)
+    g = g - G * np.floor(g / G)
+    g = np.where(g >= G, g - G, g)
+    return np.where((g >= 0.0) & (g < G), g, 0.0)
+
+
+def nufft_taps(u, n: int):
+    """(j0 int64 [M], weights fp32 [M, 6]) of the positions ``u`` [M] along an axis of n points"""
+    g = _nufft_grid_position(np.asarray(u, dtype=np.float64), int(n))
+    first = np.ceil(g - 0.5 * NUFFT_TAPS)
+    t = g[:, None] - (first[:, None] + np.arange(NUFFT_TAPS, dtype=np.float64)[None, :])
+    return first.astype(np.int64), nufft_kernel(t).astype(np.float32)
+
+
+def _nufft_check_shape(H: int, W: int) -> None:
+    if H < NUFFT_TAPS // 2 or W < NUFFT_TAPS // 2:
+        raise ValueError(f"nufft: H = {H}, W = {W} (each >= {NUFFT_TAPS // 2}: six taps must land on six cells of 2 n)")
+
+
+def _nufft_cells(pos, H: int, W: int):
+    """(iy [M, 6], ix [M, 6] wrapped cell indices, wy, wx [M, 6] fp64 copies of the fp32 weights)"""
+    jy, wy = nufft_taps(pos[:, 0], H)
+    jx, wx = nufft_taps(pos[:, 1], W)
+    k = np.arange(NUFFT_TAPS)[None, :]
+    return (jy[:, None] + k) % (2 * H), (jx[:, None] + k) % (2 * W), wy.astype(np.float64), wx.astype(np.float64)
+
+
+def _deapodisation(H: int, W: int) -> np.ndarray:
+    """[H, W] fp64: 2 / (a_y a_x) of the fp32-stored apodisation vectors"""
+    return 2.0 / (nufft_apodisation(H).astype(np.float64)[:, None] * nufft_apodisation(W).astype(np.float64)[None, :])
+
+
+def _fftc_numpy(z: np.ndarray, inverse: bool) -> np.ndarray:
+    z = np.fft.ifftshift(z, axes=(-2, -1))
+    z = (np.fft.ifft2 if inverse else np.fft.fft2)(z, axes=(-2, -1), norm="ortho")
+    return np.fft.fftshift(z, axes=(-2, -1))
+
+
+def nufft_numpy(img, pos) -> np.ndarray:
+    """[C, M] complex128: the gridding approximation of nudft_numpy, every step in fp64 (the tap weights and the
+    apodisation vectors are the fp32 numbers the device uses)"""
+    from .coils import _as_complex
+    z = np.asarray(_as_complex(img)).astype(np.complex128)
+    if z.ndim == 2:
+        z = z[None]
+    pos = check_positions(np.asarray(pos, dtype=np.float64))
+    Cn, H, W = z.shape
+    _nufft_check_shape(H, W)
+    grid = np.zeros((Cn, 2 * H, 2 * W), dtype=np.complex128)
+    y0, x0 = H - H // 2, W - W // 2
+    grid[:, y0:y0 + H, x0:x0 + W] = z * _deapodisation(H, W)[None]
+    grid = _fftc_numpy(grid, False)
+    iy, ix, wy, wx = _nufft_cells(pos, H, W)
+    cells = grid[:, iy[:, :, None], ix[:, None, :]]  # [C, M, 6, 6]
+    return np.einsum("cmyx,my,mx->cm", cells, wy, wx)
+
+
+def nufft_adjoint_numpy(val, pos, H: int, W: int, weights=None) -> np.ndarray:
+    """[C, H, W] complex128: the gridding approximation of nudft_adjoint_numpy and the exact conjugate transpose of
+    nufft_numpy applied to weights * val"""
+    v = _samples_complex(val)
+    pos = check_positions(np.asarray(pos, dtype=np.float64))
+    H, W = int(H), int(W)
+    _nufft_check_shape(H, W)
+    if v.shape[1] != pos.shape[0]:
+        raise ValueError(f"samples {v.shape} and positions {pos.shape} disagree")
+    v = v * _weights_numpy(weights, pos.shape[0])[None, :]
+    iy, ix, wy, wx = _nufft_cells(pos, H, W)
+    grid = np.zeros((v.shape[0], 2 * H, 2 * W), dtype=np.complex128)
+    contrib = v[:, :, None, None] * (wy[:, :, None] * wx[:, None, :])[None]  # [C, M, 6, 6]
+    for c in range(v.shape[0]):
+        np.add.at(grid[c], (np.broadcast_to(iy[:, :, None], contrib.shape[1:]),
+                            np.broadcast_to(ix[:, None, :], contrib.shape[1:])), contrib[c])
+    grid = _fftc_numpy(grid, True)
+    y0, x0 = H - H // 2, W - W // 2
+    return grid[:, y0:y0 + H, x0:x0 + W] * _deapodisation(H, W)[None]
+
+
+def nufft_tile_bins(tile: int, G: int) -> list:
+    """The reach rule of inr_nufft_spread along one axis: the bins, ascending, that a tile of cells
+    [16 tile, min(16 tile + 15, G - 1)] walks.  A sample is binned by the cell floor(g); its taps lie in
+    floor(g) - 3 .. floor(g) + 3 (j0 = ceil(g - 3) is floor(g) - 2, or floor(g) - 3 at an integer g), so the tile needs
+    every bin that holds a cell of [lo - 3, hi + 3] modulo G: at most four, a narrow last bin included."""
+    lo = tile * NUFFT_TILE - NUFFT_TAPS // 2
+    hi = min(tile * NUFFT_TILE + NUFFT_TILE - 1, G - 1) + NUFFT_TAPS // 2
+    return sorted({(cell % G) // NUFFT_TILE for cell in range(lo, hi + 1)})
+
+
+def nufft_bins(pos, H: int, W: int):
+    """The cell list inr_nufft_spread gathers from: (bin_start int32 [T + 1], order int32 [M]).  The 2H x 2W grid is cut
+    into bins of NUFFT_TILE x NUFFT_TILE cells (the last of an axis may be narrower), T = ceil(2H / 16) ceil(2W / 16), row
+    major; sample m belongs to bin (floor(g_y) // 16) * ceil(2W / 16) + floor(g_x) // 16 with g the grid position
+    nufft_taps uses.  ``order`` is the stable argsort of the bin numbers, so a bin lists its samples in ascending index;
+    bin b is order[bin_start[b] : bin_start[b + 1]].  Which bins a tile reads: nufft_tile_bins."""
+    pos = check_positions(np.asarray(pos, dtype=np.float64))
+    H, W = int(H), int(W)
+    _nufft_check_shape(H, W)
+    nby, nbx = -(-2 * H // NUFFT_TILE), -(-2 * W // NUFFT_TILE)
+    by = np.floor(_nufft_grid_position(pos[:, 0], H)).astype(np.int64) // NUFFT_TILE
+    bx = np.floor(_nufft_grid_position(pos[:, 1], W)).astype(np.int64) // NUFFT_TILE
+    b = by * nbx + bx
+    order = np.argsort(b, kind="stable").astype(np.int32)
+    bin_start = np.zeros(nby * nbx + 1, dtype=np.int64)
+    np.cumsum(np.bincount(b, minlength=nby * nbx), out=bin_start[1:])
+    return bin_start.astype(np.int32), order
+
+
+def _nufft_tap_sum(pos, H: int, W: int) -> float:
+    """max over the samples of (sum of the six y weights) (sum of the six x weights)"""
+    _, wy = nufft_taps(pos[:, 0], H)
+    _, wx = nufft_taps(pos[:, 1], W)
+    return float((wy.astype(np.float64).sum(axis=1) * wx.astype(np.float64).sum(axis=1)).max())
+
+
+def _gamma(n: int) -> float:
+    """n roundings of fp32, compounded: n u / (1 - n u), u = 2^-24"""
+    u = 2.0 ** -24
+    return n * u / (1.0 - n * u)
+
+
+def _fft_roundings(H: int, W: int) -> int:
+    """4 per radix-2 stage (twiddle, two in a component of the complex product, the sum) over
+    ceil(log2 Gy) + ceil(log2 Gx) stages"""
+    return 4 * (math.ceil(math.log2(2 * H)) + math.ceil(math.log2(2 * W)))
+
+
+def nufft_error_bound(img, pos) -> np.ndarray:
+    """[C] fp64: the worst-case fp32 bound of |nufft - nufft_numpy| per output,
+        gamma(J^2 + 2 + 4 + 3 + 4 L) S B_c,   B_c = sum_yx |I_c| 2 / (a_y a_x) / sqrt(Gy Gx),   S = max_m (sum wy)(sum wx):
+    every grid value is at most B_c; it carries 3 roundings of the apodisation and 4 per FFT stage (L stages); a sample adds
+    J^2 products, each with a rounded weight product and a rounded multiplication, and the two stored weights may differ
+    from the restatement's by one fp32 unit each (2 roundings each)."""
+    from .coils import _as_complex
+    z = np.asarray(_as_complex(img)).astype(np.complex128)
+    if z.ndim == 2:
+        z = z[None]
+    pos = check_positions(np.asarray(pos, dtype=np.float64))
+    Cn, H, W = z.shape
+    B = (np.abs(z) * _deapodisation(H, W)[None]).reshape(Cn, -1).sum(axis=1) / math.sqrt(4.0 * H * W)
+    return _gamma(NUFFT_TAPS ** 2 + 2 + 4 + 3 + _fft_roundings(H, W)) * _nufft_tap_sum(pos, H, W) * B
+
+
+def nufft_adjoint_error_bound(val, pos, weights, H: int, W: int) -> np.ndarray:
+    """[C] fp64: the worst-case fp32 bound of |nufft_adjoint - nufft_adjoint_numpy| per pixel,
+        gamma(M + 2 + 4 + 3 + 4 L) D S sum_m |w_m val_c[m]| / sqrt(Gy Gx),   D = max_yx 2 / (a_y a_x):
+    a cell sums at most M terms, each with the rounded w val, the rounded weight product and the one-unit allowance on
+    the two weights; the inverse FFT adds 4 per stage on sum_j |grid_j| <= S sum_m |w val|; the de-apodisation 3."""
+    v = _samples_complex(val)
+    pos = check_positions(np.asarray(pos, dtype=np.float64))
+    M = v.shape[1]
+    total = (np.abs(v) * np.abs(_weights_numpy(weights, M))[None, :]).sum(axis=1)
+    return (_gamma(M + 2 + 4 + 3 + _fft_roundings(H, W)) * float(_deapodisation(H, W).max()) * _nufft_tap_sum(pos, H, W)
+            * total / math.sqrt(4.0 * H * W))
+
+
+def nufft_scratch_floats(coils: int, H: int, W: int, M: int) -> int:
+    out = C.c_int64(0)
+    L.check(L.load().inr_nufft_scratch(int(coils), int(H), int(W), int(M), C.byref(out)))
+    return int(out.value)
+
+
+def nufft_device_apodisation(H: int, W: int, device):
+    """(apod_y [H], apod_x [W]) fp32 on the device"""
+    return (torch.from_numpy(nufft_apodisation(H)).to(device), torch.from_numpy(nufft_apodisation(W)).to(device))
+
+
+def nufft_device_bins(pos, H: int, W: int, device):
+    """nufft_bins on the device: (bin_start, order) int32 tensors"""
+    if isinstance(pos, torch.Tensor):
+        pos = pos.detach().cpu().numpy()
+    bin_start, order = nufft_bins(pos, H, W)
+    return torch.from_numpy(bin_start).to(device), torch.from_numpy(order).to(device)
+
+
+def nufft(img: torch.Tensor, pos, scratch: Optional[torch.Tensor] = None, apod=None) -> torch.Tensor:
+    """[C, M, 2] fp32 on the device: the gridding approximation of nudft(img, pos) -- inr_nufft_prepare, torch.fft
+    (evalchain.fft2c of the 2H x 2W grid), inr_nufft_interp, all on the current stream.  ``scratch``: a float32 device
+    buffer of at least nufft_scratch_floats(C, H, W, M) entries; ``apod``: nufft_device_apodisation(H, W, device)
+    (defaults: made here)."""
+    from .evalchain import fft2c
+    if not isinstance(img, torch.Tensor) or not img.is_cuda:
+        raise RuntimeError("nufft only runs on an MI355X (no CPU fallback; nufft_numpy is the host-side restatement)")
+    if img.dtype != torch.float32 or img.dim() != 4 or img.shape[-1] != 2:
+        raise RuntimeError(f"img must be float32 [C, H, W, 2] (got {img.dtype} {tuple(img.shape)})")
+    img = img.contiguous()
+    coils, H, W = (int(v) for v in img.shape[:3])
+    p = _device_positions(pos, img.device)
+    M = int(p.shape[0])
+    if scratch is None:
+        scratch = torch.empty(nufft_scratch_floats(coils, H, W, M), device=img.device, dtype=torch.float32)
+    ay, ax = apod if apod is not None else nufft_device_apodisation(H, W, img.device)
+    lib = L.load()
+    grid = torch.empty(coils, 2 * H, 2 * W, 2, device=img.device, dtype=torch.float32)
+    out = torch.empty(coils, M, 2, device=img.device, dtype=torch.float32)
+    with torch.cuda.device(img.device):
+        stream = torch.cuda.current_stream(img.device).cuda_stream
+        L.check(lib.inr_nufft_prepare(img.data_ptr(), ay.data_ptr(), ax.data_ptr(), coils, H, W, grid.data_ptr(), stream))
+        grid = fft2c(grid).contiguous()
+        L.check(lib.inr_nufft_interp(grid.data_ptr(), p.data_ptr(), coils, H, W, M, out.data_ptr(), scratch.data_ptr(),
+                                     scratch.numel(), stream))
+    return out
+
+
+def nufft_adjoint(val: torch.Tensor, pos, shape, weights=None, scratch: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None, bins=None, apod=None) -> torch.Tensor:
+    """[C, H, W, 2] fp32 on the device: the gridding approximation of nudft_adjoint(val, pos, shape, weights) --
+    inr_nufft_spread, torch.fft (evalchain.ifft2c of the 2H x 2W grid), inr_nufft_finish, all on the current stream.
+    ``bins``: nufft_device_bins(pos, H, W, device) (default: made here, which reads the positions back when they are a
+    device tensor); ``scratch``, ``apod``: as for nufft."""
+    from .evalchain import ifft2c
+    if not isinstance(val, torch.Tensor) or not val.is_cuda:
+        raise RuntimeError("nufft_adjoint only runs on an MI355X (no CPU fallback; nufft_adjoint_numpy is the host-side "
+                           "restatement)")
+    if val.dtype != torch.float32 or val.dim() != 3 or val.shape[-1] != 2:
+        raise RuntimeError(f"val must be float32 [C, M, 2] (got {val.dtype} {tuple(val.shape)})")
+    val = val.contiguous()
+    coils, M = int(val.shape[0]), int(val.shape[1])
+    H, W = (int(v) for v in tuple(shape)[-2:])
+    p = _device_positions(pos, val.device)
+    if int(p.shape[0]) != M:
+        raise ValueError(f"val has {M} samples per coil, pos {int(p.shape[0])}")
+    w = _device_weights(weights, M, val.device)
+    if scratch is None:
+        scratch = torch.empty(nufft_scratch_floats(coils, H, W, M), device=val.device, dtype=torch.float32)
+    bin_start, order = bins if bins is not None else nufft_device_bins(pos, H, W, val.device)
+    ay, ax = apod if apod is not None else nufft_device_apodisation(H, W, val.device)
+    if out is None:
+        out = torch.empty(coils, H, W, 2, device=val.device, dtype=torch.float32)
+    lib = L.load()
+    grid = torch.empty(coils, 2 * H, 2 * W, 2, device=val.device, dtype=torch.float32)
+    with torch.cuda.device(val.device):
+        stream = torch.cuda.current_stream(val.device).cuda_stream
+        L.check(lib.inr_nufft_spread(val.data_ptr(), p.data_ptr(), None if w is None else w.data_ptr(),
+                                     bin_start.data_ptr(), order.data_ptr(), coils, H, W, M, grid.data_ptr(),
+                                     scratch.data_ptr(), scratch.numel(), stream))
+        grid = ifft2c(grid).contiguous()
+        L.check(lib.inr_nufft_finish(grid.data_ptr(), ay.data_ptr(), ax.data_ptr(), coils, H, W, out.data_ptr(), stream))
+    return out
+
+
+def parse_operator(arg) -> Optional[str]:
+    """config['trajectory_operator'] -> None (key absent: the exact operators, nothing recorded), "exact" or "gridding";
+    ValueError for anything else"""
+    if arg is None:
+        return None
+    if isinstance(arg, str) and arg in ("exact", "gridding"):
+        return arg
+    raise ValueError(f"trajectory_operator = {arg!r}: 'exact' or 'gridding'")
+
+
 # ---- density compensation ----------------------------------------------------------------------------------------------
 def normalise_density(w, H: int, W: int) -> np.ndarray:
     """``w`` scaled so that sum w = H W: with the 1/sqrt(H W) of both operators the point-spread function A^H W A then
@@ -397,25 +693,36 @@ def _cg(y, w_sum, apply_a, apply_ahw, dot, axpy, iters: int):
     return iterates, objective
 
 
-def cg_baseline_numpy(values, pos, shape, weights, iters: int):
-    """cg_baseline in fp64 on the host: (iterates [C, H, W] complex128, objective)"""
+def _check_operator(operator: str) -> bool:
+    """True for "gridding", False for "exact"; ValueError otherwise"""
+    if operator not in ("exact", "gridding"):
+        raise ValueError(f"operator = {operator!r}: 'exact' or 'gridding'")
+    return operator == "gridding"
+
+
+def cg_baseline_numpy(values, pos, shape, weights, iters: int, operator: str = "exact"):
+    """cg_baseline in fp64 on the host: (iterates [C, H, W] complex128, objective).  ``operator``: "exact" (nudft_numpy
+    and its adjoint) or "gridding" (nufft_numpy and its adjoint)."""
+    fwd, adj = (nufft_numpy, nufft_adjoint_numpy) if _check_operator(operator) else (nudft_numpy, nudft_adjoint_numpy)
     y = _samples_complex(values)
     H, W = (int(v) for v in tuple(shape)[-2:])
     pos = check_positions(np.asarray(pos, dtype=np.float64))
     w = _weights_numpy(weights, pos.shape[0])
-    return _cg(y, lambda a: float((w[None, :] * np.abs(a) ** 2).sum()), lambda x: nudft_numpy(x, pos),
-               lambda a: nudft_adjoint_numpy(a, pos, H, W, w), lambda a: float((np.abs(a) ** 2).sum()),
+    return _cg(y, lambda a: float((w[None, :] * np.abs(a) ** 2).sum()), lambda x: fwd(x, pos),
+               lambda a: adj(a, pos, H, W, w), lambda a: float((np.abs(a) ** 2).sum()),
                lambda k, a, b: k * a if b is None else b + k * a, int(iters))
 
 
-def cg_baseline(values: torch.Tensor, pos, shape, weights, iters: int):
+def cg_baseline(values: torch.Tensor, pos, shape, weights, iters: int, operator: str = "exact"):
     """The density-weighted conjugate-gradient reconstruction of off-grid samples: ``iters`` iterations on
     A^H W A x = A^H W y from x_0 = 0, A = nudft, all coils at once with one alpha and one beta per iteration; the inner
     products are taken with torch on the device, accumulated in fp64, and read back (two scalars per iteration).
     ``values``: [C, M, 2] or [(C*M), 2] fp32 on the device; ``shape`` = (C, H, W); ``weights``: [M] or None.
     Returns (iterates, objective): the image [C, H, W, 2] after each iteration and sum_m w |A x - y|^2 of x_0 = 0 and of
     every iterate (iters + 1 entries, A x carried along the recurrence).  iters = 0: the plain density-weighted adjoint
-    A^H W y and its objective.  The two scratch buffers are allocated once."""
+    A^H W y and its objective.  The two scratch buffers are allocated once.  ``operator`` = "gridding" (DESIGN.md 4.21):
+    A = nufft and A^H W = nufft_adjoint instead, with their scratch, bins and apodisation made once."""
+    gridding = _check_operator(operator)
     if not isinstance(values, torch.Tensor) or not values.is_cuda:
         raise RuntimeError("cg_baseline only runs on an MI355X (no CPU fallback; cg_baseline_numpy is the host-side version)")
     C_, H, W = (int(v) for v in shape[:3])
@@ -425,15 +732,30 @@ def cg_baseline(values: torch.Tensor, pos, shape, weights, iters: int):
     p_dev = _device_positions(pos, dev)
     w32 = _device_weights(weights, M, dev)
     w64 = None if w32 is None else w32.double()
-    fwd = torch.empty(scratch_floats(C_, H, W, M), device=dev, dtype=torch.float32)
-    adj = torch.empty(adjoint_scratch_floats(C_, H, W, M), device=dev, dtype=torch.float32)
+    if gridding:
+        taps = torch.empty(nufft_scratch_floats(C_, H, W, M), device=dev, dtype=torch.float32)
+        bins, apod = nufft_device_bins(pos, H, W, dev), nufft_device_apodisation(H, W, dev)
+
+        def apply_a(x):
+            return nufft(x, p_dev, scratch=taps, apod=apod)
+
+        def apply_ahw(a):
+            return nufft_adjoint(a, p_dev, (H, W), w32, scratch=taps, bins=bins, apod=apod)
+    else:
+        fwd = torch.empty(scratch_floats(C_, H, W, M), device=dev, dtype=torch.float32)
+        adj = torch.empty(adjoint_scratch_floats(C_, H, W, M), device=dev, dtype=torch.float32)
+
+        def apply_a(x):
+            return nudft(x, p_dev, scratch=fwd)
+
+        def apply_ahw(a):
+            return nudft_adjoint(a, p_dev, (H, W), w32, scratch=adj)
 
     def w_sum(a):
         e = (a.double() ** 2).sum(dim=-1)  # [C, M]
         return float((e if w64 is None else e * w64[None, :]).sum())
 
-    return _cg(y, w_sum, lambda x: nudft(x, p_dev, scratch=fwd),
-               lambda a: nudft_adjoint(a, p_dev, (H, W), w32, scratch=adj), lambda a: float((a.double() ** 2).sum()),
+    return _cg(y, w_sum, apply_a, apply_ahw, lambda a: float((a.double() ** 2).sum()),
                lambda k, a, b: a * k if b is None else torch.add(b, a, alpha=k), int(iters))
 
 
@@ -458,6 +780,9 @@ def add_baseline_flags(ap) -> None:
     ap.add_argument("--trajectory-density", type=str, default=None, metavar="ARG",
                     help="the baseline's density compensation: ramp (spokes), uniform or a .npy file of [M] positive "
                          "float64 (config['trajectory_density']; default: ramp for spokes, uniform for a file)")
+    ap.add_argument("--trajectory-operator", type=str, default=None, metavar="ARG",
+                    help="the operator pair inside the baseline: exact (inr_nudft and its adjoint) or gridding "
+                         "(Kaiser-Bessel gridding around an FFT) (config['trajectory_operator']; default: exact)")
 
 
 def apply_baseline_flags(config: dict, opts) -> dict:
@@ -465,4 +790,6 @@ def apply_baseline_flags(config: dict, opts) -> dict:
         config["trajectory_baseline"] = opts.trajectory_baseline
     if getattr(opts, "trajectory_density", None) is not None:
         config["trajectory_density"] = opts.trajectory_density
+    if getattr(opts, "trajectory_operator", None) is not None:
+        config["trajectory_operator"] = opts.trajectory_operator
     return config
