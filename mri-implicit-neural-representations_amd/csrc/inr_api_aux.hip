@@ -1,6 +1,7 @@
-// inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network: encoders, losses, TV, Adam,
-// image metrics, display, shuffle, grid rows, band statistics, coil compression, off-grid sampling, its adjoint and their gridding form.  Each checks its arguments, fills an argument struct,
-// launches and maps the hipError_t to a code; none allocates device memory or syncs.
+// inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network, the off-grid operators apart
+// (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, grid rows, band statistics, coil
+// compression.  Each checks its arguments, fills an argument struct, launches and maps the hipError_t to a code; none
+// allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
 
@@ -62,6 +63,16 @@ inr::AdamArgs adam_args(double beta1, double beta2, double eps, double weight_de
   aa.l1 = (float)l1;
   aa.l2 = (float)l2;
   return aa;
+}
+
+int coil_count_check(int32_t v, const char* name, const char* who) {
+  if (v < 1 || v > INR_COIL_MAX) return fail(INR_ERR_INVALID, "%s: %s = %d (1..%d)", who, name, (int)v, INR_COIL_MAX);
+  return INR_OK;
+}
+
+bool ranges_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
 }
 
 extern "C" {
@@ -418,19 +429,9 @@ int inr_band_stats(const float* dist, const float* gt, const float* pred, const 
 static_assert(INR_COIL_MAX == inr::COIL_MAX && INR_COIL_TILE_PIXELS == inr::COIL_TILE_PIXELS,
               "inr_abi.h and inr_aux.h disagree");
 
-static int coil_count_check(int32_t v, const char* name, const char* who) {
-  if (v < 1 || v > INR_COIL_MAX) return fail(INR_ERR_INVALID, "%s: %s = %d (1..%d)", who, name, (int)v, INR_COIL_MAX);
-  return INR_OK;
-}
-
 static int coil_pixels_check(int64_t N, const char* who) {
   if (N < 1 || N >= (1LL << 31)) return fail(INR_ERR_INVALID, "%s: N = %lld (1 <= N < 2^31 pixels per call)", who, (long long)N);
   return INR_OK;
-}
-
-static bool ranges_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
 }
 
 int inr_coil_gram_scratch(int32_t C, int64_t N, int64_t* scratch_doubles) {
@@ -467,215 +468,6 @@ int inr_coil_apply(const float* in, const float* A, int32_t M, int32_t K, int64_
   if (ranges_overlap(out, out_bytes, A, a_bytes)) return fail(INR_ERR_INVALID, "inr_coil_apply: out overlaps A");
   hipError_t e = inr::launch_coil_apply(in, A, M, K, N, out, (hipStream_t)stream);
   return hip_done(e, "inr_coil_apply");
-}
-
-// ---- off-grid samples of the continuous k-space (inr_nudft.hip) ----
-static_assert(INR_NUDFT_TILE == inr::NUDFT_TILE, "inr_abi.h and inr_aux.h disagree");
-
-static int nudft_check(int32_t C, int64_t H, int64_t W, int64_t M, const char* who) {
-  if (int rc = coil_count_check(C, "C", who)) return rc;
-  if (H < 1 || W < 1 || H >= (1LL << 31) || W >= (1LL << 31) || H * W >= (1LL << 31))
-    return fail(INR_ERR_INVALID, "%s: H = %lld, W = %lld (each >= 1, H * W < 2^31)", who, (long long)H, (long long)W);
-  if (M < 1 || M >= (1LL << 31)) return fail(INR_ERR_INVALID, "%s: M = %lld (1 <= M < 2^31 samples per call)", who, (long long)M);
-  return INR_OK;
-}
-
-int inr_nudft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats) {
-  if (scratch_floats == nullptr) return fail(INR_ERR_INVALID, "inr_nudft_scratch: null argument");
-  if (int rc = nudft_check(C, H, W, M, "inr_nudft_scratch")) return rc;
-  *scratch_floats = inr::nudft_scratch_floats(H, W, M);
-  return INR_OK;
-}
-
-int inr_nudft(const float* img, int32_t C, int64_t H, int64_t W, const double* pos, int64_t M, float* out,
-              float* scratch, int64_t scratch_floats, void* stream) {
-  if (img == nullptr || pos == nullptr || out == nullptr || scratch == nullptr)
-    return fail(INR_ERR_INVALID, "inr_nudft: null argument");
-  if (int rc = nudft_check(C, H, W, M, "inr_nudft")) return rc;
-  if ((((uintptr_t)img | (uintptr_t)pos | (uintptr_t)out) & 7u) != 0)
-    return fail(INR_ERR_INVALID, "inr_nudft: img / pos / out is not 8-byte aligned");
-  if (((uintptr_t)scratch & 15u) != 0) return fail(INR_ERR_INVALID, "inr_nudft: scratch is not 16-byte aligned");
-  const int64_t need = inr::nudft_scratch_floats(H, W, M);
-  if (scratch_floats < need)
-    return fail(INR_ERR_INVALID, "inr_nudft: scratch holds %lld floats, H = %lld, W = %lld, M = %lld need %lld",
-                (long long)scratch_floats, (long long)H, (long long)W, (long long)M, (long long)need);
-  const int64_t img_bytes = (int64_t)C * H * W * 8, pos_bytes = M * 16, out_bytes = (int64_t)C * M * 8;
-  if (ranges_overlap(out, out_bytes, img, img_bytes)) return fail(INR_ERR_INVALID, "inr_nudft: out overlaps img");
-  if (ranges_overlap(out, out_bytes, pos, pos_bytes)) return fail(INR_ERR_INVALID, "inr_nudft: out overlaps pos");
-  if (ranges_overlap(scratch, need * 4, out, out_bytes) || ranges_overlap(scratch, need * 4, img, img_bytes) ||
-      ranges_overlap(scratch, need * 4, pos, pos_bytes))
-    return fail(INR_ERR_INVALID, "inr_nudft: scratch overlaps img, pos or out");
-  hipError_t e = inr::launch_nudft(img, C, (int)H, (int)W, pos, M, out, scratch, (hipStream_t)stream);
-  return hip_done(e, "inr_nudft");
-}
-
-// ---- ... and back onto the grid: the conjugate transpose (inr_nudft_adjoint.hip) ----
-static int adjoint_nudft_check(int32_t C, int64_t H, int64_t W, int64_t M, const char* who) {
-  if (int rc = nudft_check(C, H, W, M, who)) return rc;
-  if (H > (1LL << 31) - 64 || W > (1LL << 31) - 64)  // the tables pad both axes to 64
-    return fail(INR_ERR_INVALID, "%s: H = %lld, W = %lld (each <= 2^31 - 64)", who, (long long)H, (long long)W);
-  return INR_OK;
-}
-
-int inr_adjoint_nudft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats) {
-  if (scratch_floats == nullptr) return fail(INR_ERR_INVALID, "inr_adjoint_nudft_scratch: null argument");
-  if (int rc = adjoint_nudft_check(C, H, W, M, "inr_adjoint_nudft_scratch")) return rc;
-  *scratch_floats = inr::adjoint_nudft_scratch_floats(H, W, M);
-  return INR_OK;
-}
-
-int inr_adjoint_nudft(const float* val, const double* pos, const float* w, int32_t C, int64_t H, int64_t W, int64_t M,
-                      float* out, float* scratch, int64_t scratch_floats, void* stream) {
-  if (val == nullptr || pos == nullptr || out == nullptr || scratch == nullptr)
-    return fail(INR_ERR_INVALID, "inr_adjoint_nudft: null argument");
-  if (int rc = adjoint_nudft_check(C, H, W, M, "inr_adjoint_nudft")) return rc;
-  if ((((uintptr_t)val | (uintptr_t)pos | (uintptr_t)out) & 7u) != 0)
-    return fail(INR_ERR_INVALID, "inr_adjoint_nudft: val / pos / out is not 8-byte aligned");
-  if (((uintptr_t)w & 3u) != 0) return fail(INR_ERR_INVALID, "inr_adjoint_nudft: w is not 4-byte aligned");
-  if (((uintptr_t)scratch & 15u) != 0) return fail(INR_ERR_INVALID, "inr_adjoint_nudft: scratch is not 16-byte aligned");
-  const int64_t need = inr::adjoint_nudft_scratch_floats(H, W, M);
-  if (scratch_floats < need)
-    return fail(INR_ERR_INVALID, "inr_adjoint_nudft: scratch holds %lld floats, H = %lld, W = %lld, M = %lld need %lld",
-                (long long)scratch_floats, (long long)H, (long long)W, (long long)M, (long long)need);
-  const int64_t val_bytes = (int64_t)C * M * 8, pos_bytes = M * 16, w_bytes = w != nullptr ? M * 4 : 0,
-                out_bytes = (int64_t)C * H * W * 8;
-  if (ranges_overlap(out, out_bytes, val, val_bytes)) return fail(INR_ERR_INVALID, "inr_adjoint_nudft: out overlaps val");
-  if (ranges_overlap(out, out_bytes, pos, pos_bytes)) return fail(INR_ERR_INVALID, "inr_adjoint_nudft: out overlaps pos");
-  if (w != nullptr && ranges_overlap(out, out_bytes, w, w_bytes))
-    return fail(INR_ERR_INVALID, "inr_adjoint_nudft: out overlaps w");
-  if (ranges_overlap(scratch, need * 4, out, out_bytes) || ranges_overlap(scratch, need * 4, val, val_bytes) ||
-      ranges_overlap(scratch, need * 4, pos, pos_bytes) || (w != nullptr && ranges_overlap(scratch, need * 4, w, w_bytes)))
-    return fail(INR_ERR_INVALID, "inr_adjoint_nudft: scratch overlaps val, pos, w or out");
-  hipError_t e = inr::launch_adjoint_nudft(val, pos, w, C, (int)H, (int)W, M, out, scratch, (hipStream_t)stream);
-  return hip_done(e, "inr_adjoint_nudft");
-}
-
-// ---- the same two operators by Kaiser-Bessel gridding around the caller's FFT (inr_nufft.hip) ----
-static_assert(INR_NUFFT_TILE == inr::NUFFT_TILE && INR_NUFFT_TAPS == inr::NUFFT_TAPS, "inr_abi.h and inr_aux.h disagree");
-
-static int nufft_check(int32_t C, int64_t H, int64_t W, int64_t M, const char* who) {
-  if (int rc = nudft_check(C, H, W, M, who)) return rc;
-  if (H < INR_NUFFT_TAPS / 2 || W < INR_NUFFT_TAPS / 2)  // on 2 n < 6 cells two taps of a sample would share a cell
-    return fail(INR_ERR_INVALID, "%s: H = %lld, W = %lld (each >= %d)", who, (long long)H, (long long)W, INR_NUFFT_TAPS / 2);
-  return INR_OK;
-}
-
-static int nufft_scratch_check(const float* scratch, int64_t scratch_floats, int64_t M, const char* who) {
-  if (((uintptr_t)scratch & 15u) != 0) return fail(INR_ERR_INVALID, "%s: scratch is not 16-byte aligned", who);
-  const int64_t need = inr::nufft_scratch_floats(M);
-  if (scratch_floats < need)
-    return fail(INR_ERR_INVALID, "%s: scratch holds %lld floats, M = %lld needs %lld", who, (long long)scratch_floats,
-                (long long)M, (long long)need);
-  return INR_OK;
-}
-
-// bin_start where the host can read it (pinned host memory): 0 = bin_start[0] <= ... <= bin_start[T] = M
-static int nufft_bins_check(const int32_t* bin_start, int64_t T, int64_t M) {
-  hipPointerAttribute_t attr;
-  memset(&attr, 0, sizeof(attr));
-  if (hipPointerGetAttributes(&attr, bin_start) != hipSuccess) {
-    (void)hipGetLastError();  // a pointer the runtime does not know: nothing to check here
-    return INR_OK;
-  }
-  if (attr.type != hipMemoryTypeHost || attr.hostPointer == nullptr) return INR_OK;
-  const int32_t* b = static_cast<const int32_t*>(attr.hostPointer);
-  bool ok = b[0] == 0 && b[T] == M;
-  for (int64_t i = 0; ok && i < T; ++i) ok = b[i] <= b[i + 1];
-  if (!ok)
-    return fail(INR_ERR_INVALID, "inr_nufft_spread: bin_start is not 0 = b[0] <= ... <= b[%lld] = %lld", (long long)T,
-                (long long)M);
-  return INR_OK;
-}
-
-int inr_nufft_scratch(int32_t C, int64_t H, int64_t W, int64_t M, int64_t* scratch_floats) {
-  if (scratch_floats == nullptr) return fail(INR_ERR_INVALID, "inr_nufft_scratch: null argument");
-  if (int rc = nufft_check(C, H, W, M, "inr_nufft_scratch")) return rc;
-  *scratch_floats = inr::nufft_scratch_floats(M);
-  return INR_OK;
-}
-
-// prepare and finish: the image [C][H][W][2], the grid [C][2H][2W][2], the two apodisation vectors
-static int nufft_image_grid_check(const float* image, const float* grid, const float* apod_y, const float* apod_x, int32_t C,
-                                  int64_t H, int64_t W, bool grid_is_output, const char* who) {
-  if (image == nullptr || grid == nullptr || apod_y == nullptr || apod_x == nullptr)
-    return fail(INR_ERR_INVALID, "%s: null argument", who);
-  if (int rc = nufft_check(C, H, W, 1, who)) return rc;
-  if (((uintptr_t)image & 7u) != 0) return fail(INR_ERR_INVALID, "%s: %s is not 8-byte aligned", who, grid_is_output ? "img" : "out");
-  if (((uintptr_t)grid & 15u) != 0) return fail(INR_ERR_INVALID, "%s: grid is not 16-byte aligned", who);
-  if ((((uintptr_t)apod_y | (uintptr_t)apod_x) & 3u) != 0)
-    return fail(INR_ERR_INVALID, "%s: apod_y / apod_x is not 4-byte aligned", who);
-  const int64_t image_bytes = (int64_t)C * H * W * 8, grid_bytes = 4 * image_bytes;
-  const void* out = grid_is_output ? grid : image;
-  const int64_t out_bytes = grid_is_output ? grid_bytes : image_bytes;
-  if (ranges_overlap(grid, grid_bytes, image, image_bytes) || ranges_overlap(out, out_bytes, apod_y, H * 4) ||
-      ranges_overlap(out, out_bytes, apod_x, W * 4))
-    return fail(INR_ERR_INVALID, "%s: the output overlaps an input", who);
-  return INR_OK;
-}
-
-int inr_nufft_prepare(const float* img, const float* apod_y, const float* apod_x, int32_t C, int64_t H, int64_t W,
-                      float* grid, void* stream) {
-  if (int rc = nufft_image_grid_check(img, grid, apod_y, apod_x, C, H, W, true, "inr_nufft_prepare")) return rc;
-  hipError_t e = inr::launch_nufft_prepare(img, apod_y, apod_x, C, (int)H, (int)W, grid, (hipStream_t)stream);
-  return hip_done(e, "inr_nufft_prepare");
-}
-
-int inr_nufft_finish(const float* grid, const float* apod_y, const float* apod_x, int32_t C, int64_t H, int64_t W,
-                     float* out, void* stream) {
-  if (int rc = nufft_image_grid_check(out, grid, apod_y, apod_x, C, H, W, false, "inr_nufft_finish")) return rc;
-  hipError_t e = inr::launch_nufft_finish(grid, apod_y, apod_x, C, (int)H, (int)W, out, (hipStream_t)stream);
-  return hip_done(e, "inr_nufft_finish");
-}
-
-int inr_nufft_interp(const float* grid, const double* pos, int32_t C, int64_t H, int64_t W, int64_t M, float* out,
-                     float* scratch, int64_t scratch_floats, void* stream) {
-  if (grid == nullptr || pos == nullptr || out == nullptr || scratch == nullptr)
-    return fail(INR_ERR_INVALID, "inr_nufft_interp: null argument");
-  if (int rc = nufft_check(C, H, W, M, "inr_nufft_interp")) return rc;
-  if ((((uintptr_t)pos | (uintptr_t)out) & 7u) != 0)
-    return fail(INR_ERR_INVALID, "inr_nufft_interp: pos / out is not 8-byte aligned");
-  if (((uintptr_t)grid & 15u) != 0) return fail(INR_ERR_INVALID, "inr_nufft_interp: grid is not 16-byte aligned");
-  if (int rc = nufft_scratch_check(scratch, scratch_floats, M, "inr_nufft_interp")) return rc;
-  const int64_t grid_bytes = (int64_t)C * H * W * 32, pos_bytes = M * 16, out_bytes = (int64_t)C * M * 8,
-                scratch_bytes = inr::nufft_scratch_floats(M) * 4;
-  if (ranges_overlap(out, out_bytes, grid, grid_bytes) || ranges_overlap(out, out_bytes, pos, pos_bytes))
-    return fail(INR_ERR_INVALID, "inr_nufft_interp: out overlaps grid or pos");
-  if (ranges_overlap(scratch, scratch_bytes, out, out_bytes) || ranges_overlap(scratch, scratch_bytes, grid, grid_bytes) ||
-      ranges_overlap(scratch, scratch_bytes, pos, pos_bytes))
-    return fail(INR_ERR_INVALID, "inr_nufft_interp: scratch overlaps grid, pos or out");
-  hipError_t e = inr::launch_nufft_interp(grid, pos, C, (int)H, (int)W, M, out, scratch, (hipStream_t)stream);
-  return hip_done(e, "inr_nufft_interp");
-}
-
-int inr_nufft_spread(const float* val, const double* pos, const float* w, const int32_t* bin_start, const int32_t* order,
-                     int32_t C, int64_t H, int64_t W, int64_t M, float* grid, float* scratch, int64_t scratch_floats,
-                     void* stream) {
-  if (val == nullptr || pos == nullptr || bin_start == nullptr || order == nullptr || grid == nullptr || scratch == nullptr)
-    return fail(INR_ERR_INVALID, "inr_nufft_spread: null argument");
-  if (int rc = nufft_check(C, H, W, M, "inr_nufft_spread")) return rc;
-  if ((((uintptr_t)val | (uintptr_t)pos) & 7u) != 0)
-    return fail(INR_ERR_INVALID, "inr_nufft_spread: val / pos is not 8-byte aligned");
-  if ((((uintptr_t)w | (uintptr_t)bin_start | (uintptr_t)order) & 3u) != 0)
-    return fail(INR_ERR_INVALID, "inr_nufft_spread: w / bin_start / order is not 4-byte aligned");
-  if (((uintptr_t)grid & 15u) != 0) return fail(INR_ERR_INVALID, "inr_nufft_spread: grid is not 16-byte aligned");
-  if (int rc = nufft_scratch_check(scratch, scratch_floats, M, "inr_nufft_spread")) return rc;
-  const int64_t T = inr::nufft_bin_count(H, W);
-  const int64_t grid_bytes = (int64_t)C * H * W * 32, scratch_bytes = inr::nufft_scratch_floats(M) * 4;
-  const void* in[5] = {val, pos, w, bin_start, order};
-  const int64_t in_bytes[5] = {(int64_t)C * M * 8, M * 16, w != nullptr ? M * 4 : 0, (T + 1) * 4, M * 4};
-  for (int i = 0; i < 5; ++i) {
-    if (in[i] == nullptr) continue;
-    if (ranges_overlap(grid, grid_bytes, in[i], in_bytes[i]))
-      return fail(INR_ERR_INVALID, "inr_nufft_spread: grid overlaps val, pos, w, bin_start or order");
-    if (ranges_overlap(scratch, scratch_bytes, in[i], in_bytes[i]))
-      return fail(INR_ERR_INVALID, "inr_nufft_spread: scratch overlaps val, pos, w, bin_start or order");
-  }
-  if (ranges_overlap(scratch, scratch_bytes, grid, grid_bytes))
-    return fail(INR_ERR_INVALID, "inr_nufft_spread: scratch overlaps grid");
-  if (int rc = nufft_bins_check(bin_start, T, M)) return rc;
-  hipError_t e = inr::launch_nufft_spread(val, pos, w, bin_start, order, C, (int)H, (int)W, M, grid, scratch,
-                                          (hipStream_t)stream);
-  return hip_done(e, "inr_nufft_spread");
 }
 
 int inr_adam_schedule(double lr, double beta1, double beta2, int32_t n, float* host_out) {

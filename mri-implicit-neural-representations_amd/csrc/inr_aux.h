@@ -193,9 +193,6 @@ constexpr int NUDFT_TILE = 64;  // INR_NUDFT_TILE: samples per workgroup
 long long nudft_scratch_floats(long long H, long long W, long long M);
 hipError_t launch_nudft(const float* img, int C, int H, int W, const double* pos, long long M, float* out,
                         float* scratch, hipStream_t st);
-// the phasor tables alone, for padded sizes of the caller's choosing (Mp a multiple of 64; Hp >= H, Wp >= W)
-void launch_nudft_tables(const double* pos, long long M, long long Mp, int H, int W, int Hp, int Wp, float* tab,
-                         hipStream_t st);
 
 // the conjugate transpose of launch_nudft (inr_nudft_adjoint.hip): samples [C][M][2], optional weights
 // [M] -> coil images [C][H][W][2], from the same tables

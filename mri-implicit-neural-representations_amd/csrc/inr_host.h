@@ -1,5 +1,6 @@
 // inr_host.h -- what the host files of the C-ABI share: inr_plan.hip (plan creation), inr_layout.hip (the launch layout of
-// a call), inr_api.hip (the network entries) and inr_api_aux.hip (every other entry).  Host only: no kernel includes it.
+// a call), inr_api.hip (the network entries), inr_api_offgrid.hip (the off-grid operators' entries) and inr_api_aux.hip
+// (every other entry).  Host only: no kernel includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +26,9 @@ int fail(int code, const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 // how every entry ends once its launches are queued: the error in the entry's name, or INR_OK
 inline int hip_done(hipError_t e, const char* what) { return e != hipSuccess ? hip_fail(e, what) : INR_OK; }
+// a coil count `name` = v outside 1..INR_COIL_MAX; two byte ranges that share a byte (inr_api_aux.hip)
+int coil_count_check(int32_t v, const char* name, const char* who);
+bool ranges_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes);
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 

@@ -137,12 +137,16 @@ def _phasors(u: np.ndarray, n: int) -> np.ndarray:
     return np.exp(-2j * np.pi * t)
 
 
-def nudft_numpy(img, pos) -> np.ndarray:
-    """[C, M] complex128.  ``img``: [C, H, W, 2] pairs (array or CPU tensor) or a complex [C, H, W] array; ``pos``: [M, 2]."""
+def _image_complex(img) -> np.ndarray:
+    """[C, H, W] complex128 of [C, H, W, 2] pairs (array or CPU tensor) or a complex [C, H, W] / [H, W] array"""
     from .coils import _as_complex
     z = np.asarray(_as_complex(img)).astype(np.complex128)
-    if z.ndim == 2:
-        z = z[None]
+    return z[None] if z.ndim == 2 else z
+
+
+def nudft_numpy(img, pos) -> np.ndarray:
+    """[C, M] complex128.  ``img``: [C, H, W, 2] pairs (array or CPU tensor) or a complex [C, H, W] array; ``pos``: [M, 2]."""
+    z = _image_complex(img)
     pos = check_positions(np.asarray(pos, dtype=np.float64))
     Cn, H, W = z.shape
     ey, ex = _phasors(pos[:, 0], H), _phasors(pos[:, 1], W)
@@ -155,40 +159,49 @@ def nudft_numpy(img, pos) -> np.ndarray:
 def error_bound(img, H: int, W: int) -> np.ndarray:
     """[C] fp64: (H W + 32) 2^-24 sum |I_c| / sqrt(H W) -- the worst-case fp32 bound of |nudft - nudft_numpy| per output:
     H W accumulated terms, each formed with a few roundings after an fp64-reduced phase"""
-    from .coils import _as_complex
-    z = np.asarray(_as_complex(img)).astype(np.complex128)
-    if z.ndim == 2:
-        z = z[None]
+    z = _image_complex(img)
     return (H * W + 32) * 2.0 ** -24 * np.abs(z).reshape(z.shape[0], -1).sum(axis=1) / math.sqrt(H * W)
 
 
 # ---- the kernel --------------------------------------------------------------------------------------------------------
-def scratch_floats(coils: int, H: int, W: int, M: int) -> int:
+def _scratch_query(entry: str, coils: int, H: int, W: int, M: int) -> int:
     out = C.c_int64(0)
-    L.check(L.load().inr_nudft_scratch(int(coils), int(H), int(W), int(M), C.byref(out)))
+    L.check(getattr(L.load(), entry)(int(coils), int(H), int(W), int(M), C.byref(out)))
     return int(out.value)
+
+
+def _device_pairs(t, who: str, name: str, dims: str, host: str) -> torch.Tensor:
+    """the contiguous float32 device tensor ``name`` of (re, im) pairs, ``dims`` naming its leading axes"""
+    rank = dims.count(",") + 2
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{who} only runs on an MI355X (no CPU fallback; {host})")
+    if t.dtype != torch.float32 or t.dim() != rank or t.shape[-1] != 2:
+        raise RuntimeError(f"{name} must be float32 [{dims}, 2] (got {t.dtype} {tuple(t.shape)})")
+    return t.contiguous()
+
+
+def _device_positions(pos, device) -> torch.Tensor:
+    if isinstance(pos, torch.Tensor):
+        if pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 2:
+            raise ValueError(f"pos: expected [M, 2] float64, got {pos.dtype} {tuple(pos.shape)}")
+        return pos.to(device).contiguous()
+    return torch.from_numpy(check_positions(pos)).to(device)
+
+
+def scratch_floats(coils: int, H: int, W: int, M: int) -> int:
+    return _scratch_query("inr_nudft_scratch", coils, H, W, M)
 
 
 def nudft(img: torch.Tensor, pos, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[C, M, 2] fp32 on the device: K_c(pos[m]) of the coil images ``img`` [C, H, W, 2] (device, fp32).  ``pos``: [M, 2]
     fp64, a numpy array or a device tensor.  One inr_nudft call on the current stream; ``scratch``: a float32 device
     buffer of at least scratch_floats(C, H, W, M) entries (default: allocated here)."""
-    if not isinstance(img, torch.Tensor) or not img.is_cuda:
-        raise RuntimeError("nudft only runs on an MI355X (no CPU fallback; nudft_numpy is the host-side definition)")
-    if img.dtype != torch.float32 or img.dim() != 4 or img.shape[-1] != 2:
-        raise RuntimeError(f"img must be float32 [C, H, W, 2] (got {img.dtype} {tuple(img.shape)})")
-    img = img.contiguous()
+    img = _device_pairs(img, "nudft", "img", "C, H, W", "nudft_numpy is the host-side definition")
     coils, H, W = (int(v) for v in img.shape[:3])
-    if isinstance(pos, torch.Tensor):
-        if pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 2:
-            raise ValueError(f"pos: expected [M, 2] float64, got {pos.dtype} {tuple(pos.shape)}")
-        p = pos.to(img.device).contiguous()
-    else:
-        p = torch.from_numpy(check_positions(pos)).to(img.device)
+    p = _device_positions(pos, img.device)
     M = int(p.shape[0])
-    need = scratch_floats(coils, H, W, M)
     if scratch is None:
-        scratch = torch.empty(need, device=img.device, dtype=torch.float32)
+        scratch = torch.empty(scratch_floats(coils, H, W, M), device=img.device, dtype=torch.float32)
     out = torch.empty(coils, M, 2, device=img.device, dtype=torch.float32)
     with torch.cuda.device(img.device):
         L.check(L.load().inr_nudft(img.data_ptr(), coils, H, W, p.data_ptr(), M, out.data_ptr(), scratch.data_ptr(),
@@ -257,17 +270,7 @@ def adjoint_error_bound(val, weights, H: int, W: int) -> np.ndarray:
 
 
 def adjoint_scratch_floats(coils: int, H: int, W: int, M: int) -> int:
-    out = C.c_int64(0)
-    L.check(L.load().inr_adjoint_nudft_scratch(int(coils), int(H), int(W), int(M), C.byref(out)))
-    return int(out.value)
-
-
-def _device_positions(pos, device) -> torch.Tensor:
-    if isinstance(pos, torch.Tensor):
-        if pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 2:
-            raise ValueError(f"pos: expected [M, 2] float64, got {pos.dtype} {tuple(pos.shape)}")
-        return pos.to(device).contiguous()
-    return torch.from_numpy(check_positions(pos)).to(device)
+    return _scratch_query("inr_adjoint_nudft_scratch", coils, H, W, M)
 
 
 def _device_weights(weights, M: int, device) -> Optional[torch.Tensor]:
@@ -285,12 +288,7 @@ def nudft_adjoint(val: torch.Tensor, pos, shape, weights=None, scratch: Optional
     device tensor), times ``weights`` [M] (any float array or tensor, used in fp32; None: ones), back on the H x W grid of
     ``shape`` = (H, W) or (C, H, W).  One inr_adjoint_nudft call on the current stream; ``scratch``: a float32 device
     buffer of at least adjoint_scratch_floats(C, H, W, M) entries (default: allocated here)."""
-    if not isinstance(val, torch.Tensor) or not val.is_cuda:
-        raise RuntimeError("nudft_adjoint only runs on an MI355X (no CPU fallback; nudft_adjoint_numpy is the host-side "
-                           "definition)")
-    if val.dtype != torch.float32 or val.dim() != 3 or val.shape[-1] != 2:
-        raise RuntimeError(f"val must be float32 [C, M, 2] (got {val.dtype} {tuple(val.shape)})")
-    val = val.contiguous()
+    val = _device_pairs(val, "nudft_adjoint", "val", "C, M", "nudft_adjoint_numpy is the host-side definition")
     coils, M = int(val.shape[0]), int(val.shape[1])
     H, W = (int(v) for v in tuple(shape)[-2:])
     p = _device_positions(pos, val.device)
@@ -392,10 +390,7 @@ def _fftc_numpy(z: np.ndarray, inverse: bool) -> np.ndarray:
 def nufft_numpy(img, pos) -> np.ndarray:
     """[C, M] complex128: the gridding approximation of nudft_numpy, every step in fp64 (the tap weights and the
     apodisation vectors are the fp32 numbers the device uses)"""
-    from .coils import _as_complex
-    z = np.asarray(_as_complex(img)).astype(np.complex128)
-    if z.ndim == 2:
-        z = z[None]
+    z = _image_complex(img)
     pos = check_positions(np.asarray(pos, dtype=np.float64))
     Cn, H, W = z.shape
     _nufft_check_shape(H, W)
@@ -483,10 +478,7 @@ def nufft_error_bound(img, pos) -> np.ndarray:
     every grid value is at most B_c; it carries 3 roundings of the apodisation and 4 per FFT stage (L stages); a sample adds
     J^2 products, each with a rounded weight product and a rounded multiplication, and the two stored weights may differ
     from the restatement's by one fp32 unit each (2 roundings each)."""
-    from .coils import _as_complex
-    z = np.asarray(_as_complex(img)).astype(np.complex128)
-    if z.ndim == 2:
-        z = z[None]
+    z = _image_complex(img)
     pos = check_positions(np.asarray(pos, dtype=np.float64))
     Cn, H, W = z.shape
     B = (np.abs(z) * _deapodisation(H, W)[None]).reshape(Cn, -1).sum(axis=1) / math.sqrt(4.0 * H * W)
@@ -507,9 +499,7 @@ def nufft_adjoint_error_bound(val, pos, weights, H: int, W: int) -> np.ndarray:
 
 
 def nufft_scratch_floats(coils: int, H: int, W: int, M: int) -> int:
-    out = C.c_int64(0)
-    L.check(L.load().inr_nufft_scratch(int(coils), int(H), int(W), int(M), C.byref(out)))
-    return int(out.value)
+    return _scratch_query("inr_nufft_scratch", coils, H, W, M)
 
 
 def nufft_device_apodisation(H: int, W: int, device):
@@ -531,11 +521,7 @@ def nufft(img: torch.Tensor, pos, scratch: Optional[torch.Tensor] = None, apod=N
     buffer of at least nufft_scratch_floats(C, H, W, M) entries; ``apod``: nufft_device_apodisation(H, W, device)
     (defaults: made here)."""
     from .evalchain import fft2c
-    if not isinstance(img, torch.Tensor) or not img.is_cuda:
-        raise RuntimeError("nufft only runs on an MI355X (no CPU fallback; nufft_numpy is the host-side restatement)")
-    if img.dtype != torch.float32 or img.dim() != 4 or img.shape[-1] != 2:
-        raise RuntimeError(f"img must be float32 [C, H, W, 2] (got {img.dtype} {tuple(img.shape)})")
-    img = img.contiguous()
+    img = _device_pairs(img, "nufft", "img", "C, H, W", "nufft_numpy is the host-side restatement")
     coils, H, W = (int(v) for v in img.shape[:3])
     p = _device_positions(pos, img.device)
     M = int(p.shape[0])
@@ -561,12 +547,7 @@ def nufft_adjoint(val: torch.Tensor, pos, shape, weights=None, scratch: Optional
     ``bins``: nufft_device_bins(pos, H, W, device) (default: made here, which reads the positions back when they are a
     device tensor); ``scratch``, ``apod``: as for nufft."""
     from .evalchain import ifft2c
-    if not isinstance(val, torch.Tensor) or not val.is_cuda:
-        raise RuntimeError("nufft_adjoint only runs on an MI355X (no CPU fallback; nufft_adjoint_numpy is the host-side "
-                           "restatement)")
-    if val.dtype != torch.float32 or val.dim() != 3 or val.shape[-1] != 2:
-        raise RuntimeError(f"val must be float32 [C, M, 2] (got {val.dtype} {tuple(val.shape)})")
-    val = val.contiguous()
+    val = _device_pairs(val, "nufft_adjoint", "val", "C, M", "nufft_adjoint_numpy is the host-side restatement")
     coils, M = int(val.shape[0]), int(val.shape[1])
     H, W = (int(v) for v in tuple(shape)[-2:])
     p = _device_positions(pos, val.device)

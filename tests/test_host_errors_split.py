@@ -1,6 +1,6 @@
-"""One refused call into each host translation unit of the C-ABI -- inr_plan.hip, inr_layout.hip, inr_api.hip and
-inr_api_aux.hip -- read back through inr_last_error: every file writes the one error text, and the text is the calling
-thread's own.  CPU only: each call is refused before anything is launched."""
+"""One refused call into each host translation unit of the C-ABI -- inr_plan.hip, inr_layout.hip, inr_api.hip,
+inr_api_offgrid.hip and inr_api_aux.hip -- read back through inr_last_error: every file writes the one error text, and the
+text is the calling thread's own.  CPU only: each call is refused before anything is launched."""
 import ctypes as C
 import threading
 
@@ -42,6 +42,13 @@ def test_network_entries_file(L, siren):
     p = C.cast(buf, C.c_void_p)
     assert L.load().inr_forward(siren, None, p, p, p, 1, p, None, None) != 0
     assert L.last_error() == "inr_forward: null argument"
+
+
+def test_offgrid_entries_file(L):
+    n = C.c_int64(-1)
+    assert L.load().inr_nudft_scratch(2, 8, 8, 0, C.byref(n)) != 0
+    assert L.last_error() == "inr_nudft_scratch: M = 0 (1 <= M < 2^31 samples per call)"
+    assert n.value == -1
 
 
 def test_other_entries_file_and_one_text_per_thread(L):
