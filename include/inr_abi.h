@@ -55,7 +55,8 @@ extern "C" {
  *    its scratch query (its conjugate transpose: off-grid samples back onto the image grid); inr_plan_image_sets,
  *    inr_image_sets_after and inr_image_sets_read (weight images on demand: see inr_pack_params); inr_nufft_prepare,
  *    inr_nufft_interp, inr_nufft_spread, inr_nufft_finish and their scratch query (the same two operators by
- *    Kaiser-Bessel gridding around the caller's FFT).
+ *    Kaiser-Bessel gridding around the caller's FFT); inr_ring_scale (rows divided by the divisor of the ring their radius
+ *    lies in: ring-normalised fits).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -538,6 +539,23 @@ int inr_band_stats_scratch(int64_t n, int32_t n_bands, int64_t* scratch_doubles)
 int inr_band_stats(const float* dist, const float* gt, const float* pred, const uint8_t* mask, int32_t mask_select,
                    int64_t n, const float* band_lo, const float* band_hi, int32_t n_bands, double* stats,
                    double* scratch, void* stream);
+
+/* (v7 addition) Per-ring scaling of an [n,2] field (the reference's scale_space,
+ * train_variations/train_normalize_per_bucket.py:20-27).  dist [n], in [n,2], out [n,2]: device
+ * fp32.  radii [n_rings+1], divisors [n_rings]: HOST arrays; they travel as kernel arguments.  Row i belongs to ring r
+ * iff radii[r] <= dist[i] < radii[r+1], compared in fp32, lower end included and upper end excluded.  Both components
+ * of a row in ring r become in / divisors[r], one correctly rounded fp32 division each.  A row in no ring (dist below
+ * radii[0], at or above radii[n_rings], or NaN) is copied unchanged, bit for bit.  Equal neighbouring radii make an
+ * empty ring; a row at that radius falls into the next non-empty one.  The inverse is the same call with the table
+ * fl32(1 / divisors[r]).  inr_mi355x/ringnorm.py::ring_scale_numpy restates this in numpy.
+ * out == in (in place) is allowed.  One launch on `stream`; no scratch, nothing is allocated, nothing is read back,
+ * capturable in a graph.  Four rows per lane, with 16-byte loads and stores when dist, in and out are 16-byte aligned;
+ * nothing is written at or beyond row n.
+ * INR_ERR_INVALID before any launch: a null pointer; n < 1 or n >= 2^31; n_rings outside 1..INR_BAND_MAX; a NaN radius;
+ * radii that decrease; a divisor that is zero, NaN or infinite; in / out not 8-byte aligned or dist not 4-byte aligned;
+ * out overlapping in other than out == in, or overlapping dist. */
+int inr_ring_scale(const float* dist, const float* in, float* out, int64_t n, const float* radii, const float* divisors,
+                   int32_t n_rings, void* stream);
 
 /* (v7 addition) Software coil compression (no reference counterpart).  A scan is coil-major:
  * data [C][N][2], complex fp32 (re, im) pairs, N = H*W pixels per coil.

@@ -1,6 +1,6 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network, the off-grid operators apart
-// (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, grid rows, band statistics, coil
-// compression.  Each checks its arguments, fills an argument struct, launches and maps the hipError_t to a code; none
+// (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, grid rows, band statistics, per-ring
+// scaling, coil compression.  Each checks its arguments, fills an argument struct, launches and maps the hipError_t to a code; none
 // allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -423,6 +423,38 @@ int inr_band_stats(const float* dist, const float* gt, const float* pred, const 
   }
   hipError_t e = inr::launch_band_stats(a, dist, gt, pred, mask, n, stats, scratch, (hipStream_t)stream);
   return hip_done(e, "inr_band_stats");
+}
+
+// ---- per-ring scaling (inr_ring_scale.hip) ----
+int inr_ring_scale(const float* dist, const float* in, float* out, int64_t n, const float* radii, const float* divisors,
+                   int32_t n_rings, void* stream) {
+  if (dist == nullptr || in == nullptr || out == nullptr || radii == nullptr || divisors == nullptr)
+    return fail(INR_ERR_INVALID, "inr_ring_scale: null argument");
+  if (n < 1 || n >= (1LL << 31)) return fail(INR_ERR_INVALID, "inr_ring_scale: n = %lld (1 <= n < 2^31 rows per call)", (long long)n);
+  if (n_rings < 1 || n_rings > INR_BAND_MAX)
+    return fail(INR_ERR_INVALID, "inr_ring_scale: n_rings = %d (1..%d)", (int)n_rings, INR_BAND_MAX);
+  inr::RingArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n_rings = n_rings;
+  for (int r = 0; r <= n_rings; ++r) {
+    if (!(radii[r] == radii[r])) return fail(INR_ERR_INVALID, "inr_ring_scale: radii[%d] is NaN", r);
+    if (r > 0 && radii[r] < radii[r - 1])
+      return fail(INR_ERR_INVALID, "inr_ring_scale: radii[%d] = %g is below radii[%d] = %g (radii must not decrease)", r,
+                  (double)radii[r], r - 1, (double)radii[r - 1]);
+    a.radii[r] = radii[r];
+  }
+  for (int r = 0; r < n_rings; ++r) {
+    if (!std::isfinite(divisors[r]) || divisors[r] == 0.f)
+      return fail(INR_ERR_INVALID, "inr_ring_scale: divisors[%d] = %g (must be finite and not zero)", r, (double)divisors[r]);
+    a.divisors[r] = divisors[r];
+  }
+  if ((((uintptr_t)in | (uintptr_t)out) & 7u) != 0 || ((uintptr_t)dist & 3u) != 0)
+    return fail(INR_ERR_INVALID, "inr_ring_scale: in / out must be 8-byte aligned and dist 4-byte aligned");
+  if (out != in && ranges_overlap(out, n * 8, in, n * 8))
+    return fail(INR_ERR_INVALID, "inr_ring_scale: out overlaps in partially (in place means out == in)");
+  if (ranges_overlap(out, n * 8, dist, n * 4)) return fail(INR_ERR_INVALID, "inr_ring_scale: out overlaps dist");
+  hipError_t e = inr::launch_ring_scale(a, dist, in, out, n, (hipStream_t)stream);
+  return hip_done(e, "inr_ring_scale");
 }
 
 // ---- coil compression (inr_coils.hip) ----

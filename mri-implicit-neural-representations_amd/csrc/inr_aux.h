@@ -180,6 +180,15 @@ long long band_stats_scratch_doubles(long long n, int n_bands);
 hipError_t launch_band_stats(const BandArgs& a, const float* dist, const float* gt, const float* pred,
                              const uint8_t* mask, long long n, double* stats, double* scratch, hipStream_t st);
 
+// per-ring scaling (inr_ring_scale.hip): ring r is radii[r] <= dist < radii[r+1]; the table travels as
+// kernel arguments like BandArgs
+struct RingArgs {
+  int n_rings;
+  float radii[BAND_MAX + 1], divisors[BAND_MAX];
+};
+hipError_t launch_ring_scale(const RingArgs& a, const float* dist, const float* in, float* out, long long n,
+                             hipStream_t st);
+
 // coil compression (inr_coils.hip): Gram matrix of a coil-major scan, product with a small matrix
 constexpr int COIL_MAX = 32;           // INR_COIL_MAX
 constexpr int COIL_TILE_PIXELS = 128;  // INR_COIL_TILE_PIXELS

@@ -125,6 +125,7 @@ SYMBOLS = {
     "inr_band_stats_scratch": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "inr_band_stats": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                  C.c_int32, _P, _P, _P]),
+    "inr_ring_scale": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, _P]),
     "inr_coil_gram_scratch": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_coil_gram": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
     "inr_coil_apply": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P]),

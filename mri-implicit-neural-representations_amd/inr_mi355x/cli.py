@@ -64,13 +64,16 @@ def parse_cli(val_and_samples: bool = True, argv=None):
     from .trajectory import add_baseline_flags, add_trajectory_flag, apply_baseline_flags, apply_trajectory_flag
     add_trajectory_flag(ap)
     add_baseline_flags(ap)
+    from .ringnorm import add_ring_normalize_flag
+    add_ring_normalize_flag(ap)
     opts = ap.parse_args(argv)
     if val_and_samples and opts.save_images and not opts.val:
         ap.error("--save-images needs --val (the pictures are those of the validation epoch)")
     if opts.band_report is not None and val_and_samples and not opts.val:
         ap.error("--band-report needs --val (the report is made from the validation epoch's prediction)")
     config = apply_virtual_coils_flag(apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts), opts)
-    return opts, apply_baseline_flags(apply_trajectory_flag(config, opts), opts)
+    from .ringnorm import apply_ring_normalize_flag
+    return opts, apply_ring_normalize_flag(apply_baseline_flags(apply_trajectory_flag(config, opts), opts), opts)
 
 
 def expand_data_samples(config: dict, samples) -> list:
@@ -200,6 +203,8 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
         res["trajectory"] = tr.trajectory_info
     if getattr(tr, "gridding", None) is not None:
         res["gridding"] = tr.gridding
+    if getattr(tr, "ring_table", None) is not None:
+        res["ring_normalization"] = tr.ring_table.summary()
     if extra:
         res.update(extra)
     if opts.val:

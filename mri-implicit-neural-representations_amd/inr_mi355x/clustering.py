@@ -56,11 +56,21 @@ def _ring_logmax_device(img: torch.Tensor, dist: torch.Tensor, bounds) -> list:
     return torch.log(torch.sqrt(torch.from_numpy(_band_field_device(img, dist, bounds, "max_abs2", "ring")))).tolist()
 
 
+def _radius(kcoords: torch.Tensor) -> torch.Tensor:
+    """dist_to_center of the reference: sqrt(ky^2 + kx^2) of (coil, y, x) coordinates"""
+    return torch.sqrt(kcoords[..., 1] ** 2 + kcoords[..., 2] ** 2)
+
+
 def partition_kspace(img: torch.Tensor, kcoords: torch.Tensor, no_steps: int = 40, no_parts: int = 4):
     """clustering.py:19-89.  img [C,H,W,2], kcoords [C,H,W,3] (coil, y, x).  Returns (labels of the no_steps
     initial rings, radii [no_parts+1] separating the final partitions; the last radius is 5 = 'everything')."""
+    return partition_rows(img, _radius(kcoords), no_steps, no_parts)
+
+
+def partition_rows(img: torch.Tensor, dist: torch.Tensor, no_steps: int = 40, no_parts: int = 4):
+    """partition_kspace of rows: img [..., 2] with the radius ``dist`` [...] of every row (the grid's rows, or the
+    off-grid samples of a trajectory with the radius of their own coordinates)."""
     from sklearn.cluster import KMeans
-    dist = torch.sqrt(kcoords[..., 1] ** 2 + kcoords[..., 2] ** 2)
     if _on_kernel(img, dist):
         means = _ring_logmax_device(img, dist, ring_bounds(no_steps))
     else:
@@ -91,8 +101,13 @@ def partition_kspace(img: torch.Tensor, kcoords: torch.Tensor, no_steps: int = 4
 def partition_and_stats(img: torch.Tensor, kcoords: torch.Tensor, no_steps: int = 40, no_parts: int = 4,
                         stat: str = "max") -> Tuple[torch.Tensor, np.ndarray]:
     """clustering.py:91-135: per final partition the max (or min) of |component| of the k-space inside it."""
-    _, radii = partition_kspace(img, kcoords, no_steps, no_parts)
-    dist = torch.sqrt(kcoords[..., 1] ** 2 + kcoords[..., 2] ** 2)
+    return partition_and_stats_rows(img, _radius(kcoords), no_steps, no_parts, stat)
+
+
+def partition_and_stats_rows(img: torch.Tensor, dist: torch.Tensor, no_steps: int = 40, no_parts: int = 4,
+                             stat: str = "max") -> Tuple[torch.Tensor, np.ndarray]:
+    """partition_and_stats of rows (see partition_rows); ring intervals are closed at both ends."""
+    _, radii = partition_rows(img, dist, no_steps, no_parts)
     if _on_kernel(img, dist):
         bounds = [(float(radii[i]), float(radii[i + 1])) for i in range(len(radii) - 1)]
         vals = _band_field_device(img, dist, bounds, "min_comp" if stat == "min" else "max_comp", "partition")

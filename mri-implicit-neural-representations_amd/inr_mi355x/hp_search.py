@@ -233,7 +233,9 @@ def hp_training_function(config: dict, max_epoch: int, data, *, seed: int = 0, i
     values and strict '>' of hp_model_training.py:112-115,202-207) plus 'steps', 'fit_seconds' and 'build_seconds'.  A trainer
     construction that raises NotImplementedError / ValueError -- nothing has been launched yet -- returns
     {'error': message}.  ``band_report`` (True, a number of rings or (lo, hi) pairs; bands.report_bounds): the result
-    also carries 'bands', the error by radius of the validation with the best PSNR."""
+    also carries 'bands', the error by radius of the validation with the best PSNR.  config['ring_normalization'] (a
+    config value or a searched one): the result carries the trial's table; the trainer scales into a buffer of its own, so
+    the cached dataset tensors ``data`` holds are the same bits after the trial as before it."""
     import torch
     cfg = trial_config(config, max_epoch)
     t0 = time.time()
@@ -270,6 +272,8 @@ def hp_training_function(config: dict, max_epoch: int, data, *, seed: int = 0, i
         print("hp search: config #{}: no validation epoch within max_epoch={} (val_epoch={}): its record keeps the "
               "initial {} / {}".format(cfg.get("config_index", 0), max_epoch, cfg["val_epoch"],
                                       INITIAL_STATS["best_psnr"], INITIAL_STATS["best_ssim"]))
+    if tr.ring_table is not None:  # config['ring_normalization'], given or searched: the table this trial fitted under
+        stats["ring_normalization"] = tr.ring_table.summary()
     return dict(stats, steps=tr.global_step, fit_seconds=t2 - t1, build_seconds=t1 - t0)
 
 

@@ -116,6 +116,10 @@ class Reconstructor:
             if self.shape[0] != self.coil_compression.coils_out:
                 raise ValueError(f"the checkpoint was fitted on {self.coil_compression.coils_out} virtual coils (of "
                                  f"{self.coil_compression.coils_in} physical ones) but shape has C = {self.shape[0]}")
+        self.ring_table = None  # ringnorm.RingTable of a ring-normalised fit: render() un-scales every chunk with it
+        if checkpoint.get("ring_normalization") is not None:
+            from .ringnorm import RingTable
+            self.ring_table = RingTable.from_state(checkpoint["ring_normalization"])
         load_weights(self.model, self.encoder, checkpoint, self._rebind_encoder)
         self.engine.pack()
 
@@ -157,7 +161,8 @@ class Reconstructor:
         ``coils`` = which coils, in output order.  Image-space configs: a finer grid is super-resolution, a window a zoom.
         k-space configs: a finer grid over the same window is a larger field of view, a narrower window a lower-resolution
         image.  Per ``chunk`` rows: the grid kernel into two reused buffers, the trainers' forward call, a slice of the
-        output; no full coordinate tensor is made."""
+        output; no full coordinate tensor is made.  A checkpoint of a ring-normalised fit: every chunk is
+        taken back to the data's units by one in-place inr_ring_scale call with the radius the grid kernel made."""
         spec = self.grid(height, width, scale, window, coils)
         n = spec.rows
         chunk = int(chunk or self.predict_chunk)
@@ -168,11 +173,14 @@ class Reconstructor:
             self._bufs = (torch.empty(chunk, 3, device=self.device), torch.empty(chunk, device=self.device))
         cbuf, dbuf = self._bufs
         out = torch.empty(n, 2, device=self.device)
+        with_dist = self.takes_dist or self.ring_table is not None
         for lo in range(0, n, chunk):
             hi = min(lo + chunk, n)
-            c, d = grid_rows(spec, lo, hi, coords_out=cbuf[:hi - lo], dist_out=dbuf[:hi - lo] if self.takes_dist else None,
-                             with_dist=self.takes_dist)
+            c, d = grid_rows(spec, lo, hi, coords_out=cbuf[:hi - lo], dist_out=dbuf[:hi - lo] if with_dist else None,
+                             with_dist=with_dist)
             out[lo:hi] = self._forward_rows(c, d)
+            if self.ring_table is not None:
+                self.ring_table.unscale(d, out[lo:hi], out=out[lo:hi])
         return out.reshape(*spec.shape, 2)
 
     # ---- pictures and numbers --------------------------------------------------------------------
@@ -343,6 +351,8 @@ def main(argv=None) -> None:
             print(format_band_table(res["bands"]), flush=True)
     if rec.coil_compression is not None:
         res["coil_compression"] = rec.coil_compression.summary()
+    if rec.ring_table is not None:
+        res["ring_normalization"] = rec.ring_table.summary()
     res["files"] = rec.save(opts.output_path, pred)
     if opts.expand_coils:
         res["files"].append(os.path.join(opts.output_path, "recon_physical.npy"))

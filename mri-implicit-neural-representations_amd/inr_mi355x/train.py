@@ -14,7 +14,7 @@ CLI (same flags as the reference, train.py:255-258):
     python -m inr_mi355x.train --config cfg.yaml [--output_path out] [--synthetic C,H,W] [--val]
                                [--shuffle] [--shuffle-seed S] [--save-images] [--band-report [N]] [--virtual-coils K]
                                [--trajectory ARG] [--trajectory-baseline ARG] [--trajectory-density ARG]
-                               [--trajectory-operator ARG] [--data_samples samples.yaml]
+                               [--trajectory-operator ARG] [--ring-normalize ARG] [--data_samples samples.yaml]
 --val runs the reference's validation epoch every config['val_epoch'] epochs (its line is printed) and saves a
 checkpoint every config['image_save_epoch'] epochs.  --save-images (with --val) also writes the reference's pictures
 (train.png, train_kspace.png, recon_kspace_{e}dB.png, recon_kspace_{e}_error.png, recon_{e}_{psnr}_psnr_{ssim}_ssim.png)
@@ -139,7 +139,9 @@ class INRTrainer(ResidentFit):
                  process_group=None, mask_seed: Optional[int] = None, graph_steps: bool = False,
                  model_seed: Optional[int] = None, coil_compression=None):
         config = self._init_fit(config, shape, device, seed, rank, world, process_group, graph_steps, coil_compression,
-                                trajectory_ok=True)
+                                trajectory_ok=True, ring_norm_ok=True)
+        from .ringnorm import check_ring_normalization
+        check_ring_normalization(config, mask)  # refusals, before anything is allocated
         self.in_image_space = bool(config.get("transform", False))
         if self.trajectory is not None:
             self._check_trajectory(config, mask, graph_steps, world)
@@ -394,8 +396,7 @@ class INRTrainer(ResidentFit):
             # the reference's CenterLoss draws randperm pairs on the CPU generator in the test loss too, which shifts every
             # later training pair; that consumption is not reproduced
             raise NotImplementedError("validation with loss 'LSL' (CenterLoss)")
-        pred = self.predict_all()
-        return self._validated(epoch, pred)
+        return self._validated(epoch, self._predict_raw())
 
     def _rebind_encoder(self, enc) -> None:
         super()._rebind_encoder(enc)

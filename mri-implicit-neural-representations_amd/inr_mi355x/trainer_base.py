@@ -98,14 +98,22 @@ class ResidentFit(ValidationMixin):
 
     # ---- set-up ----------------------------------------------------------------------------------
     def _init_fit(self, config: dict, shape, device, seed: int, rank: int, world: int, process_group,
-                  graph_steps: bool = False, coil_compression=None, trajectory_ok: bool = False) -> dict:
+                  graph_steps: bool = False, coil_compression=None, trajectory_ok: bool = False,
+                  ring_norm_ok: bool = False) -> dict:
         """Defaults, the shuffle settings (which refuse shuffle with graph steps before anything is allocated), the coil
         compression the data came through (config['virtual_coils'] = K needs the record of a K-coil compression and
         K-coil data, and the other way round: ValueError before anything is allocated), the trajectory of an off-grid fit
-        (config['trajectory']; drivers that do not pass ``trajectory_ok`` refuse it) and where the fit runs.  Returns the
-        trainer's own copy of the config."""
+        (config['trajectory']; drivers that do not pass ``trajectory_ok`` refuse it), the ring normalisation
+        (config['ring_normalization']; drivers that do not pass ``ring_norm_ok`` refuse it) and where the fit
+        runs.  Returns the trainer's own copy of the config."""
         config = set_default_configs(dict(config))
         self.config = config
+        from .ringnorm import parse_ring_normalization
+        self.ring_norm_spec = parse_ring_normalization(config.get("ring_normalization"))  # no default key: absent = off
+        self.ring_table = None
+        if self.ring_norm_spec is not None and not ring_norm_ok:
+            raise NotImplementedError(f"config['ring_normalization'] = {config['ring_normalization']!r}: ring-normalised "
+                                      "fits run in INRTrainer (python -m inr_mi355x.train) only")
         from .trajectory import describe, parse_trajectory
         self.trajectory = parse_trajectory(config["trajectory"])
         if self.trajectory is not None and not trajectory_ok:
@@ -185,6 +193,9 @@ class ResidentFit(ValidationMixin):
             values, rows = sample_kspace(self.image_full, self.shape, positions(self.trajectory, H, W))
             self.train_coords, self.train_values = rows.to(self.device).contiguous(), values.contiguous()
             self.n_train = self.train_coords.shape[0]
+        self._train_values_data = self.train_values  # the training rows in the data's own units (the gridding baseline's)
+        if self.ring_norm_spec is not None:  # before the epoch buffers below are built from train_values
+            self._ring_normalize()
         self.steps_per_epoch = math.ceil(self.n_train / self.bs)
         self.global_step = 0
         # config['shuffle']: plain batches are views of a second set of resident buffers, refilled by one kernel call per
@@ -201,6 +212,22 @@ class ResidentFit(ValidationMixin):
         self._t_coords, self._t_image, self._t_dist, self._t_mask = t.coords, t.image, t.dist, t.mask
         if t is self:
             self._t_coords, self._t_image = self.train_coords, self.train_values
+
+    @torch.no_grad()
+    def _ring_normalize(self) -> None:
+        """config['ring_normalization']: the table from the rows the fit trains on and from nothing else
+        -- the grid rows, or the off-grid samples with the radius of their own coordinates -- and the training targets
+        divided by it into a buffer of the trainer's own (train_values; image_full and whatever the caller handed in stay
+        what they are).  _norm_full = the normalised full-grid targets of the validation's test loss: the training targets
+        themselves on the grid, one more inr_ring_scale call off it."""
+        from .ringnorm import make_table
+        radius = lambda c: torch.sqrt(c[:, 1] ** 2 + c[:, 2] ** 2).contiguous()
+        self._grid_dist = radius(self.coords)
+        train_dist = self._grid_dist if self.trajectory is None else radius(self.train_coords)
+        self.ring_table = make_table(self.ring_norm_spec, self.config, self.train_values, train_dist)
+        self.train_values = self.ring_table.scale(train_dist, self.train_values)  # out of place
+        self._norm_full = self.train_values if self.trajectory is None else \
+            self.ring_table.scale(self._grid_dist, self.image_full)
 
     def _finish_init(self) -> None:
         if "pretrain" in self.config:  # train.py:117-121
@@ -223,7 +250,7 @@ class ResidentFit(ValidationMixin):
         name, w = self.trajectory_density
         torch.cuda.synchronize(self.device)
         t0 = time.time()
-        iterates, objective = cg_baseline(self.train_values, positions(self.trajectory, H, W), (C, H, W), w, iters,
+        iterates, objective = cg_baseline(self._train_values_data, positions(self.trajectory, H, W), (C, H, W), w, iters,
                                           operator=self.trajectory_operator or "exact")
         self.gridding_image = iterates[-1].contiguous()
         torch.cuda.synchronize(self.device)
@@ -301,9 +328,18 @@ class ResidentFit(ValidationMixin):
         raise NotImplementedError
 
     @torch.no_grad()
-    def predict_all(self, chunk: Optional[int] = None) -> torch.Tensor:
+    def _predict_raw(self, chunk: Optional[int] = None) -> torch.Tensor:
+        """the sweep as the network gives it: normalised units in a ring-normalised fit"""
         chunk = chunk or self.predict_chunk
         return torch.cat([self._forward_chunk(lo, min(lo + chunk, self.n)) for lo in range(0, self.n, chunk)], 0)
+
+    @torch.no_grad()
+    def predict_all(self, chunk: Optional[int] = None) -> torch.Tensor:
+        """[n,2]: the reconstruction of every grid row, in the data's own units"""
+        pred = self._predict_raw(chunk)
+        if self.ring_table is not None:
+            self.ring_table.unscale(self._grid_dist, pred, out=pred)
+        return pred
 
     @torch.no_grad()
     def evaluate(self) -> float:
@@ -319,15 +355,20 @@ class ResidentFit(ValidationMixin):
         batch_size rows against the FULL data, times ``scale``, summed, divided by the train loader's length --
         train.py:242), RSS, PSNR and SSIM on the device, one host read.  Updates best_psnr / best_psnr_ep / best_ssim /
         best_ssim_ep (strict '>', 0-based epoch).  Returns {'epoch', 'test_loss', 'psnr', 'ssim'}; test_loss is None for
-        per-coil fits (their val batches are not pinned down by the reference: INTEGRATION.md)."""
+        per-coil fits (their val batches are not pinned down by the reference: INTEGRATION.md).  Ring-normalised fits:
+        ``pred`` is the raw sweep; the test loss compares it with the normalised full-grid targets, then ONE in-place inverse
+        inr_ring_scale call takes it to the data's units for everything that follows."""
         loss_sum = None
+        targets = self.image_full if self.ring_table is None else self._norm_full
         if not self.per_coil:
             loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
             for it in range(math.ceil(self.n / self.bs)):  # the grid's batches (the training batches, unless off-grid)
                 lo, hi = it * self.bs, min((it + 1) * self.bs, self.n)
                 A = self._batch_hdr_A(it, lo, hi)  # HDR / tanh take the batch's kcoords (train.py:214-217)
-                loss, _ = self.engine.loss_grad(self.loss, pred[lo:hi], self.image_full[lo:hi], hi - lo, hdr_A=A)
+                loss, _ = self.engine.loss_grad(self.loss, pred[lo:hi], targets[lo:hi], hi - lo, hdr_A=A)
                 loss_sum += loss * self.scale
+        if self.ring_table is not None:
+            self.ring_table.unscale(self._grid_dist, pred, out=pred)
         m = self._device_metrics(self.image_full, pred, self.in_image_space)
         return self._finish_validation(epoch, m, loss_sum, self.steps_per_epoch)
 
@@ -346,6 +387,8 @@ class ResidentFit(ValidationMixin):
             rec["trajectory"] = self.trajectory_info
         if self.gridding is not None:
             rec["gridding"] = self.gridding
+        if self.ring_table is not None:
+            rec["ring_normalization"] = self.ring_table.summary()
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         return rec
@@ -357,6 +400,8 @@ class ResidentFit(ValidationMixin):
         ckpt = save_dict(self.model, self.encoder, self.engine, self.config)
         if self.coil_compression is not None:  # the reference's three entries stay as they are
             ckpt["coil_compression"] = self.coil_compression.state()
+        if self.ring_table is not None:
+            ckpt["ring_normalization"] = self.ring_table.state()
         return ckpt
 
     def _rebind_encoder(self, enc) -> None:
@@ -370,6 +415,10 @@ class ResidentFit(ValidationMixin):
         from .coils import same_compression
         mine = None if self.coil_compression is None else self.coil_compression.state()
         differs = same_compression(ckpt.get("coil_compression"), mine)
+        if differs is not None:
+            raise ValueError(f"checkpoint and trainer disagree: {differs} (checkpoint first)")
+        from .ringnorm import same_table
+        differs = same_table(ckpt.get("ring_normalization"), None if self.ring_table is None else self.ring_table.state())
         if differs is not None:
             raise ValueError(f"checkpoint and trainer disagree: {differs} (checkpoint first)")
         load_dict(self.model, self.encoder, self.engine, ckpt, self._rebind_encoder)

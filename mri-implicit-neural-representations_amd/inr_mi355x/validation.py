@@ -185,6 +185,8 @@ class ValidationMixin:
             rec["trajectory"] = self.trajectory_info
         if getattr(self, "gridding", None) is not None:  # ... next to the conventional reconstruction of the same samples
             rec["gridding"] = self.gridding
+        if getattr(self, "ring_table", None) is not None:  # fitted on ring-normalised targets, scored in the data's units
+            rec["ring_normalization"] = self.ring_table.summary()
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         self.val_history.append(rec)
