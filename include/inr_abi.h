@@ -56,7 +56,8 @@ extern "C" {
  *    inr_image_sets_after and inr_image_sets_read (weight images on demand: see inr_pack_params); inr_nufft_prepare,
  *    inr_nufft_interp, inr_nufft_spread, inr_nufft_finish and their scratch query (the same two operators by
  *    Kaiser-Bessel gridding around the caller's FFT); inr_ring_scale (rows divided by the divisor of the ring their radius
- *    lies in: ring-normalised fits).
+ *    lies in: ring-normalised fits); inr_row_cdf, its scratch query and inr_sample_epoch (weighted epochs: an integer
+ *    CDF of per-row weights and a stratified draw of an epoch's rows from it).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -449,6 +450,42 @@ int inr_image_metrics(const float* coils, int64_t C, int64_t H, int64_t W, const
 int inr_shuffle_epoch(int64_t n, int64_t batch_size, uint64_t seed, uint32_t epoch, const float* coords,
                       const float* gt, const float* dist, const uint8_t* mask, float* coords_out, float* gt_out,
                       float* dist_out, uint8_t* mask_out, int32_t* batch_counts, int64_t* order_out, void* stream);
+
+/* (v7 additions) Weighted epochs (no reference counterpart beyond the per-ring loss weights of
+ * train_variations/train_weighted_kspace.py and HDRLoss_FF.forward(..., weights=)): the rows of an
+ * epoch drawn with probability proportional to a per-row weight, so that the unweighted step's expected gradient is that
+ * of the weighted loss.  Integer arithmetic after one fp64 product per row: results do not depend on a summation order
+ * or a launch shape, and inr_mi355x/sampling.py (row_cdf_numpy, epoch_draw_numpy) restates them bit for bit.
+ *
+ * inr_row_cdf: w [n] device fp32, mask [n] device uint8 or NULL, scale an fp64 argument, cdf_out [n] device uint64.
+ *   ticks q_i = 0 where mask[i] == 0 or w_i is NaN, negative or +-0; otherwise min(2^32 - 1, floor(fp64(w_i) * scale)),
+ *   so +inf gives 2^32 - 1.  cdf_out[i] = q_0 + ... + q_i (inclusive; fits for n < 2^31).
+ *   Three launches on `stream`: per-tile sums, one workgroup over the tile sums in `scratch`, per-tile scan plus offset.
+ *   No workgroup waits on another.  scratch: uint64 words, their number from inr_row_cdf_scratch.  16-byte loads of w
+ *   and stores of cdf_out when both are 16-byte aligned (and mask 4-byte aligned).  Nothing is allocated or read back.
+ *   INR_ERR_INVALID before any launch: a null w, cdf_out or scratch; n < 1 or n >= 2^31; scale not finite or <= 0;
+ *   scratch_words below the query's; w not 4-byte or cdf_out / scratch not 8-byte aligned; cdf_out or scratch
+ *   overlapping another buffer.
+ *
+ * inr_sample_epoch: cdf [n] as above, m output rows, 1 <= n, m < 2^31.  With T = cdf[n-1] (read by the kernel) and
+ *   stride = T div m, output position j holds stratum s = order_m(j) -- inr_shuffle_epoch's permutation for (seed, epoch)
+ *   over [0, m) -- whose threshold is t_s = s * stride + (u_s mod stride), u_s = MIX(s ^ k0) * 2^32 + MIX(s ^ k1) under two
+ *   keys made from (seed, epoch) by the key schedule with the constant 0x85EBCA6B.  The row is the smallest i with
+ *   cdf[i] > t_s (binary search, at most 31 steps).  A row without ticks is never drawn; row i is drawn between
+ *   max(0, floor(q_i / stride) - 1) and floor(q_i / stride) + 2 times when T mod m < stride (the strata cover
+ *   [0, m * stride): the last T mod m ticks are never reached); equal ticks and m == n give the shuffle's order itself.
+ *   stride == 0 (T < m): every position takes the row of threshold 0, row 0 when T == 0 -- defined, not useful.
+ *   The buffers from `coords` on follow inr_shuffle_epoch: inputs have n rows, outputs m rows, batch_counts
+ *   ceil(m / batch_size) entries; one memset node (batch_counts only) and one launch.
+ *   INR_ERR_INVALID before any launch: a null or misaligned cdf; n or m outside [1, 2^31); and inr_shuffle_epoch's buffer
+ *   rules with its messages. */
+int inr_row_cdf_scratch(int64_t n, int64_t* scratch_words);
+int inr_row_cdf(const float* w, const uint8_t* mask, int64_t n, double scale, uint64_t* cdf_out, uint64_t* scratch,
+                int64_t scratch_words, void* stream);
+int inr_sample_epoch(const uint64_t* cdf, int64_t n, int64_t m, int64_t batch_size, uint64_t seed, uint32_t epoch,
+                     const float* coords, const float* gt, const float* dist, const uint8_t* mask, float* coords_out,
+                     float* gt_out, float* dist_out, uint8_t* mask_out, int32_t* batch_counts, int64_t* order_out,
+                     void* stream);
 
 /* (v7 additions) The pictures and the per-coil table of the validation epoch (train.py:221-238, models/utils.py:254-287).
  * All three: no atomics, fixed-order two-stage reductions (bitwise reproducible), no host synchronisation, nothing

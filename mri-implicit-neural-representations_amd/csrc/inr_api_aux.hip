@@ -1,7 +1,7 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network, the off-grid operators apart
-// (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, grid rows, band statistics, per-ring
-// scaling, coil compression.  Each checks its arguments, fills an argument struct, launches and maps the hipError_t to a code; none
-// allocates device memory or syncs.
+// (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, weighted epochs, grid rows, band
+// statistics, per-ring scaling, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
+// the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
 
@@ -312,28 +312,100 @@ static inr::ShuffleKeys shuffle_keys(int64_t n, uint64_t seed, uint32_t epoch) {
   return sk;
 }
 
+// the optional pairs of an epoch call (inr_shuffle_epoch, inr_sample_epoch) and its batch size
+static int epoch_buffers_check(const char* who, int64_t batch_size, const float* coords, const float* gt, const float* dist,
+                               const uint8_t* mask, const float* coords_out, const float* gt_out, const float* dist_out,
+                               const uint8_t* mask_out, const int32_t* batch_counts, const int64_t* order_out) {
+  if ((coords == nullptr) != (coords_out == nullptr) || (gt == nullptr) != (gt_out == nullptr) ||
+      (dist == nullptr) != (dist_out == nullptr) || (mask == nullptr && mask_out != nullptr))
+    return fail(INR_ERR_INVALID, "%s: an input and its output buffer go together", who);
+  if (coords_out == nullptr && gt_out == nullptr && dist_out == nullptr && mask_out == nullptr &&
+      batch_counts == nullptr && order_out == nullptr)
+    return fail(INR_ERR_INVALID, "%s: no output", who);
+  if (batch_counts != nullptr && (batch_size < 1 || batch_size >= (1LL << 31)))
+    return fail(INR_ERR_INVALID, "%s: batch_counts with batch_size = %lld", who, (long long)batch_size);
+  if (((uintptr_t)gt | (uintptr_t)gt_out) & 7u)
+    return fail(INR_ERR_INVALID, "%s: gt / gt_out must be 8-byte aligned ([n,2] rows move as one load)", who);
+  if ((coords != nullptr && coords == coords_out) || (gt != nullptr && gt == gt_out) ||
+      (dist != nullptr && dist == dist_out) || (mask != nullptr && mask == mask_out))
+    return fail(INR_ERR_INVALID, "%s: in-place (an output buffer is its input)", who);
+  return INR_OK;
+}
+
 int inr_shuffle_epoch(int64_t n, int64_t batch_size, uint64_t seed, uint32_t epoch, const float* coords,
                       const float* gt, const float* dist, const uint8_t* mask, float* coords_out, float* gt_out,
                       float* dist_out, uint8_t* mask_out, int32_t* batch_counts, int64_t* order_out, void* stream) {
   if (n < 1 || n >= (1LL << 31))
     return fail(INR_ERR_INVALID, "inr_shuffle_epoch: n = %lld (the 32-bit permutation covers 1 <= n < 2^31)", (long long)n);
-  if ((coords == nullptr) != (coords_out == nullptr) || (gt == nullptr) != (gt_out == nullptr) ||
-      (dist == nullptr) != (dist_out == nullptr) || (mask == nullptr && mask_out != nullptr))
-    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: an input and its output buffer go together");
-  if (coords_out == nullptr && gt_out == nullptr && dist_out == nullptr && mask_out == nullptr &&
-      batch_counts == nullptr && order_out == nullptr)
-    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: no output");
-  if (batch_counts != nullptr && (batch_size < 1 || batch_size >= (1LL << 31)))
-    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: batch_counts with batch_size = %lld", (long long)batch_size);
-  if (((uintptr_t)gt | (uintptr_t)gt_out) & 7u)
-    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: gt / gt_out must be 8-byte aligned ([n,2] rows move as one load)");
-  if ((coords != nullptr && coords == coords_out) || (gt != nullptr && gt == gt_out) ||
-      (dist != nullptr && dist == dist_out) || (mask != nullptr && mask == mask_out))
-    return fail(INR_ERR_INVALID, "inr_shuffle_epoch: in-place (an output buffer is its input)");
+  if (int rc = epoch_buffers_check("inr_shuffle_epoch", batch_size, coords, gt, dist, mask, coords_out, gt_out, dist_out,
+                                   mask_out, batch_counts, order_out))
+    return rc;
   const inr::ShuffleKeys sk = shuffle_keys(n, seed, epoch);
   hipError_t e = inr::launch_shuffle_epoch(sk, n, batch_size, coords, gt, dist, mask, coords_out, gt_out, dist_out,
                                            mask_out, batch_counts, (long long*)order_out, (hipStream_t)stream);
   return hip_done(e, "inr_shuffle_epoch");
+}
+
+// ---- weighted epochs (inr_sample.hip) ----
+// keys of a stratum's offset: the schedule of shuffle_keys with another constant, so that the offsets share nothing with
+// the permutation of the same (seed, epoch) (inr_mi355x/sampling.py draw_keys is the same text in Python)
+static inr::DrawKeys draw_keys(uint64_t seed, uint32_t epoch) {
+  const uint32_t c = 0x85EBCA6Bu;
+  using inr::shuffle_mix;
+  const uint32_t base = shuffle_mix(shuffle_mix(shuffle_mix((uint32_t)seed + c) ^ (uint32_t)(seed >> 32)) + epoch);
+  inr::DrawKeys dk;
+  for (int r = 0; r < 2; ++r) dk.k[r] = shuffle_mix(base + (uint32_t)(r + 1) * c);
+  return dk;
+}
+
+static int row_count_check(const char* who, const char* name, int64_t v) {
+  if (v < 1 || v >= (1LL << 31)) return fail(INR_ERR_INVALID, "%s: %s = %lld (1 <= %s < 2^31)", who, name, (long long)v, name);
+  return INR_OK;
+}
+
+int inr_row_cdf_scratch(int64_t n, int64_t* scratch_words) {
+  if (scratch_words == nullptr) return fail(INR_ERR_INVALID, "inr_row_cdf_scratch: null argument");
+  if (int rc = row_count_check("inr_row_cdf_scratch", "n", n)) return rc;
+  *scratch_words = inr::row_cdf_scratch_words(n);
+  return INR_OK;
+}
+
+int inr_row_cdf(const float* w, const uint8_t* mask, int64_t n, double scale, uint64_t* cdf_out, uint64_t* scratch,
+                int64_t scratch_words, void* stream) {
+  if (w == nullptr || cdf_out == nullptr || scratch == nullptr) return fail(INR_ERR_INVALID, "inr_row_cdf: null argument");
+  if (int rc = row_count_check("inr_row_cdf", "n", n)) return rc;
+  if (!std::isfinite(scale) || scale <= 0.0)
+    return fail(INR_ERR_INVALID, "inr_row_cdf: scale = %g (must be finite and > 0)", scale);
+  if (((uintptr_t)w & 3u) != 0 || (((uintptr_t)cdf_out | (uintptr_t)scratch) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_row_cdf: w must be 4-byte aligned, cdf_out and scratch 8-byte aligned");
+  const int64_t need = inr::row_cdf_scratch_words(n);
+  if (scratch_words < need)
+    return fail(INR_ERR_INVALID, "inr_row_cdf: scratch holds %lld words, needs %lld", (long long)scratch_words, (long long)need);
+  if (ranges_overlap(cdf_out, n * 8, w, n * 4) || ranges_overlap(cdf_out, n * 8, scratch, need * 8) ||
+      ranges_overlap(scratch, need * 8, w, n * 4) ||
+      (mask != nullptr && (ranges_overlap(cdf_out, n * 8, mask, n) || ranges_overlap(scratch, need * 8, mask, n))))
+    return fail(INR_ERR_INVALID, "inr_row_cdf: cdf_out / scratch overlaps another buffer");
+  hipError_t e = inr::launch_row_cdf(w, mask, n, scale, (unsigned long long*)cdf_out, (unsigned long long*)scratch,
+                                     (hipStream_t)stream);
+  return hip_done(e, "inr_row_cdf");
+}
+
+int inr_sample_epoch(const uint64_t* cdf, int64_t n, int64_t m, int64_t batch_size, uint64_t seed, uint32_t epoch,
+                     const float* coords, const float* gt, const float* dist, const uint8_t* mask, float* coords_out,
+                     float* gt_out, float* dist_out, uint8_t* mask_out, int32_t* batch_counts, int64_t* order_out,
+                     void* stream) {
+  if (cdf == nullptr) return fail(INR_ERR_INVALID, "inr_sample_epoch: null argument");
+  if (((uintptr_t)cdf & 7u) != 0) return fail(INR_ERR_INVALID, "inr_sample_epoch: cdf is not 8-byte aligned");
+  if (int rc = row_count_check("inr_sample_epoch", "n", n)) return rc;
+  if (int rc = row_count_check("inr_sample_epoch", "m", m)) return rc;
+  if (int rc = epoch_buffers_check("inr_sample_epoch", batch_size, coords, gt, dist, mask, coords_out, gt_out, dist_out,
+                                   mask_out, batch_counts, order_out))
+    return rc;
+  const inr::ShuffleKeys sk = shuffle_keys(m, seed, epoch);  // the strata are permuted, not the rows
+  hipError_t e = inr::launch_sample_epoch(sk, draw_keys(seed, epoch), (const unsigned long long*)cdf, n, m, batch_size,
+                                          coords, gt, dist, mask, coords_out, gt_out, dist_out, mask_out, batch_counts,
+                                          (long long*)order_out, (hipStream_t)stream);
+  return hip_done(e, "inr_sample_epoch");
 }
 
 // ---- rows of a coordinate grid (inr_grid.hip) ----

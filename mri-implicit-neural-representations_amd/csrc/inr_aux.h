@@ -157,6 +157,19 @@ hipError_t launch_shuffle_epoch(const ShuffleKeys& sk, long long n, long long bs
                                 const float* dist, const uint8_t* mask, float* coords_out, float* gt_out, float* dist_out,
                                 uint8_t* mask_out, int* batch_counts, long long* order_out, hipStream_t st);
 
+// weighted epochs (inr_sample.hip): the integer CDF of per-row ticks and the stratified draw from it.
+// sk permutes the m strata ([0, m), not [0, n)); dk are the two keys of a stratum's offset (inr_api_aux.hip draw_keys)
+struct DrawKeys {
+  unsigned k[2];
+};
+long long row_cdf_scratch_words(long long n);
+hipError_t launch_row_cdf(const float* w, const uint8_t* mask, long long n, double scale, unsigned long long* cdf,
+                          unsigned long long* scratch, hipStream_t st);
+hipError_t launch_sample_epoch(const ShuffleKeys& sk, const DrawKeys& dk, const unsigned long long* cdf, long long n,
+                               long long m, long long bs, const float* coords, const float* gt, const float* dist,
+                               const uint8_t* mask, float* coords_out, float* gt_out, float* dist_out, uint8_t* mask_out,
+                               int* batch_counts, long long* order_out, hipStream_t st);
+
 // rows of a coordinate grid (inr_grid.hip): the description of inr_grid_desc plus what the host derives
 // from it -- the three steps (IEEE divisions) and the (k, y, x) of the chunk's first row
 struct GridArgs {

@@ -1,34 +1,10 @@
 // inr_shuffle.hip -- the keyed row permutation of a shuffled epoch (gfx950)
-#include "inr_device.h"
-#include "inr_aux.h"
+#include "inr_epoch_rows.h"
 
 namespace inr {
 
-// ---------------------------------------------------------------------------------------------
-// Shuffled epochs: output row j of the epoch is input row order(j), a keyed bijection of [0, 2^(2h))
-// -- a balanced Feistel network of SHUFFLE_ROUNDS rounds over two h-bit halves, round function
-// (MIX(R ^ K_r) >> 16) & (2^h - 1) -- walked until it lands in [0, n).  32-bit integer arithmetic only, so
-// inr_mi355x/shuffle.py::epoch_order gives the same integers.  One thread per output row: the writes of a wave are
-// contiguous (12 / 8 / 4 / 1 / 8 bytes per lane), the reads are single rows anywhere in the source.
-// batch_counts (zeroed by the launcher on the same stream) takes one integer atomic per wave whose 64 rows lie in one
-// batch, one per lane in the wave that straddles a batch end: integer sums, exact in any order.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned shuffle_order(const ShuffleKeys& sk, unsigned j, unsigned n) {
-  const unsigned half = (1u << sk.h) - 1u;
-  unsigned x = j;
-  do {
-    unsigned l = x >> sk.h, r = x & half;
-#pragma unroll
-    for (int i = 0; i < SHUFFLE_ROUNDS; ++i) {
-      const unsigned t = l ^ ((shuffle_mix(r ^ sk.k[i]) >> 16) & half);
-      l = r;
-      r = t;
-    }
-    x = (l << sk.h) | r;
-  } while (x >= n);
-  return x;
-}
-
+// One thread per output row of the keyed permutation shuffle_order; the gather and the batch counts are epoch_row
+// (inr_epoch_rows.h).
 __global__ __launch_bounds__(256) void shuffle_epoch_kernel(const ShuffleKeys sk, unsigned n, unsigned bs,
                                                             const float* __restrict__ coords,
                                                             const float* __restrict__ gt,
@@ -41,56 +17,18 @@ __global__ __launch_bounds__(256) void shuffle_epoch_kernel(const ShuffleKeys sk
   const unsigned long long jj = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
   const bool live = jj < n;
   const unsigned j = (unsigned)jj;
-  int sampled = 0;
-  if (live) {
-    const size_t i = shuffle_order(sk, j, n);  // < n by construction
-    const size_t o = j;
-    if (coords_out != nullptr) {
-      const float c0 = coords[3 * i], c1 = coords[3 * i + 1], c2 = coords[3 * i + 2];
-      coords_out[3 * o] = c0;
-      coords_out[3 * o + 1] = c1;
-      coords_out[3 * o + 2] = c2;
-    }
-    if (gt_out != nullptr)
-      reinterpret_cast<float2*>(gt_out)[o] = reinterpret_cast<const float2*>(gt)[i];
-    if (dist_out != nullptr) dist_out[o] = dist[i];
-    sampled = 1;
-    if (mask != nullptr) {
-      const uint8_t m = mask[i];
-      if (mask_out != nullptr) mask_out[o] = m;
-      sampled = m != 0 ? 1 : 0;
-    }
-    if (order_out != nullptr) order_out[o] = (long long)i;
-  }
-  if (batch_counts != nullptr) {
-    // a wave's rows are [w0, w0 + 64): one batch unless a batch end falls inside (wave-uniform test)
-    const unsigned long long w0 = jj - (threadIdx.x & 63);
-    const unsigned long long wl = (w0 + 63 < n ? w0 + 63 : (unsigned long long)n - 1);
-    if (w0 < n) {
-      const unsigned b0 = (unsigned)(w0 / bs), b1 = (unsigned)(wl / bs);
-      if (b0 == b1) {
-        const int cnt = __popcll(__ballot(sampled != 0));
-        if ((threadIdx.x & 63) == 0 && cnt != 0) atomicAdd(batch_counts + b0, cnt);
-      } else if (live && sampled) {
-        atomicAdd(batch_counts + j / bs, 1);
-      }
-    }
-  }
+  const size_t i = live ? shuffle_order(sk, j, n) : 0;  // < n by construction
+  epoch_row(jj, n, bs, live, i, coords, gt, dist, mask, coords_out, gt_out, dist_out, mask_out, batch_counts, order_out);
 }
 
 hipError_t launch_shuffle_epoch(const ShuffleKeys& sk, long long n, long long bs, const float* coords, const float* gt,
                                 const float* dist, const uint8_t* mask, float* coords_out, float* gt_out, float* dist_out,
                                 uint8_t* mask_out, int* batch_counts, long long* order_out, hipStream_t st) {
-  if (batch_counts != nullptr) {
-    const long long nb = (n + bs - 1) / bs;
-    const hipError_t e = hipMemsetAsync(batch_counts, 0, (size_t)nb * sizeof(int), st);
-    if (e != hipSuccess) return e;
-  } else {
-    bs = 1;
-  }
+  const hipError_t e = epoch_counts_begin(batch_counts, n, &bs, st);
+  if (e != hipSuccess) return e;
   const unsigned grid = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(shuffle_epoch_kernel, dim3(grid), dim3(256), 0, st, sk, (unsigned)n,
-                     (unsigned)(bs > n ? n : bs), coords, gt, dist, mask, coords_out, gt_out, dist_out, mask_out,
+                     (unsigned)bs, coords, gt, dist, mask, coords_out, gt_out, dist_out, mask_out,
                      batch_counts, order_out);
   return hipGetLastError();
 }

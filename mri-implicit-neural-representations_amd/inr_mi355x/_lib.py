@@ -114,6 +114,10 @@ SYMBOLS = {
     "inr_image_metrics": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_int64, _P]),
     "inr_shuffle_epoch": (C.c_int, [C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                     _P]),
+    "inr_row_cdf_scratch": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "inr_row_cdf": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, _P, C.c_int64, _P]),
+    "inr_sample_epoch": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P, _P, _P]),
     "inr_kspace_display_scratch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_kspace_display": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, _P, C.c_int64, _P]),
     "inr_gray8_scratch": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
@@ -142,6 +146,7 @@ SYMBOLS = {
 NUDFT_TILE = 64  # INR_NUDFT_TILE
 COIL_MAX, COIL_TILE_PIXELS = 32, 128  # INR_COIL_MAX, INR_COIL_TILE_PIXELS
 BAND_MAX, BAND_FIELDS, BAND_TILE_ROWS = 64, 7, 1024  # INR_BAND_MAX, INR_BAND_FIELDS, INR_BAND_TILE_ROWS
+ROW_CDF_TILE = 1024  # rows per workgroup of inr_row_cdf (one scratch word each)
 METRICS_WORDS = 8  # inr_image_metrics' metrics_out: psnr, ssim, sse, max_ref, min_ref, max_rec, min_rec, data_range
 
 _lib = None

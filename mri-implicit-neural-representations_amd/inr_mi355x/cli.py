@@ -66,6 +66,8 @@ def parse_cli(val_and_samples: bool = True, argv=None):
     add_baseline_flags(ap)
     from .ringnorm import add_ring_normalize_flag
     add_ring_normalize_flag(ap)
+    from .sampling import add_row_sampling_flag, apply_row_sampling_flag
+    add_row_sampling_flag(ap)
     opts = ap.parse_args(argv)
     if val_and_samples and opts.save_images and not opts.val:
         ap.error("--save-images needs --val (the pictures are those of the validation epoch)")
@@ -73,7 +75,8 @@ def parse_cli(val_and_samples: bool = True, argv=None):
         ap.error("--band-report needs --val (the report is made from the validation epoch's prediction)")
     config = apply_virtual_coils_flag(apply_shuffle_flags(set_default_configs(get_config(opts.config)), opts), opts)
     from .ringnorm import apply_ring_normalize_flag
-    return opts, apply_ring_normalize_flag(apply_baseline_flags(apply_trajectory_flag(config, opts), opts), opts)
+    config = apply_ring_normalize_flag(apply_baseline_flags(apply_trajectory_flag(config, opts), opts), opts)
+    return opts, apply_row_sampling_flag(config, opts)
 
 
 def expand_data_samples(config: dict, samples) -> list:
@@ -205,6 +208,8 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
         res["gridding"] = tr.gridding
     if getattr(tr, "ring_table", None) is not None:
         res["ring_normalization"] = tr.ring_table.summary()
+    if getattr(tr, "row_sampling", None) is not None:
+        res["row_sampling"] = tr._row_sampling_summary()
     if extra:
         res.update(extra)
     if opts.val:

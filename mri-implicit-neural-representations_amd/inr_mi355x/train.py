@@ -139,7 +139,7 @@ class INRTrainer(ResidentFit):
                  process_group=None, mask_seed: Optional[int] = None, graph_steps: bool = False,
                  model_seed: Optional[int] = None, coil_compression=None):
         config = self._init_fit(config, shape, device, seed, rank, world, process_group, graph_steps, coil_compression,
-                                trajectory_ok=True, ring_norm_ok=True)
+                                trajectory_ok=True, ring_norm_ok=True, row_sampling_ok=True)
         from .ringnorm import check_ring_normalization
         check_ring_normalization(config, mask)  # refusals, before anything is allocated
         self.in_image_space = bool(config.get("transform", False))
@@ -275,6 +275,15 @@ class INRTrainer(ResidentFit):
         one read-back."""
         if self.loss.kind in (L.LOSS_HDR, L.LOSS_CENTER):
             self._hdr_A_epoch = self._epoch_buf.batch_means(hdr_weight(self._t_coords, self.loss.sigma))
+
+    def set_row_weights(self, weights: torch.Tensor) -> None:
+        """Weighted epochs (config['row_sampling']): new per-row weights (device fp32 [n_train]) for the
+        draws that follow -- the next refill of the epoch buffers, so a caller's ``on_epoch_end`` can steer the next
+        epoch by the residual of this one."""
+        if self.row_sampling is None:
+            raise RuntimeError("set_row_weights: the fit has no config['row_sampling']")
+        self._epoch_buf.set_weights(weights)
+        self._epoch_buf.mode = "weights"
 
     def _penalty(self):
         """(value, cplx_reg): the penalty VALUE the reference adds to the logged loss, at the parameters the step starts from

@@ -99,13 +99,14 @@ class ResidentFit(ValidationMixin):
     # ---- set-up ----------------------------------------------------------------------------------
     def _init_fit(self, config: dict, shape, device, seed: int, rank: int, world: int, process_group,
                   graph_steps: bool = False, coil_compression=None, trajectory_ok: bool = False,
-                  ring_norm_ok: bool = False) -> dict:
+                  ring_norm_ok: bool = False, row_sampling_ok: bool = False) -> dict:
         """Defaults, the shuffle settings (which refuse shuffle with graph steps before anything is allocated), the coil
         compression the data came through (config['virtual_coils'] = K needs the record of a K-coil compression and
         K-coil data, and the other way round: ValueError before anything is allocated), the trajectory of an off-grid fit
         (config['trajectory']; drivers that do not pass ``trajectory_ok`` refuse it), the ring normalisation
-        (config['ring_normalization']; drivers that do not pass ``ring_norm_ok`` refuse it) and where the fit
-        runs.  Returns the trainer's own copy of the config."""
+        (config['ring_normalization']; drivers that do not pass ``ring_norm_ok`` refuse it), the weighted
+        epochs (config['row_sampling']; drivers that do not pass ``row_sampling_ok`` refuse it) and where the
+        fit runs.  Returns the trainer's own copy of the config."""
         config = set_default_configs(dict(config))
         self.config = config
         from .ringnorm import parse_ring_normalization
@@ -148,6 +149,13 @@ class ResidentFit(ValidationMixin):
                              f"record says {coil_compression.coils_in} -> {coil_compression.coils_out}")
         self.coil_compression = coil_compression
         self.shuffle, self.shuffle_seed = shuffle_settings(config, seed, graph_steps)
+        from .sampling import check_row_sampling
+        self.row_sampling = check_row_sampling(config, self.trajectory, graph_steps, world)  # no default key: absent = off
+        if self.row_sampling is not None:
+            if not row_sampling_ok:
+                raise NotImplementedError(f"config['row_sampling'] = {config['row_sampling']!r}: weighted epochs run in "
+                                          "INRTrainer (python -m inr_mi355x.train) only")
+            self.shuffle = True  # the fit trains from epoch buffers and the draw always permutes: 'shuffle' adds nothing
         self.device = torch.device(device)
         self.rank, self.world, self.pg = rank, world, process_group
         self.shape = shape
@@ -206,6 +214,12 @@ class ResidentFit(ValidationMixin):
         t = self
         if self.shuffle and self.per_coil:
             self._coil_order = CoilOrder(self.steps_per_epoch, self.shuffle_seed)
+        elif self.row_sampling is not None:  # the same buffers, filled by a weighted draw (sampling.py)
+            from .sampling import WeightedEpochBuffers, make_weights
+            weights = make_weights(self.row_sampling, self.config, self.train_coords, self._train_values_data, self.shape,
+                                   self.trajectory)
+            t = self._epoch_buf = WeightedEpochBuffers(self.shuffle_seed, self.bs, weights, self.train_coords,
+                                                       self.train_values, dist=dist, mask=self.mask, mode=self.row_sampling)
         elif self.shuffle:
             t = self._epoch_buf = EpochBuffers(self.shuffle_seed, self.bs, self.train_coords, self.train_values, dist=dist,
                                                mask=self.mask)
@@ -310,6 +324,9 @@ class ResidentFit(ValidationMixin):
     def _refilled(self) -> None:
         """The epoch buffers hold a new epoch's rows."""
 
+    def _row_sampling_summary(self) -> Optional[dict]:
+        return self._epoch_buf.summary() if self.row_sampling is not None else None
+
     # ---- the loop --------------------------------------------------------------------------------
     def _log_value(self, loss):
         """what fit() keeps of step()'s return value"""
@@ -389,6 +406,8 @@ class ResidentFit(ValidationMixin):
             rec["gridding"] = self.gridding
         if self.ring_table is not None:
             rec["ring_normalization"] = self.ring_table.summary()
+        if self.row_sampling is not None:
+            rec["row_sampling"] = self._row_sampling_summary()
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         return rec

@@ -187,6 +187,8 @@ class ValidationMixin:
             rec["gridding"] = self.gridding
         if getattr(self, "ring_table", None) is not None:  # fitted on ring-normalised targets, scored in the data's units
             rec["ring_normalization"] = self.ring_table.summary()
+        if getattr(self, "row_sampling", None) is not None:  # trained on weighted epochs
+            rec["row_sampling"] = self._row_sampling_summary()
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         self.val_history.append(rec)
