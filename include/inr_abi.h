@@ -57,7 +57,8 @@ extern "C" {
  *    inr_nufft_interp, inr_nufft_spread, inr_nufft_finish and their scratch query (the same two operators by
  *    Kaiser-Bessel gridding around the caller's FFT); inr_ring_scale (rows divided by the divisor of the ring their radius
  *    lies in: ring-normalised fits); inr_row_cdf, its scratch query and inr_sample_epoch (weighted epochs: an integer
- *    CDF of per-row weights and a stratified draw of an epoch's rows from it).
+ *    CDF of per-row weights and a stratified draw of an epoch's rows from it); inr_plan_step_split (how a row-split
+ *    step with gradients is split over two launches and two GEMM parts).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -213,6 +214,18 @@ typedef struct inr_step_info {
   int32_t hidden_blocks; /* 32-row blocks of the hidden images in the plan's kernel build (either kernel; was reserved = 0) */
 } inr_step_info;
 int inr_plan_step_info(const inr_plan* plan, int64_t B, inr_step_info* out);
+/* (v7) How a row-split step WITH gradients is launched, for tests and tools; no reference counterpart.  inr_plan_step_info
+ * goes on describing the single launch (what a call without gradients, a capturing call and INR_OVERLAP=0 run).  Where
+ * that launch is one round of 256 workgroups with a few tiles one column block wider than the rest, the step is split:
+ * a first launch of 256 tiles of `lo1` blocks, then -- beside part A of the weight-gradient GEMM, which needs the first
+ * launch's stash slots only -- a remainder launch of the other blocks, and behind it part B of the GEMM over the
+ * remainder's slots.  out[0] engaged (0: out[1..14] are 0) -- the layout a call MAY run: without its second stream (creation
+ * failed) a step keeps the single launch, with the same results; [1] lo1; the remainder launch: [2] hi, [3] lo, [4] n_hi
+ * (as in inr_step_info, its blocks behind the first 256 lo1), [5] workgroups, [6] ncb; part A: [7] slots [0, out[7]),
+ * [8] slots per chunk, [9] chunks, [10] workgroups; part B: [11] first slot (slots up to n_tiles), [12] slots per
+ * chunk, [13] chunks, [14] workgroups; [15] n_slabs of inr_plan_workspace. */
+#define INR_STEP_SPLIT_WORDS 16
+int inr_plan_step_split(const inr_plan* plan, int64_t B, int64_t* out);
 /* INR_PRECISION_BF16 plans (v5; 16 words since v6).  Their backward pass stashes dZ in 8 bits under a power-of-two scale that
  * follows the gradient's magnitude from step to step; the sixteen words of that state live on the device with the plan (layout:
  * csrc/inr_w2.h -- [0..3] fused steps, [4..7] split steps: next scale, bits of the last step's largest scaled |dZ|, the

@@ -17,11 +17,12 @@ using inr::g_stamp_cap;
 
 extern "C" {
 
+// `blk0`, `accumulate`: the remainder launch of a split step (behind the first launch's blocks, adding to its slabs)
 static int launch_rs(const inr_plan* plan, const LossDesc& ld, inr::MlpArgs a, int64_t nt, const RsSchedule& sc,
-                     hipStream_t st) {
+                     hipStream_t st, int blk0 = 0, int accumulate = 0) {
   a.n_tiles = (int)nt;
   a.rs_hi = sc.hi, a.rs_lo = sc.lo, a.rs_x = sc.x, a.rs_rounds = sc.rounds;
-  a.tile0 = 0, a.accumulate = 0;
+  a.tile0 = 0, a.accumulate = accumulate, a.rs_blk0 = blk0;
   return hip_done(inr::rs_kernel(sc.ncb)(plan->nd, ld, a, sc.grid, st), "inr row-split kernel launch");
 }
 
@@ -252,12 +253,42 @@ static int run_fused_step(const inr_plan* plan, const LossDesc& ld, const inr::M
                           const char* who, const AdamFuse* af = nullptr) {
   const int64_t nb = c.nb;
   if (c.rs) {
-    // row-split kernel: one launch of whole rounds (no partial round to overlap), then the batch GEMM and the reduction
-    // over its grid's slabs
-    int rc = launch_rs(plan, ld, a, c.nt, c.rsched, st);
+    // row-split kernel.  One launch of whole rounds, then the batch GEMM and the reduction over its grid's slabs: calls
+    // without gradients (profiling), calls inside a graph capture (a captured graph keeps one branch) and every batch
+    // whose layout has no split
+    hipStream_t side = nullptr;
+    if (grads != nullptr && c.rs_split && !stream_capturing(st)) side = side_stream(plan);
+    if (side == nullptr) {
+      int rc = launch_rs(plan, ld, a, c.nt, c.rsched, st);
+      if (rc != INR_OK) return rc;
+      if (grads == nullptr) return INR_OK;
+      return finish_gradients(plan, a, c, c.rsched.grid, grads, loss_out, params, packed, st, who, af);
+    }
+    // split (inr_layout.hip rs_split_schedule): the narrower round, then GEMM part A here beside the remainder launch and
+    // GEMM part B (which needs the remainder's slots only) on the side stream
+    const RsSplit& sp = c.rsplit;
+    const hipEvent_t fork = plan->fork, join = plan->join;
+    float* chunk_slabs = a.slabs + (size_t)sp.first.grid * plan->nd.slab_floats;
+    inr::DwGemmArgs gA = sp.gA, gB = sp.gB;
+    gA.save = gB.save = a.save;
+    gA.slabs = chunk_slabs;
+    gB.slabs = chunk_slabs + (size_t)gA.n_chunks * plan->nd.slab_floats;
+    int rc = launch_rs(plan, ld, a, c.nt, sp.first, st);
+    hipError_t e = hipSuccess;
+    if (rc == INR_OK) e = hipEventRecord(fork, st);
+    if (rc == INR_OK && e == hipSuccess) e = hipStreamWaitEvent(side, fork, 0);
+    // (the remainder is queued before part A: the longer branch.  Queued the other way round, or with the branches' streams
+    // exchanged, the step takes the same time within 1 us: profiles/rs_split_before_after.json)
+    if (rc == INR_OK && e == hipSuccess) rc = launch_rs(plan, ld, a, c.nt, sp.rest, side, sp.blk0, 1);
+    if (rc == INR_OK && e == hipSuccess) e = inr::launch_dw_gemm(gA, st);
+    if (rc == INR_OK && e == hipSuccess) e = inr::launch_dw_gemm(gB, side);
+    if (rc == INR_OK && e == hipSuccess) e = hipEventRecord(join, side);
+    if (rc == INR_OK && e == hipSuccess) e = hipStreamWaitEvent(st, join, 0);
+    if (rc == INR_OK && e == hipSuccess)
+      e = reduce_stage(plan, a.slabs, sp.first.grid, grads, loss_out, params, packed, st, sp.red, af);
     if (rc != INR_OK) return rc;
-    if (grads == nullptr) return INR_OK;
-    return finish_gradients(plan, a, c, c.rsched.grid, grads, loss_out, params, packed, st, who, af);
+    if (e != hipSuccess) return hip_fail(e, (std::string(who) + ": split row-split step").c_str());
+    return INR_OK;
   }
   const StepSchedule& sc = c.step;
   hipStream_t side = nullptr;

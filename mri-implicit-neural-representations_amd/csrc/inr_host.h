@@ -94,6 +94,16 @@ struct RsSchedule {
   int grid, rounds, ncb, hi, lo, x;
 };
 
+// split row-split step (inr_layout.hip rs_split_schedule): `first` (256 tiles of `lo1` column blocks) and, behind its
+// blk0 blocks, `rest` are the two launches; GEMM part A covers the first launch's slots [0, blk0 / 8), part B the others
+struct RsSplit {
+  bool split;
+  int lo1, blk0;
+  RsSchedule first, rest;
+  inr::DwGemmArgs gA, gB;  // (split only)
+  inr::SlabSplit red;      // for the reduction: n2 = all chunk slabs
+};
+
 // A function of the plan, the batch size and the two per-call environment switches, and of nothing else.  Every entry
 // derives it ONCE (begin_call), checks the caller's workspace against it and launches from it, so the sizes that were
 // checked are the sizes that are written.
@@ -103,6 +113,8 @@ struct CallLayout {
   // dw_route 1
   bool rs;                      // the row-split kernel runs the fused step
   RsSchedule rsched;            // row-split plans (whichever kernel runs: the slabs cover its grid)
+  RsSplit rsplit;               // how a step with gradients splits that launch; n_slabs covers it under every switch
+  bool rs_split;                // this call may run it: rsplit.split, the row-split kernel chosen, INR_OVERLAP not 0
   inr::DwGemmArgs plain;        // the GEMM over the whole batch: unfused backward, row-split and unsplit steps
   inr::SlabSplit plain_red;
   StepSchedule step;            // (split = false on every other route)

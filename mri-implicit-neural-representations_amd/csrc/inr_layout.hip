@@ -1,6 +1,6 @@
 // inr_layout.hip -- the launch layout of one ABI call (CallLayout, inr_host.h): tiles and workgroups, which fused kernel
-// runs and its row-split schedule, the split-step schedule, the chunking of both weight-gradient GEMMs and the workspace
-// sizes; and the three ABI readers that only report it.
+// runs and its row-split schedule, the two split-step schedules, the chunking of both weight-gradient GEMMs and the
+// workspace sizes; and the ABI readers that only report it.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -152,6 +152,86 @@ static RsSchedule rs_schedule(int64_t nt) {
   return s;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Split row-split step.  A single round whose column blocks do not divide by 256 runs the (lo1 + 1)-block kernel on every
+// workgroup, `rem` = nblk mod 256 of them on real blocks and the others on a masked one (25 000 rows: 32 tiles of 7, 224
+// of 6 -- 30.1 GFLOP issued for 26.3), and the weight-gradient GEMM waits for the widest tile although it needs nothing
+// but the stash.  With gradients asked for, the step is launched as
+//   main stream:  fused kernel, 256 tiles of lo1 blocks  ->  (fork)  ->  GEMM part A: slots [0, 32 lo1)  ->  (join)  ->
+//                 reduction over the grid's slabs, A's chunk slabs, B's chunk slabs
+//   side stream:  (fork)  ->  fused kernel on the other `rem` blocks, accumulating into the slabs of workgroups
+//                 0 .. n_rem-1  ->  GEMM part B: slots [32 lo1, nt)  ->  (join)
+// 256 lo1 blocks end on a slot boundary, so A reads nothing the remainder writes.  A's workgroups + the remainder's are at
+// most 256, B's at most the remainder's: each has a CU whatever order the dispatcher picks.  The remainder's tiles are the
+// legal shape (k blocks, or an even number below k: rs_active) that the model below likes best; the split runs only
+// where that model puts it ahead of the single launch, never under 128 slots (lo1 < 4: the shapes whose step hashes are
+// pinned) and never for a schedule of several rounds.  The stash is the single launch's bit for bit; the last layer's
+// per-workgroup sums, the loss word and the GEMM's chunk sums group their coordinates differently (fixed order all the same).
+//
+// The model, in column-block units of the fused kernel (7.9 units = 250 us at the graded shape): a fused launch costs its
+// widest tile + 0.9 (rs_schedule); a GEMM launch costs kGemmWgCost + kGemmSlotCost per 128-coordinate slot of its longest
+// chunk on 256 x 256 workgroup tiles, half that per slot on the half-height tiles of short chunks (WBM = 2).
+// ---------------------------------------------------------------------------------------------
+constexpr double kRsRoundFixed = 0.9;
+// From the kernel traces of the graded step (profiles/rs_split_before_after.json; under the tracer the 7-block launch
+// takes 270.5 us, 1 unit = 34.2 us): dw_gemm_split_kernel in chunks of 9 half-height slots (part A) 88.0 us = 2.57 units,
+// of 2 (part B) 25.1 us = 0.73, of 8 (the whole batch, 250 workgroups) 85.1 us = 2.49.  A and B give 0.53 a slot and
+// 0.21 a launch; the whole-batch launch sits 0.18 above that line, so the fixed share is set between them.
+// Calibrated on that one plan (depth 5, gauss-256) and on nothing else: at another depth a column block of the fused
+// kernel is cheaper or dearer while these constants stay, so the unit drifts.  No other depth was measured.  The drift is
+// towards NOT splitting where the network is shallower (a depth-3 plan never engages: the model, not a measurement, says
+// its GEMM is shorter than a remainder launch), and such plans simply keep the single launch they had.
+constexpr double kGemmWgCost = 0.25;
+constexpr double kGemmSlotCost = 0.53;
+
+static double dw_gemm_model(const inr::DwGemmArgs& g) {
+  return kGemmWgCost + kGemmSlotCost * (double)g.tiles_per_chunk * (g.WBM == 2 ? 0.5 : 1.0);
+}
+
+// `gemm`: the plan's GEMM (no tiles or chunks yet); `one`, `plain`, `plain_red`: the single launch, its GEMM, its reduction
+static void rs_split_schedule(const inr::DwGemmArgs& gemm, int64_t nt, const RsSchedule& one, const inr::DwGemmArgs& plain,
+                              const inr::SlabSplit& plain_red, RsSplit* sp) {
+  sp->split = false;
+  sp->lo1 = sp->blk0 = 0;
+  sp->red = plain_red;
+  const int64_t nblk = 8 * nt, lo1 = nblk / kMaxBlocks, rem = nblk % kMaxBlocks;
+  if (one.grid != kMaxBlocks || one.rounds != 1 || rem == 0 || lo1 < 4) return;
+  const int64_t slotsA = lo1 * kMaxBlocks / 8;
+  double best = (double)one.ncb + kRsRoundFixed + dw_gemm_model(plain);  // the single launch + its GEMM
+  for (int k = 1; k <= kRsMaxNcb; ++k) {
+    for (int lo = 0; lo < k; lo += 2) {  // x tiles of k blocks, then y of `lo` (0: none), as few tiles as there can be
+      int64_t x = -1, y = 0;
+      if (lo == 0) {
+        if (rem % k == 0) x = rem / k;
+      } else {
+        for (y = 1; y < k && y * lo < rem; ++y)
+          if ((rem - y * lo) % k == 0) {
+            x = (rem - y * lo) / k;
+            break;
+          }
+      }
+      if (x < 1) continue;
+      const int64_t n_rem = x + y;
+      if (n_rem >= kMaxBlocks) continue;
+      inr::DwGemmArgs gA = gemm, gB = gemm;
+      dw_gemm_chunk(gA, 0, slotsA, (int)(kMaxBlocks - n_rem));
+      dw_gemm_chunk(gB, slotsA, nt, (int)n_rem);
+      if ((int64_t)gA.n_chunks * inr::dw_gemm_units(gA) > kMaxBlocks - n_rem) continue;
+      if ((int64_t)gB.n_chunks * inr::dw_gemm_units(gB) > n_rem) continue;
+      const double t = (double)lo1 + kRsRoundFixed +
+                       std::max(dw_gemm_model(gA), (double)k + kRsRoundFixed + dw_gemm_model(gB));
+      if (!(t < best - 1e-9)) continue;
+      best = t;
+      sp->split = true;
+      sp->lo1 = (int)lo1, sp->blk0 = (int)(lo1 * kMaxBlocks);
+      sp->first = RsSchedule{kMaxBlocks, 1, (int)lo1, (int)lo1, (int)lo1, kMaxBlocks};
+      sp->rest = RsSchedule{(int)n_rem, 1, k, k, lo == 0 ? k : lo, (int)x};
+      sp->gA = gA, sp->gB = gB;
+      sp->red.n2 = gA.n_chunks + gB.n_chunks;
+    }
+  }
+}
+
 // Which fused kernel runs a batch of nt 128-coordinate slots?  The row-split kernel, unless inr_mlp_kernel's rounds of 256
 // tiles are (all but) full: then both do the same MFMA work and the row-split kernel only adds a round (65 536 rows:
 // 6 + 6 + 4 column blocks per workgroup, 649 us against 629 us; 25 000 rows: 266 us against 316 us).
@@ -180,6 +260,7 @@ void call_layout(const inr_plan* plan, int64_t B, CallLayout* c) {
   c->n_slabs = c->nb;
   c->rs = false;
   c->step.split = false;
+  c->rsplit.split = false, c->rs_split = false;
   if (plan->dw_route == 2) {  // (the unfused backward of these plans needs nb slabs only: covered)
     dw_gemm_bf16_setup(plan, nt, &c->bf16, &c->bf16_red);
     c->n_slabs = c->nb + std::max(c->bf16.n_chunks, c->bf16.n_chunks_enc);
@@ -189,16 +270,21 @@ void call_layout(const inr_plan* plan, int64_t B, CallLayout* c) {
     c->plain_red = plan->gemm_cover;
     c->plain_red.n2 = c->plain.n_chunks;
     // (a split step has its own chunking; the unfused backward keeps the plain one)
-    step_schedule(plan, nt, c->nb, !(e_overlap != nullptr && e_overlap[0] == '0'), c->plain_red, &c->step);
+    const bool overlap = !(e_overlap != nullptr && e_overlap[0] == '0');
+    step_schedule(plan, nt, c->nb, overlap, c->plain_red, &c->step);
     // (row-split fused steps run rs_schedule's grid -- more workgroups than tiles while the batch is under 256 slots; the
-    // workspace does not follow INR_RS: it covers both fused kernels' grids)
+    // workspace follows neither INR_RS nor INR_OVERLAP: it covers both fused kernels' grids and every chunking)
     int64_t grid = c->nb;
+    int split_chunks = 0;
     if (nd.rs) {
       c->rsched = rs_schedule(nt);
       c->rs = rs_enabled(e_rs, nt);
       grid = std::max<int64_t>(grid, c->rsched.grid);
+      rs_split_schedule(plan->gemm, nt, c->rsched, c->plain, c->plain_red, &c->rsplit);
+      c->rs_split = c->rs && overlap && c->rsplit.split;
+      if (c->rsplit.split) split_chunks = c->rsplit.red.n2;
     }
-    c->n_slabs = grid + std::max(c->plain.n_chunks, c->step.red.n2);
+    c->n_slabs = grid + std::max(std::max(c->plain.n_chunks, c->step.red.n2), split_chunks);
   }
 }
 
@@ -229,7 +315,7 @@ int begin_call(const inr_plan* plan, int64_t B, const char* who, CallLayout* c) 
 
 extern "C" {
 
-// (the readers of a call's layout report a bad B in inr_plan_launch_dims' name, all three)
+// (the three older readers of a call's layout report a bad B in inr_plan_launch_dims' name; inr_plan_step_split in its own)
 int inr_plan_workspace(const inr_plan* plan, int64_t B, int64_t* step_save_slots, int64_t* n_slabs) {
   if (plan == nullptr || step_save_slots == nullptr || n_slabs == nullptr)
     return fail(INR_ERR_INVALID, "inr_plan_workspace: null argument");
@@ -252,6 +338,22 @@ int inr_plan_step_info(const inr_plan* plan, int64_t B, inr_step_info* out) {
   } else {
     out->grid = (int32_t)c.nb, out->rounds = (int32_t)((c.nt + c.nb - 1) / c.nb);
   }
+  return INR_OK;
+}
+
+int inr_plan_step_split(const inr_plan* plan, int64_t B, int64_t* out) {
+  if (plan == nullptr || out == nullptr) return fail(INR_ERR_INVALID, "inr_plan_step_split: null argument");
+  CallLayout c;
+  if (int rc = begin_call(plan, B, "inr_plan_step_split", &c)) return rc;
+  for (int i = 0; i < INR_STEP_SPLIT_WORDS; ++i) out[i] = 0;
+  out[15] = c.n_slabs;
+  if (!c.rs_split) return INR_OK;
+  const RsSplit& sp = c.rsplit;
+  inr::DwGemmArgs gA = sp.gA, gB = sp.gB;
+  out[0] = 1, out[1] = sp.lo1;
+  out[2] = sp.rest.hi, out[3] = sp.rest.lo, out[4] = sp.rest.x, out[5] = sp.rest.grid, out[6] = sp.rest.ncb;
+  out[7] = gA.n_tiles, out[8] = gA.tiles_per_chunk, out[9] = gA.n_chunks, out[10] = gA.n_chunks * inr::dw_gemm_units(gA);
+  out[11] = gB.tile0, out[12] = gB.tiles_per_chunk, out[13] = gB.n_chunks, out[14] = gB.n_chunks * inr::dw_gemm_units(gB);
   return INR_OK;
 }
 

@@ -34,6 +34,9 @@ struct MlpArgs {
   // row-split fused step (inr_mlp_rs_impl.h): tile t = round * grid + workgroup owns rs_hi column blocks of 16
   // coordinates if t < rs_x, else rs_lo, blocks in tile order; n_tiles = 128-coordinate stash slots
   int rs_hi, rs_lo, rs_x, rs_rounds;
+  // ... behind the rs_blk0 column blocks an earlier launch of the same step took (0: the only launch; the remainder
+  // launch of a split step passes it with accumulate = 1 -- inr_layout.hip rs_split_schedule)
+  int rs_blk0;
 };
 
 

@@ -564,7 +564,8 @@ __global__ __launch_bounds__(256) void inr_mlp_rs_kernel(const NetDesc nd, const
   float loss_acc = 0.f;
   if (((int)blockIdx.x < a.rs_x ? a.rs_hi : a.rs_lo) == 0 && a.accumulate == 0) {
     // a workgroup without column blocks (tiles past rs_x of a schedule whose `lo` is 0) still owns a slab the reduction
-    // sums: its last-layer entries are zero
+    // sums: its last-layer entries are zero.  (Not under accumulate: the slab then holds the first launch's sums -- and the
+    // remainder launch of a split step has no such workgroup anyway.)
     for (int i = tid; i < LL.M * LL.K; i += 256) slab[LL.gw_off + i] = 0.f;
     if (tid < LL.M) slab[LL.gb_off + tid] = 0.f;
   }
@@ -586,7 +587,7 @@ __global__ __launch_bounds__(256) void inr_mlp_rs_kernel(const NetDesc nd, const
   for (int r = 0; r < a.rs_rounds; ++r) {
     const int t = r * gridDim.x + blockIdx.x;
     const int n = t < a.rs_x ? a.rs_hi : a.rs_lo;
-    const int blk0 = t < a.rs_x ? t * a.rs_hi : a.rs_x * a.rs_hi + (t - a.rs_x) * a.rs_lo;
+    const int blk0 = a.rs_blk0 + (t < a.rs_x ? t * a.rs_hi : a.rs_x * a.rs_hi + (t - a.rs_x) * a.rs_lo);
     if (n == 0) continue;  // (workgroup-uniform)
     const bool first = r == 0 && a.accumulate == 0;
     const long long g0 = (long long)blk0 * 16;

@@ -76,6 +76,7 @@ SYMBOLS = {
     "inr_plan_launch_dims": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "inr_plan_workspace": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "inr_plan_step_info": (C.c_int, [_P, C.c_int64, C.POINTER(StepInfo)]),
+    "inr_plan_step_split": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_plan_grad_scale_state": (C.c_int, [_P, C.POINTER(C.c_float), _P]),
     "inr_pack_params": (C.c_int, [_P, _P, _P, _P]),
     "inr_plan_image_sets": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -143,6 +144,7 @@ SYMBOLS = {
     "inr_nufft_spread": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
     "inr_nufft_finish": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
 }
+STEP_SPLIT_WORDS = 16  # INR_STEP_SPLIT_WORDS
 NUDFT_TILE = 64  # INR_NUDFT_TILE
 COIL_MAX, COIL_TILE_PIXELS = 32, 128  # INR_COIL_MAX, INR_COIL_TILE_PIXELS
 BAND_MAX, BAND_FIELDS, BAND_TILE_ROWS = 64, 7, 1024  # INR_BAND_MAX, INR_BAND_FIELDS, INR_BAND_TILE_ROWS
