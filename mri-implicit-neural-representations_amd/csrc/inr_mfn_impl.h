@@ -105,7 +105,7 @@ __device__ __forceinline__ void mfn_epilogue(const f32x16 (&accU)[MT], const f32
                                              const float* __restrict__ cbias, const float* __restrict__ gm, float x2,
                                              float* __restrict__ sv, int wcol, int lane) {
   const int half = lane >> 5, col = lane & 31;
-  constexpr int hsz = NB * 32 * TL;
+  constexpr int hsz = stash_tensor_floats(NB, TL);
   float* Rl = R + (32 * m0 + 4 * half) * INR_LDS_LD + col;
   // stash stores through a buffer descriptor (tensor and row offsets scalar): three per element, no 64-bit vector adds
   const __amdgpu_buffer_rsrc_t rsv = uniform_rsrc(sv, 3 * hsz * 4);
@@ -149,8 +149,8 @@ __device__ __forceinline__ void mfn_epilogue(const f32x16 (&accU)[MT], const f32
         }
         Rl[row * INR_LDS_LD] = h;
         stash_store(rsv, voff, row * TL * 4, sn);
-        stash_store(rsv, voff, (hsz + row * TL) * 4, lc);
-        stash_store(rsv, voff, (2 * hsz + row * TL) * 4, h);
+        stash_store(rsv, voff, (MfnStash::LCOS * hsz + row * TL) * 4, lc);
+        stash_store(rsv, voff, (MfnStash::HH * hsz + row * TL) * 4, h);
       }
     }
   }
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mfn_kernel(const NetDesc nd, cons
   constexpr int TL = NW * 32;
   constexpr int RS = NB * 32 * INR_LDS_LD;   // floats per wave image
   constexpr int HS = 32 * INR_LDS_LD;        // floats per wave head-gradient image
-  constexpr int HSZ = NB * 32 * TL;          // floats per stashed tensor
+  constexpr MfnStash ST(NB, TL);             // the stash of a tile (inr_stash.h)
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int half = lane >> 5, col = lane & 31;
@@ -376,10 +376,9 @@ __global__ __launch_bounds__(NW * 64) void inr_mfn_kernel(const NetDesc nd, cons
     const bool saving = (MODE != MODE_FWD) || (a.save != nullptr);
     float* sv = a.save;
     if (saving) sv += (size_t)(a.save_by_block ? blockIdx.x : tile) * nd.save_floats_per_tile;
-    // stash: stage i -> [f_i | l_i cos u_i | h_i] ; then encoder features; without a save buffer the
-    // encoder features still need a home for stages >= 1: the caller always passes one for MFN
-    float* sv_enc = sv + (size_t)3 * S * HSZ;
-    float* sv_x2 = sv_enc + (size_t)Fl[0].Kblk * 32 * TL;  // GABOR: |x_c|^2 of the tile's coordinates [TL]
+    // without a save buffer the encoder features still need a home for stages >= 1: the caller always passes one for MFN
+    float* sv_enc = sv + ST.enc(S);
+    float* sv_x2 = sv_enc + (size_t)Fl[0].Kblk * 32 * ST.TL;  // sv + ST.x2(S, rows).  GABOR: |x_c|^2 of the tile's coordinates
     float x2 = 0.f;
     float keep = 1.f;  // bounded linears: per-coordinate 0/1 (recomputed per stage)
     const float dist = (a.dist != nullptr && valid) ? a.dist[crow] : 0.f;
@@ -453,10 +452,10 @@ __global__ __launch_bounds__(NW * 64) void inr_mfn_kernel(const NetDesc nd, cons
             for (int m = 0; m < MT; ++m) q[m] = zero16();
             gemm_enc_stash<MT, TL, NB>(q, a.packed + Ml[i].pf_off + (size_t)m0 * 256, sv_enc, nd.E, wcol, lane);
             mfn_epilogue<NB, MT, TL, false, true>(accU, q, m0, R, a.packed + Fl[i].pbias_off,
-                                                  a.packed + Ml[i].pbias_off, x2, sv + (size_t)3 * i * HSZ, wcol, lane);
+                                                  a.packed + Ml[i].pbias_off, x2, sv + (size_t)3 * i * ST.T /* ST.slot(i, ST.F), written out */, wcol, lane);
           } else {
             mfn_epilogue<NB, MT, TL, false, false>(accU, accU, m0, R, a.packed + Fl[i].pbias_off, nullptr, 0.f,
-                                                   sv + (size_t)3 * i * HSZ, wcol, lane);
+                                                   sv + (size_t)3 * i * ST.T /* ST.slot(i, ST.F), written out */, wcol, lane);
           }
         }
         // head fed by this stage, if any (output_layers are distinct stages)
@@ -509,7 +508,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mfn_kernel(const NetDesc nd, cons
       if (GABOR && MODE == MODE_BWD) x2 = 0.f;  // the passes read sv_x2 themselves
 #pragma unroll 1
       for (int i = S - 1; i >= 1; --i) {
-        float* svi = sv + (size_t)3 * i * HSZ;
+        float* svi = sv + (size_t)3 * i * ST.T /* ST.slot(i, ST.F), written out */;
         // ---- heads fed by stage i: dW_head, and their contribution W_k^T g_k to g_h_i
         // ---- head fed by stage i (if any): its contribution W_k^T g_k to g_h_i now, its dW below, once the
         //      accumulators are parked (a call with 16 live accumulator blocks would spill all of them)
@@ -537,10 +536,10 @@ __global__ __launch_bounds__(NW * 64) void inr_mfn_kernel(const NetDesc nd, cons
         if (kh >= 0) {
           const LayerDesc& Hd = nd.L[nd.head_layer[kh]];
           if (Hd.M <= 4 && (TL == 64 || TL == 128)) {  // head rows on the vector ALUs (inr_mlp_impl.h)
-            dw_rows4_valu<(TL == 128 ? 128 : 64), NW>(HGall, HS, svi + (size_t)2 * HSZ, NB * 32, Hd.M, Hd.K,
+            dw_rows4_valu<(TL == 128 ? 128 : 64), NW>(HGall, HS, svi + ST.slot(0, ST.HH), NB * 32, Hd.M, Hd.K,
                                                       slab + Hd.gw_off, slab + Hd.gb_off, first, w, lane);
           } else {
-            BSrcStash<TL> bs{svi + (size_t)2 * HSZ};  // h_i
+            BSrcStash<TL> bs{svi + ST.slot(0, ST.HH)};  // h_i
             for (int nn = w; nn < Hd.Kblk; nn += NW)
               dw_pass<1, TL, false, BSrcStash<TL>>(HGall, HS, bs, nn, slab + Hd.gw_off, slab + Hd.gb_off, Hd.M, Hd.K,
                                                    first, nn == 0, lane);
@@ -549,17 +548,17 @@ __global__ __launch_bounds__(NW * 64) void inr_mfn_kernel(const NetDesc nd, cons
         // ---- dL_{i-1} = (g_h*f_i)^T h_{i-1} (+ db), dF_i = (g_h*l_i cos u_i)^T x (+ dc)
         {
           if (nd.bounded) {
-            BSrcStashKeep<TL> bh{sv + (size_t)(3 * (i - 1) + 2) * HSZ, a.dist, row0, a.B, nd.bound_lo[i - 1],
+            BSrcStashKeep<TL> bh{sv + (size_t)(3 * (i - 1) + ST.HH) * ST.T /* ST.slot(i - 1, ST.HH), written out */, a.dist, row0, a.B, nd.bound_lo[i - 1],
                                  nd.bound_hi[i - 1]};
             dwf_layer<NB, TL, false, BSrcStashKeep<TL>>(lds, RS, svi, bh, Ll[i - 1], slab, nullptr, first, w, NW, lane);
           } else {
-            BSrcStash<TL> bh{sv + (size_t)(3 * (i - 1) + 2) * HSZ};
+            BSrcStash<TL> bh{sv + (size_t)(3 * (i - 1) + ST.HH) * ST.T /* ST.slot(i - 1, ST.HH), written out */};
             dwf_layer<NB, TL, false, BSrcStash<TL>>(lds, RS, svi, bh, Ll[i - 1], slab, nullptr, first, w, NW, lane);
           }
           BSrcStash<TL> bx{sv_enc};
-          dwf_layer<NB, TL, false, BSrcStash<TL>>(lds, RS, svi + HSZ, bx, Fl[i], slab, nullptr, first, w, NW, lane);
+          dwf_layer<NB, TL, false, BSrcStash<TL>>(lds, RS, svi + ST.slot(0, ST.LCOS), bx, Fl[i], slab, nullptr, first, w, NW, lane);
           // GABOR: S1_i = (g_h * h_i)^T x, s0_i, T_i  ->  d mu_i, d gamma_i in the finishing kernel
-          if (GABOR) dwf_layer<NB, TL, true, BSrcStash<TL>>(lds, RS, svi + 2 * HSZ, bx, Ml[i], slab, sv_x2, first, w, NW, lane);
+          if (GABOR) dwf_layer<NB, TL, true, BSrcStash<TL>>(lds, RS, svi + ST.slot(0, ST.HH), bx, Ml[i], slab, sv_x2, first, w, NW, lane);
         }
         __syncthreads();
         // ---- g_h_{i-1} = L_{i-1}^T (g_h_i * f_i)   (in place on the image, which is dead afterwards)
@@ -580,8 +579,8 @@ __global__ __launch_bounds__(NW * 64) void inr_mfn_kernel(const NetDesc nd, cons
       __syncthreads();
       {
         BSrcStash<TL> bx{sv_enc};
-        dwf_layer<NB, TL, false, BSrcStash<TL>>(lds, RS, sv + HSZ, bx, Fl[0], slab, nullptr, first, w, NW, lane);
-        if (GABOR) dwf_layer<NB, TL, true, BSrcStash<TL>>(lds, RS, sv + 2 * HSZ, bx, Ml[0], slab, sv_x2, first, w, NW, lane);
+        dwf_layer<NB, TL, false, BSrcStash<TL>>(lds, RS, sv + ST.slot(0, ST.LCOS), bx, Fl[0], slab, nullptr, first, w, NW, lane);
+        if (GABOR) dwf_layer<NB, TL, true, BSrcStash<TL>>(lds, RS, sv + ST.slot(0, ST.HH), bx, Ml[0], slab, sv_x2, first, w, NW, lane);
       }
       __syncthreads();
       first = false;

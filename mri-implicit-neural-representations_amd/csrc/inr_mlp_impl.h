@@ -26,6 +26,7 @@
 #pragma once
 #include "inr_device.h"
 #include "inr_mlp_args.h"
+#include "inr_stash.h"
 
 namespace inr {
 
@@ -529,7 +530,7 @@ __device__ __forceinline__ void fwd_layer(f32x16 (&acc)[NBOUT], const float* R, 
   const auto p = make_p();
   const int gstride = ALDS ? (col < 4 ? 8 : 0) : NBT * 64;  // float4s between consecutive groups
   constexpr int n4 = NB * 4;  // K = 32*NB features -> 16*NB k-steps -> 4*NB groups of 4 (even)
-  constexpr int hsz = NB * 32 * TL;
+  constexpr int hsz = stash_tensor_floats(NB, TL);
   constexpr bool G2D = HACT == ACT_GABOR2D;  // always called with SAVE: its orth inputs live in the stash
   constexpr bool PAIR = HACT == ACT_GABOR || G2D;
   const float* Rcol = R + col;
@@ -574,7 +575,7 @@ __device__ __forceinline__ void fwd_last_valu_impl(float (&out4)[4], float* R, c
                                                    float* __restrict__ sv, int wcol, int lane) {
   const int half = lane >> 5, col = lane & 31;
   constexpr int n4 = NB * 4;
-  constexpr int hsz = NB * 32 * TL;
+  constexpr int hsz = stash_tensor_floats(NB, TL);
   typedef __attribute__((address_space(3))) float lfloat;
   typedef const __attribute__((address_space(3))) f32x4 lf4;
   lfloat* Rz = (lfloat*)(R + col + half * INR_LDS_LD);  // row 8 s4 + 2e + half, this lane's column
@@ -673,7 +674,7 @@ template <int NB, int TL, int NBT = NB>
 __device__ __forceinline__ void orth_epilogue(const f32x16 (&acc)[NB], const float* __restrict__ bias,
                                               float* __restrict__ svO, int wcol, int lane) {
   const int half = lane >> 5;
-  constexpr int hsz = NBT * 32 * TL;
+  constexpr int hsz = stash_tensor_floats(NBT, TL);
   float* so = svO + (4 * half) * TL + wcol;
   const float* bl = bias + 4 * half;
 #pragma unroll
@@ -755,7 +756,7 @@ __device__ __forceinline__ void bwd_dx(f32x16 (&acc)[NB], float* R, const float*
   const int half = lane >> 5, col = lane & 31;
   const AFragPtr p = afrag_ptr(wpT, lane);
   const int n4 = Mpad8 >> 3;
-  constexpr int hsz = NB * 32 * TL;
+  constexpr int hsz = stash_tensor_floats(NB, TL);
   float* Rcol = R + col;
   // own row's act' entries (the two tensors of a PAIR layer are hsz floats apart)
   const __amdgpu_buffer_rsrc_t rd = uniform_rsrc(HASD ? (const void*)sv_d : (const void*)wpT, 2 * hsz * 4);
@@ -1174,8 +1175,9 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
   constexpr int TL = NW * 32;                      // coordinates per tile
   constexpr bool G2D = HACT == ACT_GABOR2D;        // WIRE2D: a second Linear (scale_orth) per layer
   constexpr bool PAIR = HACT == ACT_GABOR || G2D;  // complex layers as interleaved (Re, Im) rows
-  // stashed tensors per hidden layer: h, act' (SIREN/FFN) | h, dA, dB (WIRE) | h, dA, dB, dA2, dB2, orth, u^2+v^2 (2D)
-  constexpr int NS = G2D ? 7 : (PAIR ? 3 : 2);
+  // The stash of a tile (inr_stash.h).  This kernel writes ST.slot(l, s) out on ST's constants, (ST.NS * l + s) * ST.T with
+  // the named slots: through the calls its WIRE2D builds compile to other address arithmetic.
+  constexpr MlpStash ST(NB, TL, G2D ? STASH_GABOR2D : (PAIR ? STASH_GABOR : STASH_REAL));
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int half = lane >> 5, col = lane & 31;
@@ -1204,7 +1206,6 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
     for (int i = tid; i < 3 * nd.E; i += NW * 64) encB_lds[i] = a.encB[i];
   }
   if (INMODE == IN_GAUSS || (a.ll_lds && MODE != MODE_BWD)) __syncthreads();
-  constexpr int HSZ = NB * 32 * TL;  // floats per stashed tensor
   float* slab = (MODE != MODE_FWD) ? a.slabs + (size_t)blockIdx.x * nd.slab_floats : nullptr;
   float loss_acc = 0.f;
   bool first = a.accumulate == 0;  // accumulate: a follow-up launch of the same step (inr_api.hip, split launches)
@@ -1225,9 +1226,9 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
     const bool saving = G2D || (MODE != MODE_FWD) || (a.save != nullptr);  // WIRE2D: the API insists on a buffer
     float* sv = a.save;
     if (saving) sv += (size_t)(a.save_by_block ? blockIdx.x : tile) * nd.save_floats_per_tile;
-    float* sv_last = sv + (size_t)NS * (D - 1) * HSZ;  // [4][TL]: act'(z_last) of output rows 0..3
-    float* sv_enc = sv_last + 4 * TL;                   // [Kblk0*32][TL] encoder features (gauss mode)
-    float* sv_g = sv_last + 4 * TL;                     // WIRE2D (never gauss): copy of a layer's output gradient
+    float* sv_last = sv + (size_t)ST.NS * (D - 1) * ST.T;  // sv + ST.last_dact(D)
+    float* sv_enc = sv_last + 4 * ST.TL;                   // sv + ST.enc(D)
+    float* sv_g = sv_last + 4 * ST.TL;                     // sv + ST.grad_copy(D): WIRE2D, never with sv_enc
 
     // what the loss section needs from memory, requested now: fetched where it is used, the sampling mask, the target row
     // and the four last-layer biases were up to seven serialized round trips between the last GEMM and the loss
@@ -1278,7 +1279,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
           for (int m = 0; m < NB; ++m) acc[m] = zero16();
           fwd_layer0_x<NB>(acc, a.packed + O0.pf_off, a.x + (size_t)(valid ? crow : 0) * O0.K, valid, O0.K, O0.Kpad8,
                            lane);
-          orth_epilogue<NB, TL>(acc, a.packed + O0.pbias_off, sv + (size_t)5 * HSZ, wcol, lane);
+          orth_epilogue<NB, TL>(acc, a.packed + O0.pbias_off, sv + (size_t)ST.ORTH * ST.T, wcol, lane);
         }
       }
       INR_STAMP(1);
@@ -1288,7 +1289,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
         f32x16 acc[NB];
 #pragma unroll
         for (int m = 0; m < NB; ++m) acc[m] = zero16();
-        float* sh = sv + (size_t)(NS * (l - 1)) * HSZ;
+        float* sh = sv + (size_t)(ST.NS * (l - 1)) * ST.T;
         if (saving)
           fwd_layer<NB, NB, TL, HACT, true>(acc, R, a.packed + Ll.pf_off, ap, sh, wcol, lane);
         else
@@ -1299,7 +1300,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
 #pragma unroll
           for (int m = 0; m < NB; ++m) acc[m] = zero16();
           gemm_stash_nat<NB, TL>(acc, a.packed + Ol.pf_off, sh, wcol, lane);
-          orth_epilogue<NB, TL>(acc, a.packed + Ol.pbias_off, sv + (size_t)(NS * l + 5) * HSZ, wcol, lane);
+          orth_epilogue<NB, TL>(acc, a.packed + Ol.pbias_off, sv + (size_t)(ST.NS * l + ST.ORTH) * ST.T, wcol, lane);
         }
         INR_STAMP(1 + l);
       }
@@ -1308,7 +1309,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
       accL[0] = zero16();
       {
         const ActParams ap{nd.L[D - 2].omega, nd.L[D - 2].s0};
-        float* sh = sv + (size_t)(NS * (D - 2)) * HSZ;
+        float* sh = sv + (size_t)(ST.NS * (D - 2)) * ST.T;
         if (!PAIR && a.ll_lds) {  // (ll_lds: <= 4 output rows, their fragments in LDS)
           float o4[4];
           constexpr int HA = PAIR ? ACT_ID : HACT;
@@ -1392,10 +1393,10 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
           dw_rows4_valu<TL == 128 ? 128 : 64, NW, ACT_ID>(lds, RS, nullptr, NB * 32, LL.M, LL.K, slab + LL.gw_off,
                                                           slab + LL.gb_off, first, w, lane, dz_all, 8 * INR_LDS_LD, 0.f);
         } else if (LL.M <= 4 && (TL == 128 || TL == 64)) {
-          dw_rows4_valu<TL == 128 ? 128 : 64, NW>(lds, RS, sv + (size_t)(NS * (D - 2)) * HSZ, NB * 32, LL.M, LL.K,
+          dw_rows4_valu<TL == 128 ? 128 : 64, NW>(lds, RS, sv + (size_t)(ST.NS * (D - 2)) * ST.T, NB * 32, LL.M, LL.K,
                                                   slab + LL.gw_off, slab + LL.gb_off, first, w, lane);
         } else {
-          BSrcStash<TL> bs{sv + (size_t)(NS * (D - 2)) * HSZ};
+          BSrcStash<TL> bs{sv + (size_t)(ST.NS * (D - 2)) * ST.T};
           for (int n = w; n < LL.Kblk; n += NW)
             dw_pass<1, TL, false, BSrcStash<TL>>(lds, RS, bs, n, slab + LL.gw_off, slab + LL.gb_off, LL.M, LL.K, first,
                                                  n == 0, lane);
@@ -1408,7 +1409,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
       bwd_dx<NB, TL, PAIR, false>(gacc, (ZLDS_OK && zlds) ? dzw : R, a.packed + LL.pb_off, LL.Mpad8, nullptr, wcol, lane);
       __syncthreads();  // all dW reads of the images are done
       if (D == 2)
-        acc_times_d_to_lds<NB, TL, PAIR>(gacc, R, sv + (size_t)1 * HSZ, sv + (size_t)2 * HSZ, wcol, lane);  // dZ_0
+        acc_times_d_to_lds<NB, TL, PAIR>(gacc, R, sv + (size_t)ST.DA * ST.T, sv + (size_t)ST.DB * ST.T, wcol, lane);  // dZ_0
       else
         acc_to_lds<NB, false>(gacc, R, nullptr, lane);  // R <- dH_{D-2}
       INR_STAMP(13);
@@ -1419,16 +1420,16 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
         for (int m = 0; m < NB; ++m) gacc[m] = zero16();
         if (G2D) image_copy<NB, TL, true>(R, sv_g, wcol, lane);  // dH_l is needed again for the orth Linear
         // dZ_l = dH_l * act'(z_l) (in place), dH_{l-1} = W_l^T dZ_l
-        bwd_dx<NB, TL, PAIR, true>(gacc, R, a.packed + Ll.pb_off, Ll.Mpad8, sv + (size_t)(NS * l + 1) * HSZ, wcol,
+        bwd_dx<NB, TL, PAIR, true>(gacc, R, a.packed + Ll.pb_off, Ll.Mpad8, sv + (size_t)(ST.NS * l + ST.DACT) * ST.T, wcol,
                                    lane);
         INR_STAMP(14 + 4 * l);
         if (dwg) {  // dZ_l (this wave's columns) over the act' slot it was formed from: operand of the batch GEMM
-          image_copy<NB, TL, true>(R, sv + (size_t)(NS * l + 1) * HSZ, wcol, lane);
+          image_copy<NB, TL, true>(R, sv + (size_t)(ST.NS * l + ST.DACT) * ST.T, wcol, lane);
         } else {
           __syncthreads();
           INR_STAMP(15 + 4 * l);
           {
-            BSrcStash<TL> bs{sv + (size_t)(NS * (l - 1)) * HSZ};
+            BSrcStash<TL> bs{sv + (size_t)(ST.NS * (l - 1)) * ST.T};
             for (int n = w; n < Ll.Kblk; n += NW)
               dw_pass<NB, TL, HFULL, BSrcStash<TL>>(lds, RS, bs, n, slab + Ll.gw_off, slab + Ll.gb_off, Ll.M, Ll.K,
                                                     first, n == 0, lane);
@@ -1439,11 +1440,11 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
         if (G2D) {  // second Linear of the layer: dZ_orth = J_orth dH_l, dH_{l-1} += V_l^T dZ_orth, dV_l
           const LayerDesc& Ol = nd.L[nd.orth0 + l];
           image_copy<NB, TL, false>(R, sv_g, wcol, lane);
-          bwd_dx<NB, TL, PAIR, true>(gacc, R, a.packed + Ol.pb_off, Ol.Mpad8, sv + (size_t)(NS * l + 3) * HSZ, wcol,
+          bwd_dx<NB, TL, PAIR, true>(gacc, R, a.packed + Ol.pb_off, Ol.Mpad8, sv + (size_t)(ST.NS * l + ST.DA2) * ST.T, wcol,
                                      lane);
           __syncthreads();
           {
-            BSrcStash<TL> bs{sv + (size_t)(NS * (l - 1)) * HSZ};
+            BSrcStash<TL> bs{sv + (size_t)(ST.NS * (l - 1)) * ST.T};
             for (int n = w; n < Ol.Kblk; n += NW)
               dw_pass<NB, TL, HFULL, BSrcStash<TL>>(lds, RS, bs, n, slab + Ol.gw_off, slab + Ol.gb_off, Ol.M, Ol.K,
                                                     first, n == 0, lane);
@@ -1451,7 +1452,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
           __syncthreads();
         }
         if (l == 1)
-          acc_times_d_to_lds<NB, TL, PAIR>(gacc, R, sv + (size_t)1 * HSZ, sv + (size_t)2 * HSZ, wcol, lane);  // dZ_0
+          acc_times_d_to_lds<NB, TL, PAIR>(gacc, R, sv + (size_t)ST.DA * ST.T, sv + (size_t)ST.DB * ST.T, wcol, lane);  // dZ_0
         else
           acc_to_lds<NB, false>(gacc, R, nullptr, lane);  // R <- dH_{l-1}
         INR_STAMP(17 + 4 * l);
@@ -1460,7 +1461,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
       {
         const LayerDesc& L0 = nd.L[0];
         if (INMODE == IN_GAUSS && dwg) {
-          image_copy<NB, TL, true>(R, sv + (size_t)1 * HSZ, wcol, lane);  // dZ_0 -> stash
+          image_copy<NB, TL, true>(R, sv + (size_t)ST.DACT * ST.T, wcol, lane);  // dZ_0 -> stash
         } else if (INMODE == IN_GAUSS) {
           __syncthreads();  // every wave's dZ_0 is in LDS
           INR_STAMP(40);
@@ -1479,7 +1480,7 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
         __syncthreads();  // images are overwritten by the next tile's forward / dZ_last
         if (G2D) {  // dV_0 from dZ_0,orth = J_orth,0 dH_0 (the accumulators still hold dH_0)
           const LayerDesc& O0 = nd.L[nd.orth0];
-          acc_times_d_to_lds<NB, TL, PAIR>(gacc, R, sv + (size_t)3 * HSZ, sv + (size_t)4 * HSZ, wcol, lane);
+          acc_times_d_to_lds<NB, TL, PAIR>(gacc, R, sv + (size_t)ST.DA2 * ST.T, sv + (size_t)ST.DB2 * ST.T, wcol, lane);
           __syncthreads();
           BSrcX bs{a.x, row0, a.B, O0.K};
           for (int n = w; n < O0.Kblk; n += NW)

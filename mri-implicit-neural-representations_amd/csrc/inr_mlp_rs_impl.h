@@ -41,7 +41,7 @@ constexpr int RS_CHUNK_STEPS = 2 * RS_CP / 4;     // k-steps of 4 per chunk
 constexpr int RS_PF = 8;                          // weight fragments are requested this many k-steps ahead
 constexpr int RS_LR = 8;                          // act' loads of the backward GEMMs in flight (8-byte accesses)
 constexpr int RS_OOB = 0x7ffffff0;                // per-lane offset of a column block that does not exist: loads 0, stores dropped
-constexpr int RS_HSZ = 256 * 128;                 // floats per stashed tensor of a slot
+constexpr MlpStash RS_ST(8, 128, STASH_REAL);     // the stash of a 128-coordinate slot (inr_stash.h)
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -574,7 +574,8 @@ __global__ __launch_bounds__(256) void inr_mlp_rs_kernel(const NetDesc nd, const
   const int avoff = lane * 16 + w * 1024;
   const lfloat* Bl = img + kq * RS_PITCH + jj * 8;            // B layout: row 4 s + kq
   lfloat* Cl = img + (64 * w + 4 * kq) * RS_PITCH + jj * 8;  // C layout: row 64 w + 16 rb + 4 kq + reg
-  const int enc_off = (2 * (D - 1) * RS_HSZ + 4 * 128) * 4;   // bytes from a slot's start to sv_enc
+  constexpr MlpStash ST = RS_ST;  // (int byte offsets below: ST.slot(l, s) written out as (ST.NS * l + s) * ST.T * 4)
+  const int enc_off = (ST.NS * (D - 1) * ST.T + 4 * ST.TL) * 4;   // ST.enc(D) in bytes
   const int nch = E / RS_CP;
   f32x4 Ar[RS_PF];
   {  // the weight stream starts: first k-steps of layer 0
@@ -697,8 +698,8 @@ __global__ __launch_bounds__(256) void inr_mlp_rs_kernel(const NetDesc nd, const
       INR_STAMP(20 + l - 1);
       const LayerDesc& Ll = nd.L[l];
       const int an = l < D - 2 ? nd.L[l + 1].rf_off * 4 : nd.L[D - 2].rb_off * 4;
-      rs_gemm<NCB, 64, RS_KIND_FWD, 2>(acc, Ar, ars, avoff, Ll.rf_off * 4, an, Bl, ad, w, (2 * (l - 1)) * RS_HSZ * 4, 0, dk,
-                                       ((2 * (l - 1) + 1) * RS_HSZ + 64 * w * 128) * 4, bnext);
+      rs_gemm<NCB, 64, RS_KIND_FWD, 2>(acc, Ar, ars, avoff, Ll.rf_off * 4, an, Bl, ad, w, (ST.NS * (l - 1)) * ST.T * 4, 0, dk,
+                                       ((ST.NS * (l - 1) + ST.DACT) * ST.T + 64 * w * 128) * 4, bnext);
       INR_STAMP(1 + l);
       __syncthreads();  // every wave has read h_{l-1}: the owners may overwrite their rows
       if (l == 1) INR_STAMP(61);
@@ -720,8 +721,8 @@ __global__ __launch_bounds__(256) void inr_mlp_rs_kernel(const NetDesc nd, const
     for (int l = D - 2; l >= 1; --l) {
       const LayerDesc& Ll = nd.L[l];
       const int an = (l > 1 ? nd.L[l - 1].rb_off : nd.L[0].rf_off) * 4;  // (last GEMM of the tile: the next tile's layer 0)
-      rs_gemm<NCB, 64, RS_KIND_BWD, 1>(acc, Ar, ars, avoff, Ll.rb_off * 4, an, Bl, ad, w, (2 * l + 1) * RS_HSZ * 4, 0, dk,
-                                       ((2 * (l - 1) + 1) * RS_HSZ + 64 * w * 128) * 4, bnext);
+      rs_gemm<NCB, 64, RS_KIND_BWD, 1>(acc, Ar, ars, avoff, Ll.rb_off * 4, an, Bl, ad, w, (ST.NS * l + ST.DACT) * ST.T * 4, 0, dk,
+                                       ((ST.NS * (l - 1) + ST.DACT) * ST.T + 64 * w * 128) * 4, bnext);
       INR_STAMP(12 + l);
       if (l > 1) {
         __syncthreads();  // every wave has read dZ_l
@@ -742,7 +743,7 @@ __global__ __launch_bounds__(256) void inr_mlp_rs_kernel(const NetDesc nd, const
     // dZ_0 of this lane's rows -> the act' slot of layer 0 (operand of the batch GEMM; there is no dX of the input):
     // from the accumulators, or (D == 2: layer 0 is the last hidden layer) from the lane's rows of the image
     {
-      const int so0 = (1 * RS_HSZ + 64 * w * 128) * 4;
+      const int so0 = ((int)ST.slot(0, ST.DACT) + 64 * w * 128) * 4;
 #pragma unroll
       for (int rb = 0; rb < 4; ++rb)
 #pragma unroll

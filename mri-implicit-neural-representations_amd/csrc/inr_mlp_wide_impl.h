@@ -300,11 +300,13 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
   constexpr bool G2D = HACT == ACT_GABOR2D;  // WIRE2D: second Linear (scale_orth) per layer, L[orth0 + l]
   constexpr bool PAIR = HACT == ACT_GABOR || G2D;
   constexpr bool EAGER = PAIR;  // WIRE / WIRE2D: the image holds activations y, formed once by the row owners
-  constexpr int MT = NB / 2, NG = 2, NW = 4, NS = G2D ? 7 : (PAIR ? 3 : 2);
+  constexpr int MT = NB / 2, NG = 2, NW = 4;
   constexpr int RH = MT * 32;  // image rows per wave of a pair
   constexpr int TL = NG * 32;
   constexpr int RS = NB * 32 * INR_LDS_LD;
-  constexpr int HSZ = NB * 32 * TL;
+  // the stash of a tile (inr_stash.h).  EAGER kernels keep (y, z) in slots H, DA (WIRE2D: and the second Linear's output
+  // in ORTH); DB, DA2 .. Q stay unwritten, DA and DA2 become dZ_l and dZ_orth,l in place
+  constexpr MlpStash ST(NB, TL, G2D ? STASH_GABOR2D : (PAIR ? STASH_GABOR : STASH_REAL));
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int g = w >> 1, hh = w & 1, m0 = MT * hh;
@@ -342,9 +344,9 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
     const bool saving = G2D || (MODE != MODE_FWD) || (a.save != nullptr);  // WIRE2D: the API insists on a buffer
     float* sv = a.save;
     if (saving) sv += (size_t)(a.save_by_block ? blockIdx.x : tile) * nd.save_floats_per_tile;
-    float* sv_last = sv + (size_t)NS * (D - 1) * HSZ;
-    float* sv_enc = sv_last + 4 * TL;
-    float* sv_g = sv_last + 4 * TL;  // WIRE2D (never gauss): copy of a layer's output gradient [NB*32][TL]
+    float* sv_last = sv + ST.last_dact(D);
+    float* sv_enc = sv + ST.enc(D);
+    float* sv_g = sv + ST.grad_copy(D);
     const bool stash = saving && hh == 0;  // one wave of the pair writes the (shared) lazy-activation stash
     int si = 0;  // diagnostic builds: phase stamps 0, 1, 2, ... in program order (tools/stamps.py wire)
     (void)si;
@@ -402,11 +404,11 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
           fwd_layer0_x<MT, NB>(acc2, a.packed + O0.pf_off + aoff, a.x + (size_t)(valid ? crow : 0) * O0.K, valid, O0.K,
                                O0.Kpad8, lane);
           wire2d_epilogue<MT, TL>(acc, acc2, a.packed + L0.pbias_off + m0 * 32, a.packed + O0.pbias_off + m0 * 32, Rown,
-                                  sv + (size_t)m0 * 32 * TL, sv + (size_t)1 * HSZ + (size_t)m0 * 32 * TL,
-                                  sv + (size_t)5 * HSZ + (size_t)m0 * 32 * TL, saving, L0.omega, L0.s0, wcol, lane);
+                                  sv + (size_t)m0 * 32 * TL, sv + ST.slot(0, ST.DA) + (size_t)m0 * 32 * TL,
+                                  sv + ST.slot(0, ST.ORTH) + (size_t)m0 * 32 * TL, saving, L0.omega, L0.s0, wcol, lane);
         } else if (EAGER) {
           wire_epilogue<MT, TL>(acc, a.packed + L0.pbias_off + m0 * 32, Rown, sv + (size_t)m0 * 32 * TL,
-                                sv + (size_t)1 * HSZ + (size_t)m0 * 32 * TL, saving, L0.omega, L0.s0, wcol, lane);
+                                sv + ST.slot(0, ST.DA) + (size_t)m0 * 32 * TL, saving, L0.omega, L0.s0, wcol, lane);
         } else {
           acc_to_lds<MT, true>(acc, Rown, a.packed + L0.pbias_off + m0 * 32, lane);
         }
@@ -419,7 +421,7 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
         f32x16 acc[MT];
 #pragma unroll
         for (int m = 0; m < MT; ++m) acc[m] = zero16();
-        float* sh = sv + (size_t)(NS * (l - 1)) * HSZ;
+        float* sh = sv + ST.slot(l - 1, ST.H);
         f32x16 acc2[G2D ? MT : 1];
         if (EAGER)  // plain GEMM on the activations in the image
           bwd_dx<MT, TL, false, false, NB>(acc, R, a.packed + Ll.pf_off + aoff, NB * 32, nullptr, wcol, lane);
@@ -440,12 +442,12 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
         __syncthreads();  // both waves of the pair have read the image (z_{l-1}, or y_{l-1} in the eager kernels)
         if constexpr (G2D) {
           const LayerDesc& Ol = nd.L[nd.orth0 + l];
-          float* so = sv + (size_t)(NS * l) * HSZ + (size_t)m0 * 32 * TL;
+          float* so = sv + ST.slot(l, ST.H) + (size_t)m0 * 32 * TL;
           wire2d_epilogue<MT, TL>(acc, acc2, a.packed + Ll.pbias_off + m0 * 32, a.packed + Ol.pbias_off + m0 * 32, Rown, so,
-                                  so + HSZ, so + 5 * (size_t)HSZ, saving, Ll.omega, Ll.s0, wcol, lane);
+                                  so + ST.slot(0, ST.DA), so + ST.slot(0, ST.ORTH), saving, Ll.omega, Ll.s0, wcol, lane);
         } else if (EAGER) {
-          float* so = sv + (size_t)(NS * l) * HSZ + (size_t)m0 * 32 * TL;
-          wire_epilogue<MT, TL>(acc, a.packed + Ll.pbias_off + m0 * 32, Rown, so, so + HSZ, saving, Ll.omega, Ll.s0, wcol,
+          float* so = sv + ST.slot(l, ST.H) + (size_t)m0 * 32 * TL;
+          wire_epilogue<MT, TL>(acc, a.packed + Ll.pbias_off + m0 * 32, Rown, so, so + ST.slot(0, ST.DA), saving, Ll.omega, Ll.s0, wcol,
                                 lane);
         } else {
           acc_to_lds<MT, true>(acc, Rown, a.packed + Ll.pbias_off + m0 * 32, lane);
@@ -497,7 +499,7 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
         f32x16 accL[1];
         accL[0] = zero16();
         const ActParams ap{nd.L[D - 2].omega, nd.L[D - 2].s0};
-        float* sh = sv + (size_t)(NS * (D - 2)) * HSZ;
+        float* sh = sv + ST.slot(D - 2, ST.H);
         if (ll_valu) {
 #pragma unroll
           for (int o = 0; o < 4; ++o) accL[0][o] = o4[o];
@@ -561,10 +563,10 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
       __syncthreads();  // every group's dZ_last is in LDS
       {
         if (LL.M <= 4) {  // <= 4 rows: on the vector ALUs (inr_mlp_impl.h), not as a padded 32-row MFMA block
-          dw_rows4_valu<TL, NW>(lds, RS, sv + (size_t)(NS * (D - 2)) * HSZ, NB * 32, LL.M, LL.K, slab + LL.gw_off,
+          dw_rows4_valu<TL, NW>(lds, RS, sv + ST.slot(D - 2, ST.H), NB * 32, LL.M, LL.K, slab + LL.gw_off,
                                 slab + LL.gb_off, first, w, lane);
         } else {
-          BSrcStash<TL> bs{sv + (size_t)(NS * (D - 2)) * HSZ};
+          BSrcStash<TL> bs{sv + ST.slot(D - 2, ST.H)};
           for (int n = w; n < LL.Kblk; n += NW)
             dw_pass<1, TL, false, BSrcStash<TL>>(lds, RS, bs, n, slab + LL.gw_off, slab + LL.gb_off, LL.M, LL.K, first,
                                                  n == 0, lane);
@@ -578,23 +580,23 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
       INR_STAMP(si); ++si;
       __syncthreads();  // all reads of dZ_last are done
       if (D == 2 && (EAGER || G2D))
-        acc_times_jac_to_lds<MT, TL>(gacc, Rown, sv + (size_t)m0 * 32 * TL, sv + (size_t)1 * HSZ + (size_t)m0 * 32 * TL,
+        acc_times_jac_to_lds<MT, TL>(gacc, Rown, sv + (size_t)m0 * 32 * TL, sv + ST.slot(0, ST.DA) + (size_t)m0 * 32 * TL,
                                      nd.L[0].omega, nd.L[0].s0, wcol, lane);  // dZ_0 (own rows)
       else if (D == 2)
-        acc_times_d_to_lds<MT, TL, PAIR>(gacc, Rown, sv + (size_t)1 * HSZ + (size_t)m0 * 32 * TL,
-                                         sv + (size_t)2 * HSZ + (size_t)m0 * 32 * TL, wcol, lane);  // dZ_0 (own rows)
+        acc_times_d_to_lds<MT, TL, PAIR>(gacc, Rown, sv + ST.slot(0, ST.DA) + (size_t)m0 * 32 * TL,
+                                         sv + ST.slot(0, ST.DB) + (size_t)m0 * 32 * TL, wcol, lane);  // dZ_0 (own rows)
       else
         acc_to_lds<MT, false>(gacc, Rown, nullptr, lane);  // dH_{D-2} (own rows)
       for (int l = D - 2; l >= 1; --l) {
         const LayerDesc& Ll = nd.L[l];
         INR_STAMP(si); ++si;
-        __syncthreads();  // dH_l complete
+        __syncthreads();  // dH_l complete.  (In this loop ST.slot(l, s) is written out on ST's constants, as in inr_mlp_impl.h)
         if (G2D) rows_copy<TL, RH, true>(R, sv_g, RH * hh, wcol, lane);  // needed again for the orth Linear
         if (EAGER || G2D)  // own rows: dZ_l = J_l dH_l with J_l from the stashed (y_l, z_l)
-          rows_times<TL, RH, true, 1>(R, sv + (size_t)(NS * l) * HSZ, sv + (size_t)(NS * l + 1) * HSZ, RH * hh, wcol, lane,
+          rows_times<TL, RH, true, 1>(R, sv + (size_t)(ST.NS * l) * ST.T, sv + (size_t)(ST.NS * l + ST.DA) * ST.T, RH * hh, wcol, lane,
                                          Ll.omega, Ll.s0);
         else  // own rows: dZ_l = dH_l * act'
-          rows_times<TL, RH, PAIR>(R, sv + (size_t)(NS * l + 1) * HSZ, sv + (size_t)(NS * l + 2) * HSZ, RH * hh, wcol, lane);
+          rows_times<TL, RH, PAIR>(R, sv + (size_t)(ST.NS * l + ST.DA) * ST.T, sv + (size_t)(ST.NS * l + ST.DB) * ST.T, RH * hh, wcol, lane);
         INR_STAMP(si); ++si;
         __syncthreads();
 #pragma unroll
@@ -602,25 +604,25 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
         bwd_dx<MT, TL, false, false, NB>(gacc, R, a.packed + Ll.pb_off + aoff, Ll.Mpad8, nullptr, wcol, lane);
         INR_STAMP(si); ++si;
         // dW_l is left to the batch GEMM (inr_dw_gemm.hip): own rows of dZ_l over the act' slot they were formed from
-        rows_copy<TL, RH, true>(R, sv + (size_t)(NS * l + 1) * HSZ, RH * hh, wcol, lane);
+        rows_copy<TL, RH, true>(R, sv + (size_t)(ST.NS * l + ST.DACT) * ST.T, RH * hh, wcol, lane);
         INR_STAMP(si); ++si;
         __syncthreads();  // dZ_l has been read by every wave's dX
         if (G2D) {  // second Linear of the layer: dZ_orth = J_orth dH_l, dH_{l-1} += V_l^T dZ_orth, dV_l
           const LayerDesc& Ol = nd.L[nd.orth0 + l];
           rows_copy<TL, RH, false>(R, sv_g, RH * hh, wcol, lane);
-          rows_times<TL, RH, true, 2>(R, sv + (size_t)(NS * l) * HSZ, sv + (size_t)(NS * l + 5) * HSZ, RH * hh, wcol, lane,
+          rows_times<TL, RH, true, 2>(R, sv + (size_t)(ST.NS * l) * ST.T, sv + (size_t)(ST.NS * l + ST.ORTH) * ST.T, RH * hh, wcol, lane,
                                       Ll.omega, Ll.s0);  // dZ_orth = J_orth dH_l from the stashed (y_l, orth_l)
           __syncthreads();
           bwd_dx<MT, TL, false, false, NB>(gacc, R, a.packed + Ol.pb_off + aoff, Ol.Mpad8, nullptr, wcol, lane);
-          rows_copy<TL, RH, true>(R, sv + (size_t)(NS * l + 3) * HSZ, RH * hh, wcol, lane);  // dZ_orth (own rows)
+          rows_copy<TL, RH, true>(R, sv + (size_t)(ST.NS * l + ST.DA2) * ST.T, RH * hh, wcol, lane);  // dZ_orth (own rows)
           __syncthreads();
         }
         if (l == 1 && (EAGER || G2D))
-          acc_times_jac_to_lds<MT, TL>(gacc, Rown, sv + (size_t)m0 * 32 * TL, sv + (size_t)1 * HSZ + (size_t)m0 * 32 * TL,
+          acc_times_jac_to_lds<MT, TL>(gacc, Rown, sv + (size_t)m0 * 32 * TL, sv + ST.slot(0, ST.DA) + (size_t)m0 * 32 * TL,
                                        nd.L[0].omega, nd.L[0].s0, wcol, lane);
         else if (l == 1)
-          acc_times_d_to_lds<MT, TL, PAIR>(gacc, Rown, sv + (size_t)1 * HSZ + (size_t)m0 * 32 * TL,
-                                           sv + (size_t)2 * HSZ + (size_t)m0 * 32 * TL, wcol, lane);
+          acc_times_d_to_lds<MT, TL, PAIR>(gacc, Rown, sv + ST.slot(0, ST.DA) + (size_t)m0 * 32 * TL,
+                                           sv + ST.slot(0, ST.DB) + (size_t)m0 * 32 * TL, wcol, lane);
         else
           acc_to_lds<MT, false>(gacc, Rown, nullptr, lane);
       }
@@ -629,7 +631,7 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
         INR_STAMP(si); ++si;
         __syncthreads();  // dZ_0 complete
         if (INMODE == IN_GAUSS) {
-          rows_copy<TL, RH, true>(R, sv + (size_t)1 * HSZ, RH * hh, wcol, lane);  // dZ_0 (own rows), for the GEMM
+          rows_copy<TL, RH, true>(R, sv + ST.slot(0, ST.DACT), RH * hh, wcol, lane);  // dZ_0 (own rows), for the GEMM
         } else if (EAGER && !G2D && L0.K == 3) {
           // (xs = the pair exchange buffer of the last layer, free here: 64 coordinates x 3, clamped to the batch.  Not in the
           // WIRE2D build: with dH_0 still live in 128 accumulator registers the unrolled pass spills -- 134 -> 528 scratch
@@ -651,7 +653,7 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
           if (G2D) {  // dV_0 from dZ_0,orth = J_orth,0 dH_0 (the accumulators still hold dH_0)
             const LayerDesc& O0 = nd.L[nd.orth0];
             __syncthreads();
-            acc_times_jac_to_lds<MT, TL, true>(gacc, Rown, sv + (size_t)m0 * 32 * TL, sv + (size_t)5 * HSZ + (size_t)m0 * 32 * TL,
+            acc_times_jac_to_lds<MT, TL, true>(gacc, Rown, sv + (size_t)m0 * 32 * TL, sv + ST.slot(0, ST.ORTH) + (size_t)m0 * 32 * TL,
                                                nd.L[0].omega, nd.L[0].s0, wcol, lane);  // J_orth,0 from (y_0, orth_0)
             __syncthreads();
             for (int it = w; it < 2 * O0.Kblk; it += NW) {

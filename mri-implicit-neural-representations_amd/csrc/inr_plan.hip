@@ -8,11 +8,17 @@
 #include <new>
 
 #include "inr_host.h"
+#include "inr_stash.h"
 #include "inr_w2.h"
 
 namespace {
 
 thread_local char g_err[512] = "";
+
+// the stash family (inr_stash.h) of a plain MLP's hidden activation
+inline inr::StashFamily stash_family(int hact) {
+  return hact == ACT_GABOR2D ? inr::STASH_GABOR2D : (hact == ACT_GABOR ? inr::STASH_GABOR : inr::STASH_REAL);
+}
 
 // smallest built block count that holds `need` 32-row blocks (narrower nets run zero-padded), or -1
 inline int pick_nb(int need, std::initializer_list<int> built) {
@@ -107,11 +113,12 @@ static bool dw_gemm_items(const NetDesc& nd, inr::DwGemmArgs* g, inr::SlabSplit*
   const bool g2d = nd.hact == ACT_GABOR2D;
   if (nd.bf16) return false;
   if (nd.mfn_n != 0) {
-    // 512-wide filter networks (inr_mfn_wide_impl.h):  F_t: g_u_t (stash slot 3t+1) x encoder features, t < S;
-    // L_{i-1}: g_l_i (slot 3i) x h_{i-1} (slot 3(i-1)+2), 1 <= i < S.  Their flat ranges interleave with heads and
-    // Gabor centres, so the reduction learns the covered layers as a bit mask.
+    // 512-wide filter networks (inr_mfn_wide_impl.h):  F_t: g_u_t (stash slot LCOS of stage t) x encoder features,
+    // t < S;  L_{i-1}: g_l_i (slot F of stage i) x h_{i-1} (slot HH of stage i-1), 1 <= i < S.  Their flat ranges
+    // interleave with heads and Gabor centres, so the reduction learns the covered layers as a bit mask.
     if (nd.NB != 16) return false;
-    const int S = nd.mfn_stages, n = nd.mfn_n, HSZ = 16 * 32 * 64;
+    const int S = nd.mfn_stages, n = nd.mfn_n;
+    const inr::MfnStash st(nd.NB, 32 * nd.NW);
     if (2 * S - 1 > INR_DWG_MAX_ITEMS) return false;
     g->TL = 64, g->WB = 4;
     g->save_floats_per_tile = nd.save_floats_per_tile, g->slab_floats = nd.slab_floats;
@@ -121,8 +128,8 @@ static bool dw_gemm_items(const NetDesc& nd, inr::DwGemmArgs* g, inr::SlabSplit*
       const int i = t - S + 1, l = t < S ? t : n + 1 + (i - 1);
       const LayerDesc& L = nd.L[l];
       inr::DwGemmItem& it = g->it[k++];
-      it.g_off = t < S ? (3 * t + 1) * HSZ : (3 * i) * HSZ;
-      it.h_off = t < S ? 3 * S * HSZ : (3 * (i - 1) + 2) * HSZ;
+      it.g_off = (int)(t < S ? st.slot(t, st.LCOS) : st.slot(i, st.F));
+      it.h_off = (int)(t < S ? st.enc(S) : st.slot(i - 1, st.HH));
       it.gw_off = L.gw_off, it.gb_off = L.gb_off, it.Mblk = 16, it.Kblk = L.Kblk, it.K = L.K;
       mask |= 1u << l;
     }
@@ -132,16 +139,16 @@ static bool dw_gemm_items(const NetDesc& nd, inr::DwGemmArgs* g, inr::SlabSplit*
   }
   // the plain MLP kernels, fp32: 256-row tensors (one wave per coordinate group) and the two-waves-per-group shapes
   if (!(nd.NB == 8 && !g2d) && nd.NB != 12 && nd.NB != 16) return false;
-  const int TL = 32 * nd.NW, HSZ = nd.NB * 32 * TL, D = nd.D;
-  const int NS = g2d ? 7 : (nd.hact == ACT_GABOR ? 3 : 2);
+  const int TL = 32 * nd.NW, D = nd.D;
+  const inr::MlpStash st(nd.NB, TL, stash_family(nd.hact));
   g->TL = TL;
   g->WB = nd.NB == 12 ? 3 : 4;
   g->save_floats_per_tile = nd.save_floats_per_tile;
   g->slab_floats = nd.slab_floats;
   int k = 0, covered = 0, lo = nd.P, hi = 0;
-  auto add = [&](const LayerDesc& L, int g_off, int h_off) {
+  auto add = [&](const LayerDesc& L, size_t g_off, size_t h_off) {
     inr::DwGemmItem& it = g->it[k++];
-    it.g_off = g_off, it.h_off = h_off;
+    it.g_off = (int)g_off, it.h_off = (int)h_off;
     it.gw_off = L.gw_off, it.gb_off = L.gb_off;
     it.Mblk = nd.NB, it.Kblk = L.Kblk, it.K = L.K;
     covered += L.wn + L.bn;
@@ -149,10 +156,10 @@ static bool dw_gemm_items(const NetDesc& nd, inr::DwGemmArgs* g, inr::SlabSplit*
     hi = std::max(hi, std::max(L.w_off + L.wn, L.b_off + L.bn));
   };
   if (2 * D > INR_DWG_MAX_ITEMS) return false;
-  if (nd.input == IN_GAUSS) add(nd.L[0], 1 * HSZ, NS * (D - 1) * HSZ + 4 * TL);  // dZ_0 x encoder features
+  if (nd.input == IN_GAUSS) add(nd.L[0], st.slot(0, st.DACT), st.enc(D));  // dZ_0 x encoder features
   for (int l = 1; l <= D - 2; ++l) {
-    add(nd.L[l], (NS * l + 1) * HSZ, NS * (l - 1) * HSZ);                  // dZ_l x h_{l-1}
-    if (g2d) add(nd.L[nd.orth0 + l], (NS * l + 3) * HSZ, NS * (l - 1) * HSZ);  // WIRE2D: dZ_orth,l x h_{l-1}
+    add(nd.L[l], st.slot(l, st.DACT), st.slot(l - 1, st.H));                        // dZ_l x h_{l-1}
+    if (g2d) add(nd.L[nd.orth0 + l], st.slot(l, st.DA2), st.slot(l - 1, st.H));  // WIRE2D: dZ_orth,l x h_{l-1}
   }
   if (k == 0 || covered != hi - lo) return false;  // the covered layers must be one contiguous flat range
   g->n_items = k;
@@ -342,9 +349,9 @@ static int create_mfn_plan(const inr_net_desc* d, inr_plan** out) {
   }
   place_slab(nd, pl, nd.D);
   p->packed_floats = place_images(nd, pl, nd.D, true);
-  // stash: [f | l cos u | h] per stage, encoder features, |x|^2 [TL]
   nd.w2_off = nd.w2_bias_off = -1;
-  nd.save_floats_per_tile = 3 * nd.mfn_stages * NB * 32 * TL + nd.L[0].Kblk * 32 * TL + TL;  // Kblk*32 >= 2 E'
+  const inr::MfnStash st(NB, TL);
+  nd.save_floats_per_tile = (int)st.floats_per_tile(nd.mfn_stages, nd.L[0].Kblk * 32);  // Kblk*32 >= 2 E'
   plan_set_dw_route(p);
   *out = p;
   return INR_OK;
@@ -497,10 +504,10 @@ int inr_plan_create(const inr_net_desc* d, inr_plan** out) {
   place_flat(nd, order, nd.ND);
   place_slab(nd, pl, nd.ND);
   int64_t pk = place_images(nd, pl, nd.ND, !nd.bf16);  // bf16 plans keep one image set only: the panel stream (below)
-  const int ns = wire2d ? 7 : (wire ? 3 : 2);
-  nd.save_floats_per_tile = ns * (D - 1) * NB * 32 * TL + 4 * TL +
-                            (d->input == INR_INPUT_GAUSS ? nd.L[0].Kblk * 32 * TL : 0) +
-                            (wire2d ? NB * 32 * TL : 0);  // WIRE2D: copy of a layer's output gradient
+  // (the encoder features and WIRE2D's gradient copy share an offset, inr_stash.h: WIRE behind the gauss encoder was
+  // refused above)
+  const inr::MlpStash st(NB, TL, stash_family(nd.hact));
+  nd.save_floats_per_tile = (int)st.floats_per_tile(D, d->input == INR_INPUT_GAUSS ? nd.L[0].Kblk * 32 : 0);
   nd.w2_off = nd.w2_bias_off = -1;
   // Row-split fused step (inr_mlp_rs_impl.h): SIREN / FFN behind the fused gauss encoder, hidden width 129..256, encoder
   // size a multiple of 32 that leaves room in LDS.  Such plans carry a second set of fragment images (16x16x4 MFMA

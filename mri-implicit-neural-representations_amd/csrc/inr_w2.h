@@ -15,15 +15,10 @@
 // b * w0 / 2 pi, so that an accumulator is the sine's argument in REVOLUTIONS (what v_sin_f32 takes and what the stash
 // keeps); transposed images of layer l hold bf16(W_l^T * w0_{l-1}), the factor of d sin(w0 z) / dz.
 #pragma once
+#include "inr_hd.h"
 
 #define W2_PANEL_BYTES 16384
 #define W2_PANEL_FLOATS 4096
-
-#if defined(__HIPCC__)
-#define INR_HD __host__ __device__
-#else
-#define INR_HD
-#endif
 
 INR_HD inline int w2_np0(int E) { return E / 16; }                  // panels of layer 0 (2E features / 32 per panel)
 INR_HD inline int w2_p_fwd(int l, int E) { return w2_np0(E) + 8 * (l - 1); }          // first panel of hidden layer l
