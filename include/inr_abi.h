@@ -58,7 +58,8 @@ extern "C" {
  *    Kaiser-Bessel gridding around the caller's FFT); inr_ring_scale (rows divided by the divisor of the ring their radius
  *    lies in: ring-normalised fits); inr_row_cdf, its scratch query and inr_sample_epoch (weighted epochs: an integer
  *    CDF of per-row weights and a stratified draw of an epoch's rows from it); inr_plan_step_split (how a row-split
- *    step with gradients is split over two launches and two GEMM parts).
+ *    step with gradients is split over two launches and two GEMM parts); inr_radial_scale (rows divided or multiplied
+ *    by a piecewise-linear radial profile: ring normalisation without jumps at the ring edges).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -606,6 +607,28 @@ int inr_band_stats(const float* dist, const float* gt, const float* pred, const 
  * out overlapping in other than out == in, or overlapping dist. */
 int inr_ring_scale(const float* dist, const float* in, float* out, int64_t n, const float* radii, const float* divisors,
                    int32_t n_rings, void* stream);
+
+/* (v7 addition) Continuous radial scaling of an [n,2] field (no reference counterpart): the
+ * divisor of a ring-normalised fit without its jumps at the ring edges.  dist [n], in [n,2], out [n,2], profile
+ * [n_knots]: device fp32.  The profile is piecewise linear on n_knots uniform knots that start at r_lo and lie
+ * 1 / inv_step apart, and constant beyond both ends.  Per row, every line one correctly rounded fp32 operation, nothing
+ * contracted into an FMA:
+ *   s  = d - r_lo;   u = s * inv_step;   u = u < 0 ? 0 : (u > n_knots-1 ? n_knots-1 : u)
+ *   k  = min((int)u, n_knots - 2);   t = u - (float)k          (exact)
+ *   df = p[k+1] - p[k];   pr = t * df;   q = p[k] + pr
+ *   out = multiply ? in * q : in / q                           (both components; a true division)
+ * A row whose dist is NaN is copied unchanged, bit for bit.  The inverse of a division is the same call on the same
+ * profile with multiply != 0.  inr_mi355x/ringnorm.py::radial_scale_numpy restates this in numpy.
+ * out == in (in place) is allowed.  One launch on `stream`; no scratch, nothing is allocated, nothing is read back,
+ * capturable in a graph.  Every workgroup stages the profile in LDS; four rows per lane, with 16-byte loads and stores
+ * when dist, in and out are 16-byte aligned; nothing is written at or beyond row n.
+ * INR_ERR_INVALID before any launch: a null pointer; n < 1 or n >= 2^31; n_knots outside 2..INR_RADIAL_KNOTS_MAX; a NaN
+ * or infinite r_lo; an inv_step that is not finite and positive; in / out not 8-byte aligned, dist or profile not 4-byte
+ * aligned; out overlapping in other than out == in, or overlapping dist or profile.  The profile's values are device
+ * data and are not checked. */
+#define INR_RADIAL_KNOTS_MAX 4096
+int inr_radial_scale(const float* dist, const float* in, float* out, int64_t n, const float* profile, int32_t n_knots,
+                     float r_lo, float inv_step, int32_t multiply, void* stream);
 
 /* (v7 addition) Software coil compression (no reference counterpart).  A scan is coil-major:
  * data [C][N][2], complex fp32 (re, im) pairs, N = H*W pixels per coil.

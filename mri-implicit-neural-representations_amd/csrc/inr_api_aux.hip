@@ -1,6 +1,6 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network, the off-grid operators apart
 // (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, weighted epochs, grid rows, band
-// statistics, per-ring scaling, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
+// statistics, per-ring and continuous radial scaling, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
 // the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -497,12 +497,27 @@ int inr_band_stats(const float* dist, const float* gt, const float* pred, const 
   return hip_done(e, "inr_band_stats");
 }
 
-// ---- per-ring scaling (inr_ring_scale.hip) ----
+// ---- per-ring scaling (inr_ring_scale.hip) and continuous radial scaling (inr_radial_scale.hip; 4.24) ----
+// the checks the two entries share: the row count, and where dist [n], in [n,2] and out [n,2] lie
+static int scale_rows_count_check(int64_t n, const char* who) {
+  if (n < 1 || n >= (1LL << 31)) return fail(INR_ERR_INVALID, "%s: n = %lld (1 <= n < 2^31 rows per call)", who, (long long)n);
+  return INR_OK;
+}
+
+static int scale_rows_layout_check(const float* dist, const float* in, const float* out, int64_t n, const char* who) {
+  if ((((uintptr_t)in | (uintptr_t)out) & 7u) != 0 || ((uintptr_t)dist & 3u) != 0)
+    return fail(INR_ERR_INVALID, "%s: in / out must be 8-byte aligned and dist 4-byte aligned", who);
+  if (out != in && ranges_overlap(out, n * 8, in, n * 8))
+    return fail(INR_ERR_INVALID, "%s: out overlaps in partially (in place means out == in)", who);
+  if (ranges_overlap(out, n * 8, dist, n * 4)) return fail(INR_ERR_INVALID, "%s: out overlaps dist", who);
+  return INR_OK;
+}
+
 int inr_ring_scale(const float* dist, const float* in, float* out, int64_t n, const float* radii, const float* divisors,
                    int32_t n_rings, void* stream) {
   if (dist == nullptr || in == nullptr || out == nullptr || radii == nullptr || divisors == nullptr)
     return fail(INR_ERR_INVALID, "inr_ring_scale: null argument");
-  if (n < 1 || n >= (1LL << 31)) return fail(INR_ERR_INVALID, "inr_ring_scale: n = %lld (1 <= n < 2^31 rows per call)", (long long)n);
+  if (int rc = scale_rows_count_check(n, "inr_ring_scale")) return rc;
   if (n_rings < 1 || n_rings > INR_BAND_MAX)
     return fail(INR_ERR_INVALID, "inr_ring_scale: n_rings = %d (1..%d)", (int)n_rings, INR_BAND_MAX);
   inr::RingArgs a;
@@ -520,13 +535,30 @@ int inr_ring_scale(const float* dist, const float* in, float* out, int64_t n, co
       return fail(INR_ERR_INVALID, "inr_ring_scale: divisors[%d] = %g (must be finite and not zero)", r, (double)divisors[r]);
     a.divisors[r] = divisors[r];
   }
-  if ((((uintptr_t)in | (uintptr_t)out) & 7u) != 0 || ((uintptr_t)dist & 3u) != 0)
-    return fail(INR_ERR_INVALID, "inr_ring_scale: in / out must be 8-byte aligned and dist 4-byte aligned");
-  if (out != in && ranges_overlap(out, n * 8, in, n * 8))
-    return fail(INR_ERR_INVALID, "inr_ring_scale: out overlaps in partially (in place means out == in)");
-  if (ranges_overlap(out, n * 8, dist, n * 4)) return fail(INR_ERR_INVALID, "inr_ring_scale: out overlaps dist");
+  if (int rc = scale_rows_layout_check(dist, in, out, n, "inr_ring_scale")) return rc;
   hipError_t e = inr::launch_ring_scale(a, dist, in, out, n, (hipStream_t)stream);
   return hip_done(e, "inr_ring_scale");
+}
+
+static_assert(INR_RADIAL_KNOTS_MAX == inr::RADIAL_KNOTS_MAX, "inr_abi.h and inr_aux.h disagree");
+
+int inr_radial_scale(const float* dist, const float* in, float* out, int64_t n, const float* profile, int32_t n_knots,
+                     float r_lo, float inv_step, int32_t multiply, void* stream) {
+  if (dist == nullptr || in == nullptr || out == nullptr || profile == nullptr)
+    return fail(INR_ERR_INVALID, "inr_radial_scale: null argument");
+  if (int rc = scale_rows_count_check(n, "inr_radial_scale")) return rc;
+  if (n_knots < 2 || n_knots > INR_RADIAL_KNOTS_MAX)
+    return fail(INR_ERR_INVALID, "inr_radial_scale: n_knots = %d (2..%d)", (int)n_knots, INR_RADIAL_KNOTS_MAX);
+  if (!std::isfinite(r_lo)) return fail(INR_ERR_INVALID, "inr_radial_scale: r_lo = %g (must be finite)", (double)r_lo);
+  if (!std::isfinite(inv_step) || !(inv_step > 0.f))
+    return fail(INR_ERR_INVALID, "inr_radial_scale: inv_step = %g (must be finite and positive)", (double)inv_step);
+  if (((uintptr_t)profile & 3u) != 0) return fail(INR_ERR_INVALID, "inr_radial_scale: profile must be 4-byte aligned");
+  if (int rc = scale_rows_layout_check(dist, in, out, n, "inr_radial_scale")) return rc;
+  if (ranges_overlap(out, n * 8, profile, (int64_t)n_knots * 4))
+    return fail(INR_ERR_INVALID, "inr_radial_scale: out overlaps profile");
+  hipError_t e = inr::launch_radial_scale(dist, in, out, n, profile, n_knots, r_lo, inv_step, multiply != 0,
+                                          (hipStream_t)stream);
+  return hip_done(e, "inr_radial_scale");
 }
 
 // ---- coil compression (inr_coils.hip) ----

@@ -202,6 +202,12 @@ struct RingArgs {
 hipError_t launch_ring_scale(const RingArgs& a, const float* dist, const float* in, float* out, long long n,
                              hipStream_t st);
 
+// continuous radial scaling (inr_radial_scale.hip): a piecewise-linear profile on n_knots uniform knots
+// from r_lo, 1 / inv_step apart; `profile` is device memory, staged in LDS by every block
+constexpr int RADIAL_KNOTS_MAX = 4096;  // INR_RADIAL_KNOTS_MAX
+hipError_t launch_radial_scale(const float* dist, const float* in, float* out, long long n, const float* profile,
+                               int n_knots, float r_lo, float inv_step, bool multiply, hipStream_t st);
+
 // coil compression (inr_coils.hip): Gram matrix of a coil-major scan, product with a small matrix
 constexpr int COIL_MAX = 32;           // INR_COIL_MAX
 constexpr int COIL_TILE_PIXELS = 128;  // INR_COIL_TILE_PIXELS

@@ -109,8 +109,9 @@ class ResidentFit(ValidationMixin):
         fit runs.  Returns the trainer's own copy of the config."""
         config = set_default_configs(dict(config))
         self.config = config
-        from .ringnorm import parse_ring_normalization
+        from .ringnorm import check_ring_profile, parse_ring_normalization
         self.ring_norm_spec = parse_ring_normalization(config.get("ring_normalization"))  # no default key: absent = off
+        check_ring_profile(config, self.ring_norm_spec)  # config['ring_profile'] (DESIGN.md 4.24) belongs to a ring table
         self.ring_table = None
         if self.ring_norm_spec is not None and not ring_norm_ok:
             raise NotImplementedError(f"config['ring_normalization'] = {config['ring_normalization']!r}: ring-normalised "
@@ -240,6 +241,7 @@ class ResidentFit(ValidationMixin):
         train_dist = self._grid_dist if self.trajectory is None else radius(self.train_coords)
         self.ring_table = make_table(self.ring_norm_spec, self.config, self.train_values, train_dist)
         self.train_values = self.ring_table.scale(train_dist, self.train_values)  # out of place
+        self.ring_table.note_scaled(self.train_values)  # a smooth table's normalized_max
         self._norm_full = self.train_values if self.trajectory is None else \
             self.ring_table.scale(self._grid_dist, self.image_full)
 
