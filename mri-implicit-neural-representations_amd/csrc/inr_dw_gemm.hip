@@ -213,13 +213,8 @@ __global__ __launch_bounds__(256) void dw_gemm_kernel(const DwGemmArgs a) {
 template <int TL, int WBM, int WB>
 static hipError_t launch_tl(const DwGemmArgs& a, dim3 grid, hipStream_t st) {
   constexpr size_t lds_bytes = (size_t)2 * dwg_stage<WBM, WB>() * sizeof(float);  // two stages (4 x 4: 147 KB)
-  auto k = dw_gemm_kernel<TL, WBM, WB>;
-  {
-    hipError_t e = allow_full_lds<dw_gemm_kernel<TL, WBM, WB>>();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, grid, dim3(256), lds_bytes, st, a);
-  return hipGetLastError();
+  static_assert(lds_bytes <= LDS_BYTES_PER_CU, "two stage buffers must fit the CU's LDS");
+  return launch_lds<dw_gemm_kernel<TL, WBM, WB>>(grid, dim3(256), lds_bytes, st, a);
 }
 
 #ifdef INR_STAMPS

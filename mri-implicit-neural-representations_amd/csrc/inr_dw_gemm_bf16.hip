@@ -36,10 +36,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int GB_KS = 64;                 // coordinates per stage
-constexpr int GB_PITCH = 72;              // LDS row pitch in 2-byte elements: 64 coordinates + 16 bytes of padding
-constexpr int GB_TILE = 256 * GB_PITCH;   // one operand tile (elements)
-constexpr int GB_STAGE = 2 * GB_TILE;     // A tile + B tile
+// (GB_KS, GB_PITCH, GB_TILE, GB_STAGE: inr_lds.h, with the kernel's LDS layout DwGemmBf16Lds)
 constexpr int GB_NT = 512;                // threads: eight waves, two per SIMD (staging of one hides under MFMAs of the other)
 
 #ifdef GB_STAMPS  // timing experiment: per-wave cycle sums of the parts of a stage (tools/gemm_stamps.py)
@@ -132,9 +129,10 @@ __device__ __forceinline__ float gauss_phase(const float* x, float b0, float b1,
 template <int TL, bool ENC, bool BIAS, bool LASTROWS>
 __device__ __forceinline__ void dwgb_body(const DwGemmBf16Args& a, const DwGemmBf16Unit& it, int kc, int tiles_per_chunk,
                                           char* lds_raw) {
-  _Float16* lds = reinterpret_cast<_Float16*>(lds_raw);
-  float* xs_lds = reinterpret_cast<float*>(lds_raw + (size_t)2 * GB_STAGE * 2);  // [2 stages][64 coords][3]
-  float* encB_lds = xs_lds + 2 * GB_KS * 3;                                      // [E][3]
+  typedef DwGemmBf16Lds LY;  // where the pieces of `lds_raw` live (inr_lds.h; byte offsets)
+  _Float16* lds = reinterpret_cast<_Float16*>(lds_raw + LY::stages());
+  float* xs_lds = reinterpret_cast<float*>(lds_raw + LY::xs());     // [2 stages][64 coords][3]
+  float* encB_lds = reinterpret_cast<float*>(lds_raw + LY::enc());  // [E][3]
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int half = lane >> 5, li = lane & 31;
   const int wm = w >> 1, wn = w & 1;  // wave tile: rows [64 wm, +64) x columns [128 wn, +128) = 2 x 4 MFMA blocks
@@ -457,12 +455,8 @@ hipError_t launch_dw_gemm_bf16(const DwGemmBf16Args& a_in, hipStream_t st) {
     return hipErrorInvalidValue;
   for (int u = 0; u < a.n_units; ++u)  // the first-layer units come first
     if ((a.unit[u].z_off < 0) != (u < a.n_enc_units)) return hipErrorInvalidValue;
-  const size_t lds_bytes = (size_t)2 * GB_STAGE * 2 + (size_t)(2 * GB_KS * 3 + 3 * a.E) * sizeof(float);
-  if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = allow_full_lds<dw_gemm_bf16_kernel<128>>();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(dw_gemm_bf16_kernel<128>, dim3((unsigned)(a.n_enc_units * a.n_chunks_enc + (a.n_units - a.n_enc_units) * a.n_chunks)), dim3(GB_NT), lds_bytes, st, a);
-  return hipGetLastError();
+  const dim3 grid((unsigned)(a.n_enc_units * a.n_chunks_enc + (a.n_units - a.n_enc_units) * a.n_chunks));
+  return launch_lds<dw_gemm_bf16_kernel<128>>(grid, dim3(GB_NT), DwGemmBf16Lds(a.E).bytes(), st, a);
 }
 
 }  // namespace inr

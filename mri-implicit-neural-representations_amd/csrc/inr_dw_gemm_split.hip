@@ -272,12 +272,9 @@ __global__ __launch_bounds__(256) void dw_gemm_split_kernel(const DwGemmArgs a) 
 template <int SPLITM>
 static hipError_t launch_split(const DwGemmArgs& a, hipStream_t st) {
   constexpr size_t lds_bytes = (size_t)2 * SP_STAGE;
-  static_assert(lds_bytes <= 160 * 1024, "two stage buffers must fit the CU's LDS");
-  hipError_t e = allow_full_lds<dw_gemm_split_kernel<SPLITM>>();
-  if (e != hipSuccess) return e;
+  static_assert(lds_bytes <= LDS_BYTES_PER_CU, "two stage buffers must fit the CU's LDS");
   const dim3 grid((unsigned)(a.n_chunks * a.blocks_per_chunk * SPLITM));
-  hipLaunchKernelGGL(dw_gemm_split_kernel<SPLITM>, grid, dim3(256), lds_bytes, st, a);
-  return hipGetLastError();
+  return launch_lds<dw_gemm_split_kernel<SPLITM>>(grid, dim3(256), lds_bytes, st, a);
 }
 
 // called by launch_dw_gemm with units / blocks_per_chunk / stamps filled in

@@ -344,17 +344,21 @@ template <int NB, int NW, int MODE, bool GABOR>
 __global__ __launch_bounds__(NW * 64) void inr_mfn_kernel(const NetDesc nd, const LossDesc ld, const MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int TL = NW * 32;
-  constexpr int RS = NB * 32 * INR_LDS_LD;   // floats per wave image
-  constexpr int HS = 32 * INR_LDS_LD;        // floats per wave head-gradient image
+  constexpr MfnLds LY(NB, NW);  // where the pieces of `lds` live (inr_lds.h): the encoder matrix is last, no offset needs E
+  // (its offsets as constants, the pointers formed from them below: through calls with the run-time w the kernels
+  // compile to other code)
+  constexpr int RS = LY.image_floats();      // floats per wave image: LY.image(w) = w * RS
+  constexpr int HS = LY.head_grad_floats();  // floats per wave head-gradient image: LY.head_grad(w) = LY.head_grad(0) + w * HS
   constexpr MfnStash ST(NB, TL);             // the stash of a tile (inr_stash.h)
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int half = lane >> 5, col = lane & 31;
   const int wcol = w * 32 + col;
   float* R = lds + w * RS;
-  float* HGall = lds + NW * RS;
+  constexpr int HG0 = LY.head_grad(0), ENC = LY.enc();
+  float* HGall = lds + HG0;
   float* HG = HGall + w * HS;
-  float* encB_lds = HGall + NW * HS;
+  float* encB_lds = lds + ENC;
   const bool xin = nd.input == IN_X;  // x [B,in] in memory instead of the fused gauss encoder
   if (!xin) {
     for (int i = tid; i < 3 * nd.E; i += NW * 64) encB_lds[i] = a.encB[i];
@@ -604,15 +608,8 @@ __global__ __launch_bounds__(NW * 64) void inr_mfn_kernel(const NetDesc nd, cons
 
 template <int NB, int NW, int MODE, bool GABOR>
 inline hipError_t launch_mfn(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st) {
-  const size_t lds_bytes = ((size_t)NW * (NB + 1) * 32 * INR_LDS_LD + (nd.input == IN_GAUSS ? 3 * (size_t)nd.E : 0)) * sizeof(float);
-  auto k = inr_mfn_kernel<NB, NW, MODE, GABOR>;
-  if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-  {
-    hipError_t e = allow_full_lds<inr_mfn_kernel<NB, NW, MODE, GABOR>>();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(NW * 64), lds_bytes, st, nd, ld, a);
-  return hipGetLastError();
+  const MfnLds LY(NB, NW, nd.input == IN_GAUSS, nd.E);
+  return launch_lds<inr_mfn_kernel<NB, NW, MODE, GABOR>>(dim3(grid), dim3(NW * 64), LY.bytes(), st, nd, ld, a);
 }
 
 }  // namespace inr

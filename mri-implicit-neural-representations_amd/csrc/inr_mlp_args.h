@@ -26,8 +26,9 @@ struct MlpArgs {
   int dw_gemm;         // 1: leave dZ_l of the hidden-width layers in the stash for inr_dw_gemm.hip, skip their dW passes
   long long* dbg;      // diagnostic builds (-DINR_STAMPS) only: per-wave phase time stamps
   long long dbg_cap;   // entries behind dbg (a stamp past it is dropped)
-  int ll_lds;          // inr_mlp_kernel: the last layer's live A fragments (rows 0..3) sit in LDS (set by launch_mlp)
-  int dz_lds;    // set by the launcher: dZ_last has its own LDS image (fused step; inr_mlp_impl.h)
+  int ll_lds;          // inr_mlp_kernel: the last layer's live A fragments (rows 0..3) sit in LDS, at MlpLds::last_frag()
+                       // (inr_lds.h); set by launch_mlp where MlpLds::ll_fits()
+  int dz_lds;          // ... and dZ_last has its own LDS images, MlpLds::dz_image(w) (fused step); where MlpLds::dz_fits()
   float* dz_state;     // bf16 plans: the plan's gradient-scale state (inr_w2.h), W2_STATE_FLOATS floats on the device
   int tile0;           // first tile of this launch (tiles [tile0, n_tiles)); accumulate: the workgroups' slabs and loss
   int accumulate;      // words already hold an earlier launch's sums of the same step -- add to them

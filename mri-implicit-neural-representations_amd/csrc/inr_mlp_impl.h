@@ -1182,17 +1182,20 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
   const int lane = tid & 63, w = tid >> 6;
   const int half = lane >> 5, col = lane & 31;
   const int wcol = w * 32 + col;
-  constexpr int RS = NB * 32 * INR_LDS_LD;  // floats per wave image
-  float* R = lds + w * RS;
-  float* encB_lds = lds + NW * RS;  // [E][3] encoder matrix (gauss mode)
+  const MlpLds LY(NB, NW, INMODE == IN_GAUSS, nd.E);  // where the pieces of `lds` live (inr_lds.h)
+  constexpr int RS = lds_image_floats(NB, INR_LDS_LD);  // floats per wave image: image w at w * RS
+  float* R = lds + LY.image(w);
+  float* encB_lds = lds + LY.enc();  // [E][3] encoder matrix (gauss mode)
   // a.ll_lds: the last layer's fragments of output rows 0..3, [NB*4 groups][2 halves][4 rows] float4 + a float4 of zeros
-  float* ll_lds = encB_lds + (INMODE == IN_GAUSS ? ((3 * nd.E + 3) & ~3) : 0);
+  // (the pieces behind the encoder matrix are chained on LY's sizes, not taken through its accessors: as one sum from
+  // `lds` the run-time encoder size lands elsewhere in the address arithmetic and the kernels compile differently)
+  float* ll_lds = encB_lds + LY.EF;  // lds + LY.last_frag()
   // a.dz_lds (fused step, real activations): dZ_last gets its own 8-row image per wave behind the fragments, so that the
   // waves' images still hold h_{D-2} (fwd_last_valu writes it back over z) when the last layer's dW is formed
-  float* dz_all = ll_lds + (NB * 4 * 8 + 1) * 4;  // [NW][8][INR_LDS_LD]
   constexpr bool ZLDS_OK = MODE == MODE_FUSED && !PAIR && (TL == 128 || TL == 64);
   const bool zlds = ZLDS_OK && a.dz_lds != 0;
-  float* dzw = dz_all + w * 8 * INR_LDS_LD;
+  float* dz_all = ll_lds + LY.last_frag_floats();  // lds + LY.dz_image(0): [NW][8][INR_LDS_LD]
+  float* dzw = dz_all + w * LY.dz_image_floats();  // lds + LY.dz_image(w)
   const int D = nd.D;
   if (a.ll_lds && MODE != MODE_BWD) {
     const f32x4* src = reinterpret_cast<const f32x4*>(a.packed + nd.L[D - 1].pf_off);
@@ -1391,7 +1394,8 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
       {
         if (ZLDS_OK && zlds) {
           dw_rows4_valu<TL == 128 ? 128 : 64, NW, ACT_ID>(lds, RS, nullptr, NB * 32, LL.M, LL.K, slab + LL.gw_off,
-                                                          slab + LL.gb_off, first, w, lane, dz_all, 8 * INR_LDS_LD, 0.f);
+                                                          slab + LL.gb_off, first, w, lane, dz_all,
+                                                          LY.dz_image_floats(), 0.f);
         } else if (LL.M <= 4 && (TL == 128 || TL == 64)) {
           dw_rows4_valu<TL == 128 ? 128 : 64, NW>(lds, RS, sv + (size_t)(ST.NS * (D - 2)) * ST.T, NB * 32, LL.M, LL.K,
                                                   slab + LL.gw_off, slab + LL.gb_off, first, w, lane);
@@ -1510,34 +1514,21 @@ __global__ __launch_bounds__(NW * 64) void inr_mlp_kernel(const NetDesc nd, cons
   }
 }
 
-// hipFuncSetAttribute + launch
 template <int NB, int NW, int INMODE, int HACT, int MODE>
 inline hipError_t launch_mlp(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a_in, int grid, hipStream_t st) {
   MlpArgs a = a_in;
-  size_t lds_bytes = ((size_t)NW * NB * 32 * INR_LDS_LD + 3 * (size_t)nd.E) * sizeof(float);
-  auto k = inr_mlp_kernel<NB, NW, INMODE, HACT, MODE>;
-  if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-  // the last layer's fragments in LDS when they fit (4 KB + 16 B behind the 16-byte aligned encoder matrix) and the
-  // layer really has <= 4 output rows
-  const size_t with_ll = ((size_t)NW * NB * 32 * INR_LDS_LD + (INMODE == IN_GAUSS ? ((3 * (size_t)nd.E + 3) & ~(size_t)3) : 0) +
-                          (size_t)(NB * 4 * 8 + 1) * 4) * sizeof(float);
-  a.ll_lds = (MODE != MODE_BWD && nd.L[nd.D - 1].M <= 4 && with_ll <= 160 * 1024) ? 1 : 0;
-  if (a.ll_lds) lds_bytes = with_ll;
+  const MlpLds LY(NB, NW, INMODE == IN_GAUSS, nd.E);
+  // the last layer's fragments in LDS when they fit and the layer really has <= 4 output rows
+  a.ll_lds = (MODE != MODE_BWD && nd.L[nd.D - 1].M <= 4 && LY.ll_fits()) ? 1 : 0;
   // ... and, in the fused step, an 8-row dZ_last image per wave behind them (see the kernel)
-  const size_t with_dz = with_ll + (size_t)NW * 8 * INR_LDS_LD * sizeof(float);
   constexpr bool real_act = HACT != ACT_GABOR && HACT != ACT_GABOR2D;
-  a.dz_lds = (a.ll_lds && MODE == MODE_FUSED && real_act && nd.L[nd.D - 1].Mpad8 <= 8 && with_dz <= 160 * 1024) ? 1 : 0;
-  if (a.dz_lds) lds_bytes = with_dz;
+  a.dz_lds = (a.ll_lds && MODE == MODE_FUSED && real_act && nd.L[nd.D - 1].Mpad8 <= 8 && LY.dz_fits()) ? 1 : 0;
 #ifdef INR_DWG_STATIC  // the kernel has no in-kernel dW passes for layers the GEMM can take: the caller must run it
   if (MODE != MODE_FWD && HACT != ACT_GABOR2D && !a.dw_gemm && (nd.D > 2 || INMODE == IN_GAUSS))
     return hipErrorInvalidValue;
 #endif
-  {
-    hipError_t e = allow_full_lds<inr_mlp_kernel<NB, NW, INMODE, HACT, MODE>>();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(NW * 64), lds_bytes, st, nd, ld, a);
-  return hipGetLastError();
+  return launch_lds<inr_mlp_kernel<NB, NW, INMODE, HACT, MODE>>(dim3(grid), dim3(NW * 64), LY.bytes(a.ll_lds, a.dz_lds), st,
+                                                                 nd, ld, a);
 }
 
 }  // namespace inr

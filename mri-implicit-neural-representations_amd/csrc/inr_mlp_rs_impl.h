@@ -33,8 +33,7 @@
 
 namespace inr {
 
-constexpr int RS_PITCH = 132;                     // floats per feature row of the LDS image: 16 jj x 8 c + 4
-constexpr int RS_IMG_FLOATS = 256 * RS_PITCH;     // 135 168 B
+// (RS_PITCH, RS_IMG_FLOATS: inr_lds.h, with the kernel's LDS layout RsLds)
 constexpr int RS_CP = 32;                         // encoder phases per chunk: 64 feature rows (sines | cosines)
 constexpr int RS_CHUNK_FLOATS = 2 * RS_CP * RS_PITCH;
 constexpr int RS_CHUNK_STEPS = 2 * RS_CP / 4;     // k-steps of 4 per chunk
@@ -548,15 +547,18 @@ __global__ __launch_bounds__(256) void inr_mlp_rs_kernel(const NetDesc nd, const
   INR_RT_STAMP(a.dbg, a.dbg_cap, NW, w, lane, 44);  // (diagnostic builds: kernel entry / exit of each wave, slots 44 / 45)
   const int kq = lane >> 4, jj = lane & 15;
   const int D = nd.D, E = nd.E;
-  lfloat* img = (lfloat*)lds;
-  lfloat* encB_lds = img + RS_IMG_FLOATS;
-  lfloat* wl_lds = encB_lds + ((3 * E + 3) & ~3);  // W_last [4][256], zero padded
-  lfloat* dzl = wl_lds + 1024;                     // dZ_last [4][128]
-  lfloat* red = dzl + 512;                         // [8] sums of dZ_last of waves 0, 1 | [4] loss partials of the waves
-  lfloat* part = red + 32;                         // the waves' partial outputs of the last layer [4][MO][128]
+  const RsLds LY(E);  // where the pieces of `lds` live (inr_lds.h)
+  // (each piece chained on the size of the one before it, not taken through LY's accessors: as one sum from `lds` the
+  // run-time encoder size lands elsewhere in the address arithmetic and the kernel compiles differently)
+  lfloat* img = (lfloat*)lds;                    // lds + LY.image()
+  lfloat* encB_lds = img + RS_IMG_FLOATS;        // lds + LY.enc()
+  lfloat* wl_lds = encB_lds + LY.EF;             // lds + LY.w_last(): W_last [4][256], zero padded
+  lfloat* dzl = wl_lds + LY.w_last_floats();     // lds + LY.dz_last(): dZ_last [4][128]
+  lfloat* red = dzl + LY.dz_last_floats();       // lds + LY.red(): [8] sums of dZ_last of waves 0, 1 | [4] loss partials
+  lfloat* part = red + LY.red_floats();          // lds + LY.part(): the waves' partial outputs of the last layer [4][MO][128]
   const LayerDesc& LL = nd.L[D - 1];
   for (int i = tid; i < 3 * E; i += 256) encB_lds[i] = a.encB[i];
-  for (int i = tid; i < 1024; i += 256) {
+  for (int i = tid; i < LY.w_last_floats(); i += 256) {
     const int o = i >> 8, k = i & 255;
     wl_lds[i] = (o < LL.M && k < LL.K) ? a.params[LL.w_off + o * LL.K + k] : 0.f;
   }
@@ -778,18 +780,9 @@ __global__ __launch_bounds__(256) void inr_mlp_rs_kernel(const NetDesc nd, const
   INR_RT_STAMP(a.dbg, a.dbg_cap, NW, w, lane, 45);
 }
 
-inline size_t rs_lds_bytes(const NetDesc& nd) {
-  return ((size_t)RS_IMG_FLOATS + ((3 * (size_t)nd.E + 3) & ~(size_t)3) + 1024 + 512 + 32 + 2048) * sizeof(float);
-}
-
 template <int NCB, int HACT>
 inline hipError_t launch_mlp_rs(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st) {
-  const size_t lds_bytes = rs_lds_bytes(nd);
-  if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = allow_full_lds<inr_mlp_rs_kernel<NCB, HACT>>();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((inr_mlp_rs_kernel<NCB, HACT>), dim3(grid), dim3(256), lds_bytes, st, nd, ld, a);
-  return hipGetLastError();
+  return launch_lds<inr_mlp_rs_kernel<NCB, HACT>>(dim3(grid), dim3(256), RsLds(nd.E).bytes(), st, nd, ld, a);
 }
 
 }  // namespace inr

@@ -294,16 +294,22 @@ __device__ __forceinline__ void dw_first3_valu(const float* lds_img, int region_
   }
 }
 
+// WIRE / WIRE2D: the image holds activations y, formed once by the row owners; their last layer of <= 4 rows keeps its
+// fragments and the wave pairs' exchange buffer in LDS (MlpWideLds, inr_lds.h)
+template <int HACT>
+constexpr bool WIDE_EAGER = HACT == ACT_GABOR || HACT == ACT_GABOR2D;
+
 template <int NB, int INMODE, int HACT, int MODE>
 __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, const LossDesc ld, const MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr bool G2D = HACT == ACT_GABOR2D;  // WIRE2D: second Linear (scale_orth) per layer, L[orth0 + l]
   constexpr bool PAIR = HACT == ACT_GABOR || G2D;
-  constexpr bool EAGER = PAIR;  // WIRE / WIRE2D: the image holds activations y, formed once by the row owners
+  constexpr bool EAGER = WIDE_EAGER<HACT>;
   constexpr int MT = NB / 2, NG = 2, NW = 4;
   constexpr int RH = MT * 32;  // image rows per wave of a pair
   constexpr int TL = NG * 32;
-  constexpr int RS = NB * 32 * INR_LDS_LD;
+  const MlpWideLds LY(NB, INMODE == IN_GAUSS, nd.E, EAGER);  // where the pieces of `lds` live (inr_lds.h)
+  constexpr int RS = lds_image_floats(NB, INR_LDS_LD);        // floats per group image: image g at g * RS
   // the stash of a tile (inr_stash.h).  EAGER kernels keep (y, z) in slots H, DA (WIRE2D: and the second Linear's output
   // in ORTH); DB, DA2 .. Q stay unwritten, DA and DA2 become dZ_l and dZ_orth,l in place
   constexpr MlpStash ST(NB, TL, G2D ? STASH_GABOR2D : (PAIR ? STASH_GABOR : STASH_REAL));
@@ -312,9 +318,9 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
   const int g = w >> 1, hh = w & 1, m0 = MT * hh;
   const int half = lane >> 5, col = lane & 31;
   const int wcol = g * 32 + col;
-  float* R = lds + g * RS;
+  float* R = lds + LY.image(g);
   float* Rown = R + m0 * 32 * INR_LDS_LD;
-  float* encB_lds = lds + NG * RS;
+  float* encB_lds = lds + LY.enc();
   if (INMODE == IN_GAUSS) {
     for (int i = tid; i < 3 * nd.E; i += NW * 64) encB_lds[i] = a.encB[i];
     __syncthreads();
@@ -322,8 +328,8 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
   const int D = nd.D;
   // EAGER kernels, last layer of <= 4 rows: its fragments (rows 0..3; float4 (s4*2 + half)*4 + row) and the exchange
   // buffer of the wave pairs' partial sums sit behind the encoder matrix (see the last layer below)
-  float* llw = encB_lds + (INMODE == IN_GAUSS ? ((3 * nd.E + 3) & ~3) : 0);
-  float* xw = llw + NB * 4 * 8 * 4;  // [NG][4][32]
+  float* llw = lds + LY.last_frag();
+  float* xw = lds + LY.pair_exchange();  // [NG][4][32]
   const bool ll_valu = EAGER && MODE != MODE_BWD && nd.L[D - 1].M <= 4;
   if (ll_valu) {
     const f32x4* src = reinterpret_cast<const f32x4*>(a.packed + nd.L[D - 1].pf_off);
@@ -688,19 +694,10 @@ __global__ __launch_bounds__(256) void inr_mlp_wide_kernel(const NetDesc nd, con
 
 template <int NB, int INMODE, int HACT, int MODE>
 inline hipError_t launch_mlp_wide(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st) {
-  constexpr bool eager = HACT == ACT_GABOR || HACT == ACT_GABOR2D;  // + last-layer fragments and the pair exchange buffer
-  const size_t lds_bytes = ((size_t)2 * NB * 32 * INR_LDS_LD + (INMODE == IN_GAUSS ? ((3 * (size_t)nd.E + 3) & ~(size_t)3) : 0) +
-                            (eager ? (size_t)NB * 4 * 8 * 4 + 2 * 4 * 32 : 0)) * sizeof(float);
-  auto k = inr_mlp_wide_kernel<NB, INMODE, HACT, MODE>;
-  if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+  const MlpWideLds LY(NB, INMODE == IN_GAUSS, nd.E, WIDE_EAGER<HACT>);
   // backward has no dW passes for the hidden-width layers: the caller runs the batch GEMM on the stash
   if (MODE != MODE_FWD && !a.dw_gemm && (nd.D > 2 || INMODE == IN_GAUSS)) return hipErrorInvalidValue;
-  {
-    hipError_t e = allow_full_lds<inr_mlp_wide_kernel<NB, INMODE, HACT, MODE>>();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds_bytes, st, nd, ld, a);
-  return hipGetLastError();
+  return launch_lds<inr_mlp_wide_kernel<NB, INMODE, HACT, MODE>>(dim3(grid), dim3(256), LY.bytes(), st, nd, ld, a);
 }
 
 }  // namespace inr

@@ -43,8 +43,7 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-constexpr int PN_SLOTS = 8;   // ring slots of W2_PANEL_BYTES
-constexpr int PN_WAVES = 8;   // waves per workgroup; each moves 16 / 8 = 2 of a panel's 1 KB pieces
+// (PN_SLOTS, PN_WAVES: inr_lds.h, with the kernel's LDS layout SirenBf16Lds)
 #ifndef PN_FD_N
 #define PN_FD_N 6
 #endif
@@ -249,7 +248,7 @@ struct SirenTile {
                                        const float* bias, const float* encB, int lane_, int w_, float mult_)
       : nd(nd_), ld(ld_), a(a_), r(r_), bias_lds(bias), encB_lds(encB), lane(lane_), half(lane_ >> 5), col(lane_ & 31),
         wcol((w_ & 3) * 32 + (lane_ & 31)), w(w_), mult(mult_) {
-    bias_voff = PN_SLOTS * W2_PANEL_BYTES + 16 * half;
+    bias_voff = SirenBf16Lds::ring_end() + 16 * half;  // (the table sits at bias() == ring_end())
     asm volatile("" : "+v"(bias_voff));
   }
 
@@ -661,16 +660,18 @@ __global__ __launch_bounds__(512, 2) void inr_siren_bf16_kernel(const NetDesc nd
     a.dbg[((long long)blockIdx.x * NW + w) * 64 + 60] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
   if (MODE != MODE_FWD) asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");
-  float* bias_lds = reinterpret_cast<float*>(lds_raw + PN_SLOTS * W2_PANEL_BYTES);  // [D][256]
-  float* encB_lds = bias_lds + D * 256;                                             // [E][4]
-  float* red_lds = encB_lds + 4 * nd.E;                                             // [2][8]: loss partials, |dZ| maxima
+  const SirenBf16Lds LY(D, nd.E);  // where the pieces of `lds_raw` live (inr_lds.h; byte offsets)
+  float* bias_lds = reinterpret_cast<float*>(lds_raw + LY.bias());  // [D][256]
+  float* encB_lds = reinterpret_cast<float*>(lds_raw + LY.enc());   // [E][4]
+  // (chained on the encoder matrix: taken as lds_raw + LY.red() the backward kernels compile differently)
+  float* red_lds = encB_lds + 4 * nd.E;  // lds_raw + LY.red(): [2][8] loss partials, |dZ| maxima
   const int E = nd.E;
   for (int i = tid; i < D * 256; i += 64 * NW) bias_lds[i] = a.packed[nd.w2_bias_off + i];
   for (int i = tid; i < 4 * E; i += 64 * NW)  // rows padded to 16 bytes: one broadcast read per feature
     encB_lds[i] = (a.encB != nullptr && (i & 3) != 3) ? a.encB[3 * (i >> 2) + (i & 3)] : 0.f;
   PnRing r;
   r.gbase = reinterpret_cast<const char*>(a.packed + nd.w2_off);
-  r.ring = lds_raw;
+  r.ring = lds_raw + LY.ring();
   r.first = MODE == MODE_BWD ? w2_n_fwd(D, E) : 0;
   r.len = MODE == MODE_FUSED ? w2_np(D, E) : (MODE == MODE_FWD ? w2_n_fwd(D, E) : w2_np(D, E) - w2_n_fwd(D, E));
   r.p = 0, r.req = 0, r.req_img = 0;
@@ -745,14 +746,11 @@ __global__ __launch_bounds__(512, 2) void inr_siren_bf16_kernel(const NetDesc nd
 
 template <int MODE, int NH>
 inline hipError_t launch_siren_bf16_nh(const NetDesc& nd, const LossDesc& ld, const MlpArgs& a, int grid, hipStream_t st) {
-  const size_t lds_bytes = (size_t)PN_SLOTS * W2_PANEL_BYTES + ((size_t)nd.D * 256 + 4 * (size_t)nd.E + 2 * PN_WAVES) * sizeof(float);
-  if (lds_bytes > 160 * 1024 || a.save_by_block) return hipErrorInvalidValue;
+  if (a.save_by_block) return hipErrorInvalidValue;
   if (MODE != MODE_FWD && (a.save == nullptr || a.dz_state == nullptr)) return hipErrorInvalidValue;
   if (MODE == MODE_FUSED && a.slabs == nullptr) return hipErrorInvalidValue;
-  hipError_t e = allow_full_lds<inr_siren_bf16_kernel<MODE, NH>>();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((inr_siren_bf16_kernel<MODE, NH>), dim3(grid), dim3(64 * PN_WAVES), lds_bytes, st, nd, ld, a);
-  return hipGetLastError();
+  return launch_lds<inr_siren_bf16_kernel<MODE, NH>>(dim3(grid), dim3(64 * PN_WAVES), SirenBf16Lds(nd.D, nd.E).bytes(), st,
+                                                     nd, ld, a);
 }
 
 // one instantiation per depth (3 .. 8 Linear layers): the layer loops are unrolled at compile time (see "vector loads the
