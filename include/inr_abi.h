@@ -59,7 +59,9 @@ extern "C" {
  *    lies in: ring-normalised fits); inr_row_cdf, its scratch query and inr_sample_epoch (weighted epochs: an integer
  *    CDF of per-row weights and a stratified draw of an epoch's rows from it); inr_plan_step_split (how a row-split
  *    step with gradients is split over two launches and two GEMM parts); inr_radial_scale (rows divided or multiplied
- *    by a piecewise-linear radial profile: ring normalisation without jumps at the ring edges).
+ *    by a piecewise-linear radial profile: ring normalisation without jumps at the ring edges); inr_gain_loss_grad and
+ *    inr_gain_apply (a learned radial gain: the backbone's output times exp(-s) of a second network, the loss on the
+ *    product and its gradients to both in one pass).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -629,6 +631,26 @@ int inr_ring_scale(const float* dist, const float* in, float* out, int64_t n, co
 #define INR_RADIAL_KNOTS_MAX 4096
 int inr_radial_scale(const float* dist, const float* in, float* out, int64_t n, const float* profile, int32_t n_knots,
                      float r_lo, float inv_step, int32_t multiply, void* stream);
+
+/* (v7 additions) A learned radial gain (the reference's ScalerWrapper, models/networks.py:380-405: res = backbone(x) *
+ * exp(-scaler(z))).  y [B,2] is the backbone's output, s [B] the gain network's, both from
+ * inr_forward; the gradients go back through inr_backward of either plan.  Per row, in fp32:
+ *   g = expf(-s);  res_c = y_c g;  (loss, dres) = the pointwise loss of inr_loss_grad on (res, gt);
+ *   dy_c = dres_c g;  ds = -(dres_0 res_0 + dres_1 res_1).
+ * inr_gain_loss_grad: every loss kind inr_loss_grad takes, the same inr_loss_desc (inv_count = 1 / sampled rows, hdr_A).
+ *   Rows with mask[r] == 0 (mask may be NULL: every row) get dy = ds = 0 and stay out of the loss; res (may be NULL) is
+ *   written for every row.  loss_out[0] = the loss; loss_out[1..256] are ordered partial sums (a loss_out buffer holds
+ *   INR_LOSS_WORDS floats), folded by one thread: no atomics, the same inputs give the same bits on every call, and
+ *   res == NULL changes no bit of the other outputs.  y, gt, dy, res 8-byte aligned, s, ds 4-byte aligned; with 16- and
+ *   8-byte alignment two rows move per 16-byte access, and the results do not depend on which path ran.
+ *   Two launches on `stream`.
+ * inr_gain_apply: res = y exp(-s) alone (no-grad sweeps), equal bit for bit to inr_gain_loss_grad's res; res == y is
+ *   allowed.  One launch.
+ * INR_ERR_INVALID before any launch: a null loss, y, s, gt, loss_out, dy, ds (res in inr_gain_apply); B <= 0; an unknown
+ * loss kind; a misaligned pointer. */
+int inr_gain_loss_grad(const inr_loss_desc* loss, const float* y, const float* s, const float* gt, const uint8_t* mask,
+                       int64_t B, float* res, float* loss_out, float* dy, float* ds, void* stream);
+int inr_gain_apply(const float* y, const float* s, int64_t B, float* res, void* stream);
 
 /* (v7 addition) Software coil compression (no reference counterpart).  A scan is coil-major:
  * data [C][N][2], complex fp32 (re, im) pairs, N = H*W pixels per coil.

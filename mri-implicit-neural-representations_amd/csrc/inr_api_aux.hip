@@ -1,6 +1,6 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network, the off-grid operators apart
 // (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, weighted epochs, grid rows, band
-// statistics, per-ring and continuous radial scaling, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
+// statistics, per-ring and continuous radial scaling, learned radial gain, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
 // the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -559,6 +559,33 @@ int inr_radial_scale(const float* dist, const float* in, float* out, int64_t n, 
   hipError_t e = inr::launch_radial_scale(dist, in, out, n, profile, n_knots, r_lo, inv_step, multiply != 0,
                                           (hipStream_t)stream);
   return hip_done(e, "inr_radial_scale");
+}
+
+// ---- learned radial gain (inr_gain.hip) ----
+int inr_gain_loss_grad(const inr_loss_desc* loss, const float* y, const float* s, const float* gt, const uint8_t* mask,
+                       int64_t B, float* res, float* loss_out, float* dy, float* ds, void* stream) {
+  if (loss == nullptr || y == nullptr || s == nullptr || gt == nullptr || loss_out == nullptr || dy == nullptr ||
+      ds == nullptr)
+    return fail(INR_ERR_INVALID, "inr_gain_loss_grad: null argument");
+  if (loss->kind < INR_LOSS_L2_HALF || loss->kind > INR_LOSS_CENTER)
+    return fail(INR_ERR_INVALID, "inr_gain_loss_grad: loss kind %d", loss->kind);
+  if (B <= 0) return fail(INR_ERR_INVALID, "inr_gain_loss_grad: B = %lld", (long long)B);
+  if ((((uintptr_t)y | (uintptr_t)gt | (uintptr_t)dy | (uintptr_t)res) & 7u) != 0 || (((uintptr_t)s | (uintptr_t)ds) & 3u) != 0)
+    return fail(INR_ERR_INVALID, "inr_gain_loss_grad: y / gt / dy / res must be 8-byte aligned ([B,2] rows move as one "
+                "load), s / ds 4-byte aligned");
+  LossDesc ld;
+  to_loss_desc(loss, &ld);
+  hipError_t e = inr::launch_gain_loss_grad(ld, y, s, gt, mask, B, res, loss_out, dy, ds, (hipStream_t)stream);
+  return hip_done(e, "inr_gain_loss_grad");
+}
+
+int inr_gain_apply(const float* y, const float* s, int64_t B, float* res, void* stream) {
+  if (y == nullptr || s == nullptr || res == nullptr) return fail(INR_ERR_INVALID, "inr_gain_apply: null argument");
+  if (B <= 0) return fail(INR_ERR_INVALID, "inr_gain_apply: B = %lld", (long long)B);
+  if ((((uintptr_t)y | (uintptr_t)res) & 7u) != 0 || ((uintptr_t)s & 3u) != 0)
+    return fail(INR_ERR_INVALID, "inr_gain_apply: y / res must be 8-byte aligned, s 4-byte aligned");
+  hipError_t e = inr::launch_gain_apply(y, s, B, res, (hipStream_t)stream);
+  return hip_done(e, "inr_gain_apply");
 }
 
 // ---- coil compression (inr_coils.hip) ----

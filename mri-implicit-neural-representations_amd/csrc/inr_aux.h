@@ -208,6 +208,12 @@ constexpr int RADIAL_KNOTS_MAX = 4096;  // INR_RADIAL_KNOTS_MAX
 hipError_t launch_radial_scale(const float* dist, const float* in, float* out, long long n, const float* profile,
                                int n_knots, float r_lo, float inv_step, bool multiply, hipStream_t st);
 
+// learned radial gain (inr_gain.hip): res = y exp(-s), the loss on res and its gradients to y and s in one
+// pass; the no-grad product alone.  res may be nullptr in the first
+hipError_t launch_gain_loss_grad(const LossDesc& ld, const float* y, const float* s, const float* gt, const uint8_t* mask,
+                                 long long B, float* res, float* loss_out, float* dy, float* ds, hipStream_t st);
+hipError_t launch_gain_apply(const float* y, const float* s, long long B, float* res, hipStream_t st);
+
 // coil compression (inr_coils.hip): Gram matrix of a coil-major scan, product with a small matrix
 constexpr int COIL_MAX = 32;           // INR_COIL_MAX
 constexpr int COIL_TILE_PIXELS = 128;  // INR_COIL_TILE_PIXELS

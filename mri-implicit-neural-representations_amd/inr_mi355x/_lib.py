@@ -132,6 +132,8 @@ SYMBOLS = {
                                  C.c_int32, _P, _P, _P]),
     "inr_ring_scale": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, _P]),
     "inr_radial_scale": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float, C.c_int32, _P]),
+    "inr_gain_loss_grad": (C.c_int, [C.POINTER(LossDesc), _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    "inr_gain_apply": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "inr_coil_gram_scratch": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_coil_gram": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
     "inr_coil_apply": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P]),

@@ -210,6 +210,8 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
         res["ring_normalization"] = tr.ring_table.summary()
     if getattr(tr, "row_sampling", None) is not None:
         res["row_sampling"] = tr._row_sampling_summary()
+    if getattr(tr, "gain_summary", None) is not None:  # a learned-gain fit: exp(-s) over the grid, from evaluate()'s sweep
+        res["gain"] = tr.gain_summary
     if extra:
         res.update(extra)
     if opts.val:

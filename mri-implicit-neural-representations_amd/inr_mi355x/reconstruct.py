@@ -90,6 +90,22 @@ class Reconstructor:
             self.engine = self.model._engine()
             self.enc_B = None
         self.engine.drop_training_state()  # forward only: no gradient buffer, no Adam moments
+        # a learned-gain fit (train_scaling.py): 'net' holds a ScalerWrapper's keys, and the gain network's
+        # size is read from them
+        if not isinstance(checkpoint, dict):
+            checkpoint = torch.load(checkpoint, map_location=self.device)
+        self.scaler = self.scaler_engine = None
+        from .train_scaling import SCALER_NET, has_scaler_keys
+        if has_scaler_keys(checkpoint.get("net", {})):
+            if self.is_mfn:
+                raise NotImplementedError(f"a checkpoint with 'scaler.' keys and model {name!r}")
+            from .networks import FFN
+            weights = [v for k, v in checkpoint["net"].items() if k.startswith("scaler.") and k.endswith(".weight")]
+            with torch.random.fork_rng(devices=[]):
+                self.scaler = FFN(dict(SCALER_NET, network_width=int(weights[0].shape[0]),
+                                       network_depth=len(weights))).to(self.device)
+            self.scaler_engine = self.scaler._engine()
+            self.scaler_engine.drop_training_state()
         self.load(checkpoint)
         self._bufs = None
         self._metric_bufs = {}
@@ -120,7 +136,14 @@ class Reconstructor:
         if checkpoint.get("ring_normalization") is not None:
             from .ringnorm import RingTable
             self.ring_table = RingTable.from_state(checkpoint["ring_normalization"])
-        load_weights(self.model, self.encoder, checkpoint, self._rebind_encoder)
+        if self.scaler is not None:
+            from .train_scaling import split_state
+            back, scal = split_state(checkpoint["net"])
+            load_weights(self.model, self.encoder, {"net": back, "enc": checkpoint.get("enc")}, self._rebind_encoder)
+            load_weights(self.scaler, None, {"net": scal})
+            self.scaler_engine.pack()
+        else:
+            load_weights(self.model, self.encoder, checkpoint, self._rebind_encoder)
         self.engine.pack()
 
     @torch.no_grad()
@@ -150,7 +173,13 @@ class Reconstructor:
         if self.is_mfn:
             o = self.engine.forward(x, self.enc_B, save=False, dist=dist if self.takes_dist else None)
             return o[-1]  # the last head is the reconstruction (train_kspace_multiscale.py:225); single-scale: the only one
-        return self.engine.forward(x, self.enc_B, save=False)
+        y = self.engine.forward(x, self.enc_B, save=False)
+        if self.scaler is not None:  # z = (coil column, the radius the grid kernel made), as gain.gain_inputs
+            z = torch.stack((coords[:, 0], dist), dim=1).contiguous()
+            s = self.scaler_engine.forward(z, None, save=False).view(-1)
+            from .gain import gain_apply
+            return gain_apply(y, s, out=y)
+        return y
 
     @torch.no_grad()
     def render(self, height: Optional[int] = None, width: Optional[int] = None, scale: Optional[float] = None,
@@ -173,7 +202,7 @@ class Reconstructor:
             self._bufs = (torch.empty(chunk, 3, device=self.device), torch.empty(chunk, device=self.device))
         cbuf, dbuf = self._bufs
         out = torch.empty(n, 2, device=self.device)
-        with_dist = self.takes_dist or self.ring_table is not None
+        with_dist = self.takes_dist or self.ring_table is not None or self.scaler is not None
         for lo in range(0, n, chunk):
             hi = min(lo + chunk, n)
             c, d = grid_rows(spec, lo, hi, coords_out=cbuf[:hi - lo], dist_out=dbuf[:hi - lo] if with_dist else None,

@@ -407,6 +407,12 @@ class INRTrainer(ResidentFit):
             raise NotImplementedError("validation with loss 'LSL' (CenterLoss)")
         return self._validated(epoch, self._predict_raw())
 
+    def load_checkpoint(self, ckpt: dict) -> None:
+        if any(k.startswith("scaler.") for k in ckpt.get("net", {})):
+            raise ValueError("the checkpoint has 'scaler.' keys: it is a learned-gain fit's -- load it with "
+                             "ScaledFitTrainer (python -m inr_mi355x.train_scaling)")
+        super().load_checkpoint(ckpt)
+
     def _rebind_encoder(self, enc) -> None:
         super()._rebind_encoder(enc)
         if self.is_mfn:
