@@ -123,8 +123,10 @@ __device__ __forceinline__ int swz(int feat, int col) { return feat * INR_LDS_LD
 //
 // Default: the hardware v_sin_f32 / v_cos_f32 (argument in revolutions) behind a two-constant Cody-Waite
 // reduction by 2 pi: k = rint(x / 2pi), r = x - k 2pi in two FMAs (2pi = hi - lo with hi = float(2pi)), r / 2pi in
-// [-0.5, 0.5].  Measured on MI355X against double precision (tools/probes/sin_probe.hip): max abs error 3.8e-7,
-// mean 5.5e-8 for |x| <= 300 rad -- 7 VALU issue slots + 2 transcendentals, against 26 VALU for the polynomial
+// [-0.5, 0.5].  Against double precision on MI355X: max abs error 3.8e-7, mean 5.5e-8 for |x| <= 300 rad -- held, per
+// call site and element by element, by tests/test_gpu_sincos.py, which holds the same figure up to 8192 rad (the
+// reduction's error does not grow with |x|; largest seen there 2.2e-7 in either range) -- 7 VALU issue slots + 2
+// transcendentals, against 26 VALU for the polynomial
 // form below, and on the fp32 MFMA path every VALU instruction is time added to the matrix pipe's.
 // -DINR_SINCOS_POLY: three-constant Cody-Waite by pi/2 + cephes minimax polynomials on [-pi/4, pi/4] (max abs
 // error 9e-8, mean 1.6e-8): kept for A/B runs (make poly).

@@ -47,8 +47,9 @@ def test_library_is_the_hip_build():
 
 
 def test_encoder_and_sincos_accuracy(dev):
-    """inr_encode_gauss == Positional_Encoder.embedding (networks.py:30-33); also pins the branch-free
-    sincos used inside the fused kernels (abs error vs float64 <= 3e-7 up to |phase| ~ 250 rad)."""
+    """inr_encode_gauss == Positional_Encoder.embedding (networks.py:30-33); also pins the sincos of the STAND-ALONE
+    encoder kernel, which is OCML's sincosf (csrc/inr_encode.hip): abs error vs float64 <= 3e-7 up to |phase| ~ 250 rad.
+    (The branch-free sincos_cw inside the fused kernels is held by tests/test_gpu_sincos.py.)"""
     from inr_mi355x import encode_gauss
     g = torch.Generator().manual_seed(0)
     coords = torch.rand(4096, 3, generator=g) * 2 - 1
@@ -71,6 +72,33 @@ def test_encoder_and_sincos_accuracy(dev):
     err_s = np.abs(out[:, :256].numpy().astype(np.float64) - np.sin(ph.astype(np.float64))).max()
     err_c = np.abs(out[:, 256:].numpy().astype(np.float64) - np.cos(ph.astype(np.float64))).max()
     assert err_s <= 3e-7 and err_c <= 3e-7, (err_s, err_c)
+
+
+def test_logf_encoder_sincos_accuracy(dev):
+    """inr_encode_logf (csrc/inr_encode.hip, OCML sincosf) element by element against float64.  Bands are powers of two,
+    2^0 .. 2^7, so the kernel's phase fl(fl(2 pi) x_a) * band is exact and numpy restates it to the bit; |phase| reaches
+    2^7 * 2 pi = 804 rad.  Bound: the 3e-7 that test_encoder_and_sincos_accuracy holds the gauss encoder's sincosf to.
+    Rows: random coordinates, then 0, +-1, +-1/2 and their fp32 neighbours (phases next to multiples of pi)."""
+    from inr_mi355x.engine import encode_logf
+    g = torch.Generator().manual_seed(3)
+    one, half = np.float32(1), np.float32(0.5)
+    edge = np.array([0.0, 1.0, np.nextafter(one, np.float32(0)), 0.5, np.nextafter(half, np.float32(0)),
+                     np.nextafter(half, one), 0.25, 0.75], dtype=np.float32)
+    edge = np.concatenate([edge, -edge])
+    coords = torch.cat([torch.rand(1000, 3, generator=g) * 2 - 1, torch.from_numpy(np.repeat(edge[:, None], 3, axis=1))])
+    bands = 2.0 ** torch.arange(8, dtype=torch.float32)
+    nb = bands.numel()
+    out = encode_logf(coords.to(dev), bands.reshape(-1, 1).to(dev)).cpu().numpy().astype(np.float64)
+    assert out.shape == (coords.shape[0], 6 * nb)
+    xs = (np.float32(6.283185307179586) * coords.numpy()).astype(np.float32)
+    worst = 0.0
+    for a in range(3):
+        ph = (xs[:, a:a + 1] * bands.numpy()[None, :]).astype(np.float32).astype(np.float64)  # exact: a power of two
+        assert float(np.abs(ph).max()) > 800
+        blk = out[:, a * 2 * nb:(a + 1) * 2 * nb]
+        worst = max(worst, float(np.abs(blk[:, :nb] - np.sin(ph)).max()), float(np.abs(blk[:, nb:] - np.cos(ph)).max()))
+    print("logf sincosf max abs error", worst)
+    assert worst <= 3e-7, worst
 
 
 @pytest.mark.parametrize("name", ["SIREN", "SIREN_tanh", "SIREN_raw3", "FFN"])
