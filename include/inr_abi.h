@@ -61,7 +61,8 @@ extern "C" {
  *    step with gradients is split over two launches and two GEMM parts); inr_radial_scale (rows divided or multiplied
  *    by a piecewise-linear radial profile: ring normalisation without jumps at the ring edges); inr_gain_loss_grad and
  *    inr_gain_apply (a learned radial gain: the backbone's output times exp(-s) of a second network, the loss on the
- *    product and its gradients to both in one pass).
+ *    product and its gradients to both in one pass); inr_focal_loss_grad (the focal frequency loss: rows weighted by
+ *    their own error relative to the batch's largest, in two passes).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -651,6 +652,37 @@ int inr_radial_scale(const float* dist, const float* in, float* out, int64_t n, 
 int inr_gain_loss_grad(const inr_loss_desc* loss, const float* y, const float* s, const float* gt, const uint8_t* mask,
                        int64_t B, float* res, float* loss_out, float* dy, float* ds, void* stream);
 int inr_gain_apply(const float* y, const float* s, int64_t B, float* res, void* stream);
+
+/* inr_focal_loss_grad (below): its descriptor, its block count and where the words of its loss_out buffer lie */
+#define INR_FOCAL_BLOCKS 255
+#define INR_FOCAL_PARTIALS 1   /* loss_out[1 .. 255] */
+#define INR_FOCAL_MAXIMA 256   /* loss_out[256 .. 510] */
+#define INR_FOCAL_NMAX 511     /* the last of the INR_LOSS_WORDS words */
+typedef struct { float alpha; int32_t log_matrix; float loss_weight; float inv_count; } inr_focal_desc;
+/* (v7 addition) The focal frequency loss (the reference's FocalFrequencyLoss.loss_formulation with matrix = None,
+ * metrics/losses.py:57-119; Jiang et al., ICCV 2021) on k-space rows out, gt [B,2]: every sampled
+ * row's squared error weighted by that error relative to the largest of the batch.  Per sampled row r (mask[r] != 0; mask
+ * may be NULL: every row), every fp32 operation rounded on its own (no contraction), inv = inv_count = 1 / sampled rows:
+ *   e_o = out_o - gt_o;  q = e_0 e_0 + e_1 e_1;  m = sqrtf(q) (alpha == 1) or powf(sqrtf(q), alpha);
+ *   n = logf(m + 1.0f) (log_matrix != 0) or m;      n_max = the largest n of the sampled rows (0 when there are none);
+ *   w = 0 if n_max == 0, else fminf(fmaxf(n / n_max, 0), 1)          -- a constant: no gradient flows through w
+ *   loss_out[0] = ((sum_r w_r q_r) inv) loss_weight                  -- the sum in the order given below, then two products
+ *   dout_o = (((loss_weight 2) e_o) w) inv                           -- in this order: the product by 2 is exact, so the
+ *            row that attains n_max (w == 1.0f exactly: both passes evaluate n with one device function) gets
+ *            fl(fl(loss_weight 2 e_o) inv) to the bit.  Rows with mask[r] == 0: dout = 0, not in n_max, not in the sum.
+ * n_max == 0 (prediction equals target on every sampled row, or nothing is sampled) gives loss 0 and dout 0, never NaN.
+ * dout may be NULL (the loss alone); whether it is changes no bit of loss_out.  Non-finite inputs are outside the contract.
+ * Two passes over INR_FOCAL_BLOCKS contiguous ranges of row pairs: the first leaves every range's largest n in
+ * loss_out[INR_FOCAL_MAXIMA + b]; the second folds those words itself (every block, the same fixed tree; block 0 stores
+ * n_max in loss_out[INR_FOCAL_NMAX]), writes dout and leaves its ordered partial sum of w q in loss_out[INR_FOCAL_PARTIALS
+ * + b] (a lane's rows in order, the 256-lane tree); one thread folds the partials in block order.  No atomics: the same
+ * inputs give the same bits on every call.  A max does not depend on order, so n_max is exact.  loss_out holds
+ * INR_LOSS_WORDS floats.  out, gt, dout 8-byte aligned; with 16-byte alignment two rows move per 16-byte access and the
+ * results do not depend on which path ran.  Three launches on `stream`.
+ * INR_ERR_INVALID before any launch, the outputs untouched: a null d, out, gt or loss_out; B <= 0; alpha <= 0 or a
+ * non-finite alpha, loss_weight or inv_count; out, gt or dout not 8-byte aligned. */
+int inr_focal_loss_grad(const inr_focal_desc* d, const float* out, const float* gt, const uint8_t* mask,
+                        int64_t B, float* loss_out, float* dout, void* stream);
 
 /* (v7 addition) Software coil compression (no reference counterpart).  A scan is coil-major:
  * data [C][N][2], complex fp32 (re, im) pairs, N = H*W pixels per coil.

@@ -1,6 +1,6 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network, the off-grid operators apart
 // (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, weighted epochs, grid rows, band
-// statistics, per-ring and continuous radial scaling, learned radial gain, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
+// statistics, per-ring and continuous radial scaling, learned radial gain, focal frequency loss, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
 // the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -586,6 +586,32 @@ int inr_gain_apply(const float* y, const float* s, int64_t B, float* res, void* 
     return fail(INR_ERR_INVALID, "inr_gain_apply: y / res must be 8-byte aligned, s 4-byte aligned");
   hipError_t e = inr::launch_gain_apply(y, s, B, res, (hipStream_t)stream);
   return hip_done(e, "inr_gain_apply");
+}
+
+// ---- focal frequency loss (inr_loss_focal.hip) ----
+static_assert(INR_FOCAL_BLOCKS == inr::FOCAL_BLOCKS && INR_FOCAL_PARTIALS == inr::FOCAL_PARTIALS &&
+                  INR_FOCAL_MAXIMA == inr::FOCAL_MAXIMA && INR_FOCAL_NMAX == inr::FOCAL_NMAX &&
+                  INR_FOCAL_NMAX < INR_LOSS_WORDS, "inr_abi.h and inr_aux.h disagree");
+
+int inr_focal_loss_grad(const inr_focal_desc* d, const float* out, const float* gt, const uint8_t* mask, int64_t B,
+                        float* loss_out, float* dout, void* stream) {
+  if (d == nullptr || out == nullptr || gt == nullptr || loss_out == nullptr)
+    return fail(INR_ERR_INVALID, "inr_focal_loss_grad: null argument");
+  if (B <= 0) return fail(INR_ERR_INVALID, "inr_focal_loss_grad: B = %lld", (long long)B);
+  if (!std::isfinite(d->alpha) || !(d->alpha > 0.f))
+    return fail(INR_ERR_INVALID, "inr_focal_loss_grad: alpha = %g (must be finite and > 0)", (double)d->alpha);
+  if (!std::isfinite(d->loss_weight) || !std::isfinite(d->inv_count))
+    return fail(INR_ERR_INVALID, "inr_focal_loss_grad: loss_weight = %g, inv_count = %g (must be finite)",
+                (double)d->loss_weight, (double)d->inv_count);
+  if ((((uintptr_t)out | (uintptr_t)gt | (uintptr_t)dout) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_focal_loss_grad: out / gt / dout must be 8-byte aligned ([B,2] rows move as one load)");
+  inr::FocalArgs a;
+  a.alpha = d->alpha;
+  a.log_matrix = d->log_matrix != 0;
+  a.loss_weight = d->loss_weight;
+  a.inv_count = d->inv_count;
+  hipError_t e = inr::launch_focal_loss_grad(a, out, gt, mask, B, loss_out, dout, (hipStream_t)stream);
+  return hip_done(e, "inr_focal_loss_grad");
 }
 
 // ---- coil compression (inr_coils.hip) ----

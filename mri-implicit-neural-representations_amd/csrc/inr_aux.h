@@ -214,6 +214,21 @@ hipError_t launch_gain_loss_grad(const LossDesc& ld, const float* y, const float
                                  long long B, float* res, float* loss_out, float* dy, float* ds, hipStream_t st);
 hipError_t launch_gain_apply(const float* y, const float* s, long long B, float* res, hipStream_t st);
 
+// focal frequency loss (inr_loss_focal.hip): the batch's largest weight, then the weighted squared error
+// and its gradient; the words of loss_out are laid out by the FOCAL_* constants.  dout may be nullptr
+constexpr int FOCAL_BLOCKS = 255;    // INR_FOCAL_BLOCKS
+constexpr int FOCAL_PARTIALS = 1;    // INR_FOCAL_PARTIALS
+constexpr int FOCAL_MAXIMA = 256;    // INR_FOCAL_MAXIMA
+constexpr int FOCAL_NMAX = 511;      // INR_FOCAL_NMAX
+struct FocalArgs {
+  float alpha;
+  int log_matrix;
+  float loss_weight;  // as given; the kernel doubles it (exactly) for the gradient
+  float inv_count;
+};
+hipError_t launch_focal_loss_grad(const FocalArgs& a, const float* out, const float* gt, const uint8_t* mask, long long B,
+                                  float* loss_out, float* dout, hipStream_t st);
+
 // coil compression (inr_coils.hip): Gram matrix of a coil-major scan, product with a small matrix
 constexpr int COIL_MAX = 32;           // INR_COIL_MAX
 constexpr int COIL_TILE_PIXELS = 128;  // INR_COIL_TILE_PIXELS

@@ -39,6 +39,13 @@ class LossDesc(C.Structure):
                 ("cons_inv", C.c_float * 4)]
 
 
+class FocalDesc(C.Structure):  # inr_focal_desc
+    _fields_ = [("alpha", C.c_float), ("log_matrix", C.c_int32), ("loss_weight", C.c_float), ("inv_count", C.c_float)]
+
+
+# words of an inr_focal_loss_grad loss_out buffer: INR_FOCAL_BLOCKS / _PARTIALS / _MAXIMA / _NMAX
+FOCAL_BLOCKS, FOCAL_PARTIALS, FOCAL_MAXIMA, FOCAL_NMAX = 255, 1, 256, 511
+
 ABI_VERSION = 7  # INR_ABI_VERSION of include/inr_abi.h
 
 
@@ -134,6 +141,7 @@ SYMBOLS = {
     "inr_radial_scale": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float, C.c_int32, _P]),
     "inr_gain_loss_grad": (C.c_int, [C.POINTER(LossDesc), _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "inr_gain_apply": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "inr_focal_loss_grad": (C.c_int, [C.POINTER(FocalDesc), _P, _P, _P, C.c_int64, _P, _P, _P]),
     "inr_coil_gram_scratch": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_coil_gram": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
     "inr_coil_apply": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P]),

@@ -15,6 +15,9 @@ import torch
 from . import _lib as L
 
 
+LOSS_FOCAL_HOST = -1  # LossSpec.kind of 'FFL': a host-side marker, no value of the C enum inr_loss_kind
+
+
 @dataclass
 class LossSpec:
     """Loss selection of train.py:81-98 (+ loss_opts of the YAML configs)."""
@@ -23,6 +26,7 @@ class LossSpec:
     sigma: float = 2.0
     factor: float = 0.5
     min_sample: int = 3000  # CenterLoss: pairs per radial band (loss_opts['min_sample'], losses.py:150)
+    focal: Optional["FocalSpec"] = None  # 'FFL': kind is LOSS_FOCAL_HOST and this holds the loss (inr_mi355x/focal.py)  # noqa: F821
 
     @staticmethod
     def from_config(config: dict) -> "LossSpec":
@@ -30,11 +34,17 @@ class LossSpec:
         opts = config.get("loss_opts", {}) or {}
         kinds = {"L2": L.LOSS_L2_HALF, "L1": L.LOSS_L1_HALF, "tanh": L.LOSS_TANH, "HDR": L.LOSS_HDR,
                  "LogSpace": L.LOSS_LOGSPACE, "MSLE": L.LOSS_MSLE_HALF, "LSL": L.LOSS_CENTER}  # train.py:82-96 ('LSL'
-        # there is CenterLoss -- its pairs come from torch.randperm on the CPU generator, as here; 'T' / 'FFL' are broken
-        # at their call sites: SURVEY A.4 #7, #8)
+        # there is CenterLoss -- its pairs come from torch.randperm on the CPU generator, as here; 'T' is broken at its
+        # call site: SURVEY A.4 #8)
+        if name == "FFL":
+            # the focal frequency loss needs the batch's largest weight before any row's gradient: no kind of loss_row and
+            # no entry of `kinds` (the C enum is unchanged) but a kernel of its own, inr_focal_loss_grad; the reference's
+            # call site cannot run -- what the loss is here: inr_mi355x/focal.py, DESIGN.md 4.26
+            from .focal import FocalSpec
+            return LossSpec(LOSS_FOCAL_HOST, focal=FocalSpec.from_opts(opts))
         if name not in kinds:
             # the reference evaluates `NotImplementedError` without raising (train.py:98); we raise
-            raise NotImplementedError(f"loss {name!r} has no MI355X kernel (supported: {sorted(kinds)})")
+            raise NotImplementedError(f"loss {name!r} has no MI355X kernel (supported: {sorted(list(kinds) + ['FFL'])})")
         return LossSpec(kinds[name], float(opts.get("hdr_eps", 1e-3)), float(opts.get("hdr_ff_sigma", 2.0)),
                         float(opts.get("hdr_ff_factor", 0.5)), int(opts.get("min_sample", 3000)))
 

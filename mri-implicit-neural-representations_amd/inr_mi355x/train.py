@@ -33,6 +33,7 @@ from . import _lib as L
 from .cli import (add_shuffle_flags, apply_shuffle_flags, cli_data, cli_fit_data, cli_fits,  # noqa: F401
                   expand_data_samples, get_config, parse_cli, run_cli)
 from .engine import LossSpec
+from .focal import focal_loss_grad
 from .mfn import FourierNet, GaborNet, KGaborNet
 from .networks import FFN, SIREN, WIRE, WIRE2D
 from .trainer_base import (ResidentFit, lr_factor, mfn_engine, run_epochs, set_default_configs,  # noqa: F401
@@ -145,6 +146,8 @@ class INRTrainer(ResidentFit):
         self.in_image_space = bool(config.get("transform", False))
         if self.trajectory is not None:
             self._check_trajectory(config, mask, graph_steps, world)
+        if config.get("loss") == "FFL":
+            self._check_focal(config, world)
         if config["model"] not in MODELS:
             raise NotImplementedError(f"model {config['model']!r} has no MI355X kernel yet (have {sorted(MODELS)})")
         if config.get("optimizer", "Adam") != "Adam":
@@ -216,11 +219,11 @@ class INRTrainer(ResidentFit):
         # Single rank only (the gradient all-reduce sits between the two halves) and only where a step is ONE
         # fused launch sequence on resident views.
         self.graph_steps = bool(graph_steps) and world == 1 and not self.use_tv and \
-            self.loss.kind != L.LOSS_CENTER and (self.enc_B is not None or emb == "none") and not self._cplx_reg
+            self.loss.kind != L.LOSS_CENTER and self.loss.focal is None and (self.enc_B is not None or emb == "none") and not self._cplx_reg
         self._graphs = {}
         # plain single-rank steps of the MLP engines go through inr_train_adam_step (INR_ONE_CALL_STEPS=0: two calls)
         self.one_call_steps = (os.environ.get("INR_ONE_CALL_STEPS", "1") != "0" and not self.is_mfn and not self.use_tv
-                               and self.loss.kind != L.LOSS_CENTER and not self._cplx_reg)
+                               and self.loss.kind != L.LOSS_CENTER and self.loss.focal is None and not self._cplx_reg)
         self._finish_init()
 
     @staticmethod
@@ -242,6 +245,24 @@ class INRTrainer(ResidentFit):
             raise NotImplementedError(f"trajectory = {t!r} with graph_steps")
         if world > 1:
             raise NotImplementedError(f"trajectory = {t!r} on more than one rank")
+
+    @staticmethod
+    def _check_focal(config: dict, world: int) -> None:
+        """What a focal-frequency-loss fit (loss 'FFL') cannot be combined with -- refused before anything
+        is allocated.  Masks, shuffled and weighted epochs, trajectories, ring normalisation, virtual coils and the L1 / L2
+        penalties only choose rows or targets or act in the Adam kernel: they all apply."""
+        if world > 1:
+            # n_max is a quantity of the whole batch: a MAX all-reduce would have to sit between the kernel's two passes
+            raise NotImplementedError("loss 'FFL' on more than one rank: the batch's largest weight would need an "
+                                      "all-reduce between the two passes of inr_focal_loss_grad")
+        if config["per_coil"] or config["use_tv"]:
+            raise NotImplementedError("loss 'FFL' with per_coil / use_tv: focal-frequency-loss fits train on plain batches")
+        if config["model"] in MFN_MODELS:
+            raise NotImplementedError(f"loss 'FFL' with model {config['model']!r}: the filter networks' steps are fused "
+                                      "around loss_row; FFL fits run SIREN / FFN / WIRE / WIRE2D through the tier-1 calls")
+        if config.get("precision", "f32") != "f32":
+            raise NotImplementedError(f"loss 'FFL' with precision {config['precision']!r}: the step is the fp32 tier-1 "
+                                      "forward, inr_focal_loss_grad and the fp32 backward")
 
     # ---- one optimizer step on batch `it` of epoch `epoch` --------------------------------------
     def _inputs(self, lo: int, hi: int, train: bool = False):
@@ -327,6 +348,8 @@ class INRTrainer(ResidentFit):
                 loss = self._tv_step(lo, count, A)
             elif self.loss.kind == L.LOSS_CENTER:
                 loss = self._center_step(lo, hi, A)
+            elif self.loss.focal is not None:
+                loss = self._focal_step(lo, hi, count)
             else:
                 loss = self._on_shard(lo, hi, lambda slo, shi: self._fused(
                     slo, shi, count, self._t_mask[slo:shi] if self.mask is not None else None, A))
@@ -369,6 +392,17 @@ class INRTrainer(ResidentFit):
         loss, dout = self.engine.loss_grad(self.loss, out, gt, hi - lo, hdr_A=A)
         for rows_a, rows_b in center_pair_rows(self._t_coords[lo:hi], self.loss.min_sample):
             loss = self.engine.center_pairs_grad(out, gt, dout, rows_a, rows_b, 0.1)
+        self.engine.backward(x, self.enc_B, dout)
+        return loss
+
+    def _focal_step(self, lo: int, hi: int, count: int) -> torch.Tensor:
+        """Focal frequency loss ('FFL'): forward (stashing) -> inr_focal_loss_grad on the batch's sampled
+        rows (two passes: the batch's largest weight, then the weighted error and its gradient) -> backward.  Single
+        rank, whole batches (the weight is relative to the batch's maximum)."""
+        x, gt = self._inputs(lo, hi, True), self._t_image[lo:hi]
+        m = self._t_mask[lo:hi] if self.mask is not None else None
+        out = self.engine.forward(x, self.enc_B, save=True)
+        loss, dout = focal_loss_grad(self.loss.focal, out, gt, count, mask=m, loss_out=self.engine._loss)
         self.engine.backward(x, self.enc_B, dout)
         return loss
 

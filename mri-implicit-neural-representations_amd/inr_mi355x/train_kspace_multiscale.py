@@ -36,6 +36,9 @@ class MultiscaleTrainer(ResidentFit):
                  coil_compression=None):
         config = self._init_fit(config, shape, device, seed, rank, world, process_group,
                                 coil_compression=coil_compression)
+        if config.get("loss") == "FFL":  # before the partition below touches the device
+            raise NotImplementedError("loss 'FFL' (focal frequency loss) in the multiscale loop: its heads train through "
+                                      "the fused multi-head step; FFL fits run in INRTrainer (python -m inr_mi355x.train) only")
         if radii is None:  # train_kspace_multiscale.py:73-84
             from .clustering import partition_and_stats
             C, H, W = int(shape[0]), int(shape[1]), int(shape[2])

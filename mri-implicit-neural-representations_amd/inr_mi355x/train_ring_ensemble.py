@@ -50,6 +50,9 @@ class RingEnsembleTrainer(ResidentFit):
         config = self._init_fit(config, shape, device, seed, rank, world, process_group,
                                 coil_compression=coil_compression)
         self.in_image_space = bool(config.get("transform", False))
+        if config.get("loss") == "FFL":  # its weight is relative to the batch's largest error: a ring sees only its rows
+            raise NotImplementedError("loss 'FFL' (focal frequency loss): ring ensembles train through the fused step; "
+                                      "FFL fits run in INRTrainer (python -m inr_mi355x.train) only")
         if config["model"] not in MODELS or config["model"] in MFN_MODELS:
             raise NotImplementedError(f"ring ensembles are built from SIREN / FFN / WIRE / WIRE2D, not {config['model']!r}")
         C, H, W = int(shape[0]), int(shape[1]), int(shape[2])

@@ -94,6 +94,9 @@ def check_scaled_config(config: dict, world: int = 1, graph_steps: bool = False)
         raise NotImplementedError("per_coil / use_tv: learned-gain fits train on plain batches")
     if config.get("loss") == "LSL":
         raise NotImplementedError("loss 'LSL' (CenterLoss): its random-pair term is not part of inr_gain_loss_grad")
+    if config.get("loss") == "FFL":
+        raise NotImplementedError("loss 'FFL' (focal frequency loss): inr_gain_loss_grad forms its loss through loss_row; "
+                                  "FFL fits run in INRTrainer (python -m inr_mi355x.train) only")
     if config["regularization"]["type"] != "none":
         raise NotImplementedError(f"regularization {config['regularization']['type']!r}: the penalty is over all "
                                   "parameters of both networks and would couple the two engines")

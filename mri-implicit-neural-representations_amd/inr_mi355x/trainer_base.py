@@ -329,6 +329,12 @@ class ResidentFit(ValidationMixin):
     def _row_sampling_summary(self) -> Optional[dict]:
         return self._epoch_buf.summary() if self.row_sampling is not None else None
 
+    @property
+    def focal_summary(self) -> Optional[dict]:
+        """{'alpha', 'log_matrix', 'loss_weight'} of a focal-frequency-loss fit (loss 'FFL'); else None"""
+        focal = getattr(getattr(self, "loss", None), "focal", None)
+        return None if focal is None else focal.summary()
+
     # ---- the loop --------------------------------------------------------------------------------
     def _log_value(self, loss):
         """what fit() keeps of step()'s return value"""
@@ -383,6 +389,12 @@ class ResidentFit(ValidationMixin):
             loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
             for it in range(math.ceil(self.n / self.bs)):  # the grid's batches (the training batches, unless off-grid)
                 lo, hi = it * self.bs, min((it + 1) * self.bs, self.n)
+                if getattr(self.loss, "focal", None) is not None:  # 'FFL': the training step's call, the loss alone
+                    from .focal import focal_loss_grad
+                    loss, _ = focal_loss_grad(self.loss.focal, pred[lo:hi], targets[lo:hi], hi - lo, want_grad=False,
+                                              loss_out=self.engine._loss)
+                    loss_sum += loss * self.scale
+                    continue
                 A = self._batch_hdr_A(it, lo, hi)  # HDR / tanh take the batch's kcoords (train.py:214-217)
                 loss, _ = self.engine.loss_grad(self.loss, pred[lo:hi], targets[lo:hi], hi - lo, hdr_A=A)
                 loss_sum += loss * self.scale
@@ -410,6 +422,8 @@ class ResidentFit(ValidationMixin):
             rec["ring_normalization"] = self.ring_table.summary()
         if self.row_sampling is not None:
             rec["row_sampling"] = self._row_sampling_summary()
+        if self.focal_summary is not None:
+            rec["focal"] = self.focal_summary
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         return rec

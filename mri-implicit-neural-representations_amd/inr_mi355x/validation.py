@@ -189,6 +189,8 @@ class ValidationMixin:
             rec["ring_normalization"] = self.ring_table.summary()
         if getattr(self, "row_sampling", None) is not None:  # trained on weighted epochs
             rec["row_sampling"] = self._row_sampling_summary()
+        if getattr(self, "focal_summary", None) is not None:  # fitted under the focal frequency loss
+            rec["focal"] = self.focal_summary
         if self._band_bounds is not None:
             rec.update(self._last_bands)
         self.val_history.append(rec)
