@@ -62,7 +62,9 @@ extern "C" {
  *    by a piecewise-linear radial profile: ring normalisation without jumps at the ring edges); inr_gain_loss_grad and
  *    inr_gain_apply (a learned radial gain: the backbone's output times exp(-s) of a second network, the loss on the
  *    product and its gradients to both in one pass); inr_focal_loss_grad (the focal frequency loss: rows weighted by
- *    their own error relative to the batch's largest, in two passes).
+ *    their own error relative to the batch's largest, in two passes); inr_mix_loss_grad and inr_mix_apply (a mixture of
+ *    heads: K experts' outputs mixed by a gate network's weights, the loss on the mix plus each expert's own loss on its
+ *    k-space ring, and the gradients to all of them in one pass).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -652,6 +654,48 @@ int inr_radial_scale(const float* dist, const float* in, float* out, int64_t n, 
 int inr_gain_loss_grad(const inr_loss_desc* loss, const float* y, const float* s, const float* gt, const uint8_t* mask,
                        int64_t B, float* res, float* loss_out, float* dy, float* ds, void* stream);
 int inr_gain_apply(const float* y, const float* s, int64_t B, float* res, void* stream);
+
+/* (v7 additions) A mixture of heads (the reference's MultiHeadWrapper with backbone = None, models/networks.py:275-328;
+ * DESIGN.md section 4.27): K expert networks' outputs y_k [B,2] mixed by a gate network's w [B,K], all from inr_forward;
+ * the gradients go back through inr_backward of each plan.  Per row, in fp32, every product and sum rounded on its own
+ * (nothing contracted), d = dist[row], t = gt[row]:
+ *   pre_c = ((w_0 y_0c + w_1 y_1c) + ...) + w_{K-1} y_{K-1,c};   res_c = clamp ? min(max(pre_c, -1), 1) : pre_c
+ *   (L_0, dres) = the pointwise loss of inr_loss_grad on (res, t) with inv_count[0]
+ *   dpre_c = dres_c where clamp == 0 or -1 <= pre_c <= 1 (both ends included), else 0
+ *   dw_k = dpre_0 y_k0 + dpre_1 y_k1
+ *   where radii[k] <= d <= radii[k+1] (both ends included; a row on an edge is in two rings):
+ *       (L_{1+k}, g_k) = the same pointwise loss on (y_k, t) with inv_count[1+k];  elsewhere g_k = 0
+ *   dy_kc = g_kc (detach != 0)  or  g_kc + w_k dpre_c (detach == 0)
+ * inr_mix_loss_grad: the loss kinds inr_gain_loss_grad takes; the descriptor's inv_count is replaced per term by
+ *   mix->inv_count (the mixed term, then rings 0..K-1; 0 for a ring without rows), its hdr_A serves every term.  Rows with
+ *   mask[r] == 0 (mask may be NULL: every row) get dy_k = dw = 0 and stay out of every term; res (may be NULL) is written
+ *   for every row, and whether it is changes no bit of the other outputs.  loss_out[0] = the total, loss_out[1 .. K+1] =
+ *   the mixed term and the K ring terms; loss_out[INR_MIX_PARTIALS + term * INR_MIX_BLOCKS + block] are ordered partial
+ *   sums (a loss_out buffer holds INR_LOSS_WORDS floats), each term folded by one thread in block order and the total
+ *   added in term order: no atomics, the same inputs give the same bits on every call.  mix->y[k] / mix->dy[k], k <
+ *   n_heads: expert k's [B,2] buffers (no stacked copy is made); dw [B,K] is the gate plan's dout.  y_k, dy_k, gt, res
+ *   8-byte aligned, w, dw, dist 4-byte aligned; with 16-byte alignment throughout two rows move per 16-byte access, and
+ *   the results do not depend on which path ran.  Two launches on `stream`.
+ * inr_mix_apply: res alone (no-grad sweeps; reads n_heads, clamp and y of the descriptor), equal bit for bit to
+ *   inr_mix_loss_grad's res; res == y[0] is allowed.  One launch.
+ * INR_ERR_INVALID before any launch, the outputs untouched: a null loss, mix, w, gt, dist, loss_out or dw (mix, w, res in
+ * inr_mix_apply); n_heads outside 2..INR_MIX_MAX_HEADS; a null y[k] or dy[k] below n_heads; radii that do not increase
+ * (or a NaN among them); a negative or non-finite inv_count; B < 1; a loss kind outside inr_gain_loss_grad's; a
+ * misaligned pointer. */
+#define INR_MIX_MAX_HEADS 8
+#define INR_MIX_BLOCKS 55
+#define INR_MIX_PARTIALS 10
+typedef struct {
+  int32_t n_heads, detach, clamp, reserved;
+  float radii[INR_MIX_MAX_HEADS + 1];
+  float inv_count[INR_MIX_MAX_HEADS + 1];
+  const float* y[INR_MIX_MAX_HEADS];
+  float* dy[INR_MIX_MAX_HEADS];
+} inr_mix_desc;
+int inr_mix_loss_grad(const inr_loss_desc* loss, const inr_mix_desc* mix, const float* w, const float* gt,
+                      const float* dist, const uint8_t* mask, int64_t B, float* res, float* loss_out, float* dw,
+                      void* stream);
+int inr_mix_apply(const inr_mix_desc* mix, const float* w, int64_t B, float* res, void* stream);
 
 /* inr_focal_loss_grad (below): its descriptor, its block count and where the words of its loss_out buffer lie */
 #define INR_FOCAL_BLOCKS 255

@@ -1,6 +1,6 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network, the off-grid operators apart
 // (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, weighted epochs, grid rows, band
-// statistics, per-ring and continuous radial scaling, learned radial gain, focal frequency loss, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
+// statistics, per-ring and continuous radial scaling, learned radial gain, mixture of heads, focal frequency loss, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
 // the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -586,6 +586,73 @@ int inr_gain_apply(const float* y, const float* s, int64_t B, float* res, void* 
     return fail(INR_ERR_INVALID, "inr_gain_apply: y / res must be 8-byte aligned, s 4-byte aligned");
   hipError_t e = inr::launch_gain_apply(y, s, B, res, (hipStream_t)stream);
   return hip_done(e, "inr_gain_apply");
+}
+
+// ---- mixture of heads (inr_mix.hip) ----
+static_assert(INR_MIX_MAX_HEADS == inr::MIX_MAX_HEADS && INR_MIX_BLOCKS == inr::MIX_BLOCKS &&
+                  INR_MIX_PARTIALS == inr::MIX_PARTIALS &&
+                  INR_MIX_PARTIALS + (INR_MIX_MAX_HEADS + 1) * INR_MIX_BLOCKS <= INR_LOSS_WORDS,
+              "inr_abi.h and inr_aux.h disagree");
+
+// the descriptor's own fields (n_heads, the y table, and with `grad` the radii, inv_count and the dy table) -> a
+static int mix_desc_check(const inr_mix_desc* mix, bool grad, inr::MixArgs* a, const char* who) {
+  const int K = mix->n_heads;
+  if (K < 2 || K > INR_MIX_MAX_HEADS) return fail(INR_ERR_INVALID, "%s: n_heads = %d (2..%d)", who, K, INR_MIX_MAX_HEADS);
+  memset(a, 0, sizeof(*a));
+  a->n_heads = K;
+  a->detach = mix->detach != 0;
+  a->clamp = mix->clamp != 0;
+  for (int k = 0; k < K; ++k) {
+    if (mix->y[k] == nullptr || (grad && mix->dy[k] == nullptr)) return fail(INR_ERR_INVALID, "%s: null table entry %d", who, k);
+    if (((uintptr_t)mix->y[k] & 7u) != 0 || (grad && ((uintptr_t)mix->dy[k] & 7u) != 0))
+      return fail(INR_ERR_INVALID, "%s: y[%d] / dy[%d] must be 8-byte aligned ([B,2] rows move as one load)", who, k, k);
+    a->y[k] = mix->y[k];
+    a->dy[k] = grad ? mix->dy[k] : nullptr;
+  }
+  if (!grad) return INR_OK;
+  for (int k = 0; k <= K; ++k) {
+    if (!(mix->radii[k] == mix->radii[k])) return fail(INR_ERR_INVALID, "%s: radii[%d] is NaN", who, k);
+    if (k > 0 && !(mix->radii[k] > mix->radii[k - 1]))
+      return fail(INR_ERR_INVALID, "%s: radii[%d] = %g is not above radii[%d] = %g (radii must increase)", who, k,
+                  (double)mix->radii[k], k - 1, (double)mix->radii[k - 1]);
+    if (!std::isfinite(mix->inv_count[k]) || mix->inv_count[k] < 0.f)
+      return fail(INR_ERR_INVALID, "%s: inv_count[%d] = %g (must be finite and not negative)", who, k,
+                  (double)mix->inv_count[k]);
+    a->radii[k] = mix->radii[k];
+    a->inv_count[k] = mix->inv_count[k];
+  }
+  return INR_OK;
+}
+
+int inr_mix_loss_grad(const inr_loss_desc* loss, const inr_mix_desc* mix, const float* w, const float* gt,
+                      const float* dist, const uint8_t* mask, int64_t B, float* res, float* loss_out, float* dw,
+                      void* stream) {
+  if (loss == nullptr || mix == nullptr || w == nullptr || gt == nullptr || dist == nullptr || loss_out == nullptr ||
+      dw == nullptr)
+    return fail(INR_ERR_INVALID, "inr_mix_loss_grad: null argument");
+  if (loss->kind < INR_LOSS_L2_HALF || loss->kind > INR_LOSS_CENTER)
+    return fail(INR_ERR_INVALID, "inr_mix_loss_grad: loss kind %d", loss->kind);
+  if (B <= 0) return fail(INR_ERR_INVALID, "inr_mix_loss_grad: B = %lld", (long long)B);
+  inr::MixArgs a;
+  if (int rc = mix_desc_check(mix, true, &a, "inr_mix_loss_grad")) return rc;
+  if ((((uintptr_t)gt | (uintptr_t)res) & 7u) != 0 || (((uintptr_t)w | (uintptr_t)dw | (uintptr_t)dist) & 3u) != 0)
+    return fail(INR_ERR_INVALID, "inr_mix_loss_grad: gt / res must be 8-byte aligned ([B,2] rows move as one load), "
+                "w / dw / dist 4-byte aligned");
+  LossDesc ld;
+  to_loss_desc(loss, &ld);
+  hipError_t e = inr::launch_mix_loss_grad(ld, a, w, gt, dist, mask, B, res, loss_out, dw, (hipStream_t)stream);
+  return hip_done(e, "inr_mix_loss_grad");
+}
+
+int inr_mix_apply(const inr_mix_desc* mix, const float* w, int64_t B, float* res, void* stream) {
+  if (mix == nullptr || w == nullptr || res == nullptr) return fail(INR_ERR_INVALID, "inr_mix_apply: null argument");
+  if (B <= 0) return fail(INR_ERR_INVALID, "inr_mix_apply: B = %lld", (long long)B);
+  inr::MixArgs a;
+  if (int rc = mix_desc_check(mix, false, &a, "inr_mix_apply")) return rc;
+  if (((uintptr_t)res & 7u) != 0 || ((uintptr_t)w & 3u) != 0)
+    return fail(INR_ERR_INVALID, "inr_mix_apply: res must be 8-byte aligned, w 4-byte aligned");
+  hipError_t e = inr::launch_mix_apply(a, w, B, res, (hipStream_t)stream);
+  return hip_done(e, "inr_mix_apply");
 }
 
 // ---- focal frequency loss (inr_loss_focal.hip) ----

@@ -214,6 +214,23 @@ hipError_t launch_gain_loss_grad(const LossDesc& ld, const float* y, const float
                                  long long B, float* res, float* loss_out, float* dy, float* ds, hipStream_t st);
 hipError_t launch_gain_apply(const float* y, const float* s, long long B, float* res, hipStream_t st);
 
+// mixture of heads (inr_mix.hip): res = clamp(sum_k w_k y_k), the loss on res plus expert k's own loss on
+// ring k, and the gradients to every y_k and to w in one pass; the no-grad mix alone.  The tables travel as kernel
+// arguments; y[k] / dy[k] are expert k's [B,2] buffers (dy unused by the second).  res may be nullptr in the first
+constexpr int MIX_MAX_HEADS = 8;  // INR_MIX_MAX_HEADS
+constexpr int MIX_BLOCKS = 55;    // INR_MIX_BLOCKS: 9 terms x 55 ordered partials behind the 10 result words
+constexpr int MIX_PARTIALS = 10;  // INR_MIX_PARTIALS
+struct MixArgs {
+  int n_heads, detach, clamp;
+  float radii[MIX_MAX_HEADS + 1];      // ring k: radii[k] <= dist <= radii[k+1]
+  float inv_count[MIX_MAX_HEADS + 1];  // the mixed term's 1 / rows, then each ring's (0: no row)
+  const float* y[MIX_MAX_HEADS];
+  float* dy[MIX_MAX_HEADS];
+};
+hipError_t launch_mix_loss_grad(const LossDesc& ld, const MixArgs& a, const float* w, const float* gt, const float* dist,
+                                const uint8_t* mask, long long B, float* res, float* loss_out, float* dw, hipStream_t st);
+hipError_t launch_mix_apply(const MixArgs& a, const float* w, long long B, float* res, hipStream_t st);
+
 // focal frequency loss (inr_loss_focal.hip): the batch's largest weight, then the weighted squared error
 // and its gradient; the words of loss_out are laid out by the FOCAL_* constants.  dout may be nullptr
 constexpr int FOCAL_BLOCKS = 255;    // INR_FOCAL_BLOCKS

@@ -46,6 +46,15 @@ class FocalDesc(C.Structure):  # inr_focal_desc
 # words of an inr_focal_loss_grad loss_out buffer: INR_FOCAL_BLOCKS / _PARTIALS / _MAXIMA / _NMAX
 FOCAL_BLOCKS, FOCAL_PARTIALS, FOCAL_MAXIMA, FOCAL_NMAX = 255, 1, 256, 511
 
+MIX_MAX_HEADS, MIX_BLOCKS, MIX_PARTIALS = 8, 55, 10  # INR_MIX_MAX_HEADS / _BLOCKS / _PARTIALS
+
+
+class MixDesc(C.Structure):  # inr_mix_desc
+    _fields_ = [("n_heads", C.c_int32), ("detach", C.c_int32), ("clamp", C.c_int32), ("reserved", C.c_int32),
+                ("radii", C.c_float * (MIX_MAX_HEADS + 1)), ("inv_count", C.c_float * (MIX_MAX_HEADS + 1)),
+                ("y", C.c_void_p * MIX_MAX_HEADS), ("dy", C.c_void_p * MIX_MAX_HEADS)]
+
+
 ABI_VERSION = 7  # INR_ABI_VERSION of include/inr_abi.h
 
 
@@ -141,6 +150,8 @@ SYMBOLS = {
     "inr_radial_scale": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float, C.c_int32, _P]),
     "inr_gain_loss_grad": (C.c_int, [C.POINTER(LossDesc), _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "inr_gain_apply": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "inr_mix_loss_grad": (C.c_int, [C.POINTER(LossDesc), C.POINTER(MixDesc), _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "inr_mix_apply": (C.c_int, [C.POINTER(MixDesc), _P, C.c_int64, _P, _P]),
     "inr_focal_loss_grad": (C.c_int, [C.POINTER(FocalDesc), _P, _P, _P, C.c_int64, _P, _P, _P]),
     "inr_coil_gram_scratch": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_coil_gram": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),

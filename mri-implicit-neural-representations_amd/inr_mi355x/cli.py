@@ -212,6 +212,8 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
         res["row_sampling"] = tr._row_sampling_summary()
     if getattr(tr, "gain_summary", None) is not None:  # a learned-gain fit: exp(-s) over the grid, from evaluate()'s sweep
         res["gain"] = tr.gain_summary
+    if getattr(tr, "mixture_summary", None) is not None:  # a mixture-of-heads fit: the gate's weights over the grid
+        res["mixture"] = tr.mixture_summary
     if getattr(tr, "focal_summary", None) is not None:  # loss 'FFL': the three settings the fit ran under
         res["focal"] = tr.focal_summary
     if extra:

@@ -106,6 +106,29 @@ class Reconstructor:
                                        network_depth=len(weights))).to(self.device)
             self.scaler_engine = self.scaler._engine()
             self.scaler_engine.drop_training_state()
+        # a mixture-of-heads fit (train_multihead.py): 'net' holds 'heads.{k}.' and 'weighted_avg.' keys;
+        # self.model / self.engine above are expert 0, the others and the gate (sized from its weights) follow
+        self.experts = self.expert_engines = self.gate = self.gate_engine = None
+        self.mix_clamp = True
+        from .train_multihead import GATE_NET, GATE_PREFIX, has_head_keys, split_state as split_heads
+        if has_head_keys(checkpoint.get("net", {})):
+            if self.is_mfn:
+                raise NotImplementedError(f"a checkpoint with 'heads.' keys and model {name!r}")
+            from .networks import FFN
+            heads, gate = split_heads(checkpoint["net"])
+            weights = [v for k, v in gate.items() if k.endswith(".weight")]
+            with torch.random.fork_rng(devices=[]):
+                self.experts = [self.model] + [MODELS[name](config["net"]).to(self.device) for _ in heads[1:]]
+                self.gate = FFN(dict(GATE_NET, network_output_size=len(heads), network_width=int(weights[0].shape[0]),
+                                     network_depth=len(weights))).to(self.device)
+            self.expert_engines = [self.engine]
+            for m in self.experts[1:]:
+                eng = m.fused_engine(config["encoder"]["embedding_size"]) if emb == "gauss" else m._engine()
+                eng.drop_training_state()
+                self.expert_engines.append(eng)
+            self.gate_engine = self.gate._engine()
+            self.gate_engine.drop_training_state()
+            self.mix_clamp = bool((checkpoint.get("mixture") or {}).get("clamp", True))
         self.load(checkpoint)
         self._bufs = None
         self._metric_bufs = {}
@@ -136,7 +159,18 @@ class Reconstructor:
         if checkpoint.get("ring_normalization") is not None:
             from .ringnorm import RingTable
             self.ring_table = RingTable.from_state(checkpoint["ring_normalization"])
-        if self.scaler is not None:
+        if self.experts is not None:
+            from .train_multihead import split_state as split_heads
+            heads, gate = split_heads(checkpoint["net"])
+            if len(heads) != len(self.experts):
+                raise ValueError(f"the checkpoint has {len(heads)} heads, this Reconstructor {len(self.experts)}")
+            for k, (m, eng) in enumerate(zip(self.experts, self.expert_engines)):
+                load_weights(m, self.encoder if k == 0 else None,
+                             {"net": heads[k], "enc": checkpoint.get("enc") if k == 0 else None}, self._rebind_encoder)
+                eng.pack()
+            load_weights(self.gate, None, {"net": gate})
+            self.gate_engine.pack()
+        elif self.scaler is not None:
             from .train_scaling import split_state
             back, scal = split_state(checkpoint["net"])
             load_weights(self.model, self.encoder, {"net": back, "enc": checkpoint.get("enc")}, self._rebind_encoder)
@@ -173,6 +207,11 @@ class Reconstructor:
         if self.is_mfn:
             o = self.engine.forward(x, self.enc_B, save=False, dist=dist if self.takes_dist else None)
             return o[-1]  # the last head is the reconstruction (train_kspace_multiscale.py:225); single-scale: the only one
+        if self.experts is not None:  # z as below; the trainers' mix_apply over the K experts' rows
+            ys = [eng.forward(x, self.enc_B, save=False) for eng in self.expert_engines]
+            z = torch.stack((coords[:, 0], dist), dim=1).contiguous()
+            from .mix import mix_apply
+            return mix_apply(ys, self.gate_engine.forward(z, None, save=False), clamp=self.mix_clamp, out=ys[0])
         y = self.engine.forward(x, self.enc_B, save=False)
         if self.scaler is not None:  # z = (coil column, the radius the grid kernel made), as gain.gain_inputs
             z = torch.stack((coords[:, 0], dist), dim=1).contiguous()
@@ -202,7 +241,8 @@ class Reconstructor:
             self._bufs = (torch.empty(chunk, 3, device=self.device), torch.empty(chunk, device=self.device))
         cbuf, dbuf = self._bufs
         out = torch.empty(n, 2, device=self.device)
-        with_dist = self.takes_dist or self.ring_table is not None or self.scaler is not None
+        with_dist = self.takes_dist or self.ring_table is not None or self.scaler is not None or \
+            self.experts is not None
         for lo in range(0, n, chunk):
             hi = min(lo + chunk, n)
             c, d = grid_rows(spec, lo, hi, coords_out=cbuf[:hi - lo], dist_out=dbuf[:hi - lo] if with_dist else None,
