@@ -64,7 +64,9 @@ extern "C" {
  *    product and its gradients to both in one pass); inr_focal_loss_grad (the focal frequency loss: rows weighted by
  *    their own error relative to the batch's largest, in two passes); inr_mix_loss_grad and inr_mix_apply (a mixture of
  *    heads: K experts' outputs mixed by a gate network's weights, the loss on the mix plus each expert's own loss on its
- *    k-space ring, and the gradients to all of them in one pass).
+ *    k-space ring, and the gradients to all of them in one pass); inr_sense_apply and inr_sense_grad (SENSE-model fits:
+ *    coil images as the product of an image network and a sensitivity network in image space, written where ifftshift
+ *    puts them, and the adjoint of that product).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -696,6 +698,30 @@ int inr_mix_loss_grad(const inr_loss_desc* loss, const inr_mix_desc* mix, const 
                       const float* dist, const uint8_t* mask, int64_t B, float* res, float* loss_out, float* dw,
                       void* stream);
 int inr_mix_apply(const inr_mix_desc* mix, const float* w, int64_t B, float* res, void* stream);
+
+/* (v7 additions) SENSE-model fits (no reference counterpart): two networks in IMAGE space, fitted to
+ * k-space data.  img [H*W,2] is the image network's output (one complex number per pixel), sens [G*H*W,2] the
+ * sensitivity network's for G coils, both from inr_forward; x / gx [G,H,W,2] the coil images and the gradient that came
+ * back to them (through the caller's FFT and inr_loss_grad); dimg / dsens like img / sens, for inr_backward of either
+ * plan.  A (re, im) pair is one complex number.  Per pixel p = (y, x) and coil g, in fp32, every product and sum rounded
+ * on its own (nothing contracted), in this order:
+ *   inr_sense_apply:  re = sr*ir - si*ii;  im = sr*ii + si*ir;  x[g][q] = (scale*re, scale*im)
+ *   inr_sense_grad:   (gr, gi) = gx[g][q];  ur = scale*gr;  ui = scale*gi
+ *                     dsens[g][p] = (ir*ur + ii*ui, ir*ui - ii*ur)
+ *                     dimg[p]     = (((0 + t_0) + t_1) + ...) + t_{G-1},  t_g = (sr*ur + si*ui, sr*ui - si*ur)
+ * shift = 0: q = p.  shift = 1: q = ((y - H/2) mod H, (x - W/2) mod W) with integer H/2, W/2 -- where torch.fft.ifftshift
+ * over (H, W) puts pixel p, for every parity of H and W -- so that a plain 2-D FFT of x is the centred transform of the
+ * coil images before its fftshift, and no shifted copy is made in a step.
+ * One lane owns its pixel(s) for every coil: no atomics, no shared-memory or cross-lane reduction, the same bits on every
+ * call.  With every pointer 16-byte aligned and W and W/2 even, two pixels move per 16-byte access, else one per 8-byte
+ * access; the results do not depend on which path ran.  One launch on `stream`, sized from H * W.
+ * INR_ERR_INVALID before any launch, the outputs untouched: a null pointer; G, H or W < 1 (or H, W > 2^30, G*H*W > 2^40);
+ * shift outside {0, 1}; a non-finite scale; a pointer that is not 8-byte aligned; an output that overlaps an input or
+ * the other output. */
+int inr_sense_apply(const float* img, const float* sens, int32_t G, int64_t H, int64_t W, float scale, int32_t shift,
+                    float* x, void* stream);
+int inr_sense_grad(const float* img, const float* sens, const float* gx, int32_t G, int64_t H, int64_t W, float scale,
+                   int32_t shift, float* dimg, float* dsens, void* stream);
 
 /* inr_focal_loss_grad (below): its descriptor, its block count and where the words of its loss_out buffer lie */
 #define INR_FOCAL_BLOCKS 255

@@ -1,6 +1,6 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network, the off-grid operators apart
 // (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, weighted epochs, grid rows, band
-// statistics, per-ring and continuous radial scaling, learned radial gain, mixture of heads, focal frequency loss, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
+// statistics, per-ring and continuous radial scaling, learned radial gain, mixture of heads, the SENSE product, focal frequency loss, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
 // the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -653,6 +653,49 @@ int inr_mix_apply(const inr_mix_desc* mix, const float* w, int64_t B, float* res
     return fail(INR_ERR_INVALID, "inr_mix_apply: res must be 8-byte aligned, w 4-byte aligned");
   hipError_t e = inr::launch_mix_apply(a, w, B, res, (hipStream_t)stream);
   return hip_done(e, "inr_mix_apply");
+}
+
+// ---- SENSE-model fits (inr_sense.hip) ----
+// what the two entries share: the extents, the shift switch and the factor; *plane_bytes = H * W * 8
+static int sense_dims_check(int32_t G, int64_t H, int64_t W, float scale, int32_t shift, int64_t* plane_bytes,
+                            const char* who) {
+  if (G < 1 || H < 1 || W < 1 || H > (1LL << 30) || W > (1LL << 30) || H * W > (1LL << 40) / G)
+    return fail(INR_ERR_INVALID, "%s: G %d, H %lld, W %lld (each >= 1, G * H * W <= 2^40)", who, (int)G, (long long)H,
+                (long long)W);
+  if (shift != 0 && shift != 1) return fail(INR_ERR_INVALID, "%s: shift = %d (0 or 1)", who, (int)shift);
+  if (!std::isfinite(scale)) return fail(INR_ERR_INVALID, "%s: scale = %g (must be finite)", who, (double)scale);
+  *plane_bytes = H * W * 8;
+  return INR_OK;
+}
+
+int inr_sense_apply(const float* img, const float* sens, int32_t G, int64_t H, int64_t W, float scale, int32_t shift,
+                    float* x, void* stream) {
+  if (img == nullptr || sens == nullptr || x == nullptr) return fail(INR_ERR_INVALID, "inr_sense_apply: null argument");
+  int64_t pb;
+  if (int rc = sense_dims_check(G, H, W, scale, shift, &pb, "inr_sense_apply")) return rc;
+  if ((((uintptr_t)img | (uintptr_t)sens | (uintptr_t)x) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_sense_apply: img / sens / x must be 8-byte aligned ((re, im) pairs move as one load)");
+  if (ranges_overlap(x, G * pb, img, pb) || ranges_overlap(x, G * pb, sens, G * pb))
+    return fail(INR_ERR_INVALID, "inr_sense_apply: x overlaps img or sens (a shifted write has no in-place form)");
+  hipError_t e = inr::launch_sense_apply(img, sens, G, H, W, scale, shift, x, (hipStream_t)stream);
+  return hip_done(e, "inr_sense_apply");
+}
+
+int inr_sense_grad(const float* img, const float* sens, const float* gx, int32_t G, int64_t H, int64_t W, float scale,
+                   int32_t shift, float* dimg, float* dsens, void* stream) {
+  if (img == nullptr || sens == nullptr || gx == nullptr || dimg == nullptr || dsens == nullptr)
+    return fail(INR_ERR_INVALID, "inr_sense_grad: null argument");
+  int64_t pb;
+  if (int rc = sense_dims_check(G, H, W, scale, shift, &pb, "inr_sense_grad")) return rc;
+  if ((((uintptr_t)img | (uintptr_t)sens | (uintptr_t)gx | (uintptr_t)dimg | (uintptr_t)dsens) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_sense_grad: img / sens / gx / dimg / dsens must be 8-byte aligned ((re, im) pairs "
+                "move as one load)");
+  if (ranges_overlap(dimg, pb, img, pb) || ranges_overlap(dimg, pb, sens, G * pb) || ranges_overlap(dimg, pb, gx, G * pb) ||
+      ranges_overlap(dsens, G * pb, img, pb) || ranges_overlap(dsens, G * pb, sens, G * pb) ||
+      ranges_overlap(dsens, G * pb, gx, G * pb) || ranges_overlap(dimg, pb, dsens, G * pb))
+    return fail(INR_ERR_INVALID, "inr_sense_grad: dimg / dsens overlaps another buffer");
+  hipError_t e = inr::launch_sense_grad(img, sens, gx, G, H, W, scale, shift, dimg, dsens, (hipStream_t)stream);
+  return hip_done(e, "inr_sense_grad");
 }
 
 // ---- focal frequency loss (inr_loss_focal.hip) ----

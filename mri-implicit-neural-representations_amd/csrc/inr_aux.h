@@ -231,6 +231,13 @@ hipError_t launch_mix_loss_grad(const LossDesc& ld, const MixArgs& a, const floa
                                 const uint8_t* mask, long long B, float* res, float* loss_out, float* dw, hipStream_t st);
 hipError_t launch_mix_apply(const MixArgs& a, const float* w, long long B, float* res, hipStream_t st);
 
+// SENSE-model fits (inr_sense.hip): coil images x_g = scale * S_g * I of an image network's and a
+// sensitivity network's outputs, written at the ifftshift-ed pixel when `shift`, and the adjoint of that product
+hipError_t launch_sense_apply(const float* img, const float* sens, int G, long long H, long long W, float scale, int shift,
+                              float* x, hipStream_t st);
+hipError_t launch_sense_grad(const float* img, const float* sens, const float* gx, int G, long long H, long long W,
+                             float scale, int shift, float* dimg, float* dsens, hipStream_t st);
+
 // focal frequency loss (inr_loss_focal.hip): the batch's largest weight, then the weighted squared error
 // and its gradient; the words of loss_out are laid out by the FOCAL_* constants.  dout may be nullptr
 constexpr int FOCAL_BLOCKS = 255;    // INR_FOCAL_BLOCKS

@@ -152,6 +152,8 @@ SYMBOLS = {
     "inr_gain_apply": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "inr_mix_loss_grad": (C.c_int, [C.POINTER(LossDesc), C.POINTER(MixDesc), _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "inr_mix_apply": (C.c_int, [C.POINTER(MixDesc), _P, C.c_int64, _P, _P]),
+    "inr_sense_apply": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_float, C.c_int32, _P, _P]),
+    "inr_sense_grad": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_float, C.c_int32, _P, _P, _P]),
     "inr_focal_loss_grad": (C.c_int, [C.POINTER(FocalDesc), _P, _P, _P, C.c_int64, _P, _P, _P]),
     "inr_coil_gram_scratch": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_coil_gram": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),

@@ -214,6 +214,8 @@ def run_cli(tr, config: dict, opts, extra: Optional[dict] = None) -> None:
         res["gain"] = tr.gain_summary
     if getattr(tr, "mixture_summary", None) is not None:  # a mixture-of-heads fit: the gate's weights over the grid
         res["mixture"] = tr.mixture_summary
+    if getattr(tr, "sense_summary", None) is not None:  # a SENSE-model fit: its settings and sqrt(sum_c |S_c|^2) over the grid
+        res["sense"] = tr.sense_summary
     if getattr(tr, "focal_summary", None) is not None:  # loss 'FFL': the three settings the fit ran under
         res["focal"] = tr.focal_summary
     if extra:

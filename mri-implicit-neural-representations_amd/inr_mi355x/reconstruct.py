@@ -9,7 +9,9 @@ at a time (inr_mi355x/grid.py): no full coordinate tensor exists at any point.
 What the grid means depends on the domain of the fit.  In image-space configs (config['transform']) a finer grid is
 super-resolution and a window is a zoom.  In k-space configs a finer grid over the same window samples k-space more
 densely, which is a larger field of view after the inverse FFT, and a narrower window keeps the low frequencies only,
-which is a lower-resolution image.
+which is a lower-resolution image.  A checkpoint of a SENSE-model fit (train_sense.py; 'image.' / 'sens.' keys) holds two
+networks in image space: render() gives its coil IMAGES on the grid (a finer one is super-resolution), kspace() their
+centred transform, recon.npy holds the images.
 
 CLI:
     python -m inr_mi355x.reconstruct --config C --checkpoint F (--shape C,H,W | --synthetic C,H,W | the config's scan)
@@ -129,6 +131,37 @@ class Reconstructor:
             self.gate_engine = self.gate._engine()
             self.gate_engine.drop_training_state()
             self.mix_clamp = bool((checkpoint.get("mixture") or {}).get("clamp", True))
+        # a SENSE-model fit (train_sense.py): 'net' holds 'image.' and 'sens.' keys; self.model /
+        # self.engine above are the image network, the sensitivity network (sized from its weights) and its encoder
+        # follow.  Both networks live in image space: render() gives coil IMAGES (renders_images) although the fit's data
+        # are k-space (in_image_space stays what the config says), kspace() their centred transform
+        self.sens_model = self.sens_engine = self.sens_encoder = self.sens_enc_B = self.sense_scale = None
+        self.renders_images = self.in_image_space  # what render() returns; in_image_space: what the fit's DATA are
+        from .sense import has_sense_keys, sens_encoder_config, split_state as split_sense
+        if has_sense_keys(checkpoint.get("net", {})):
+            if self.is_mfn:
+                raise NotImplementedError(f"a checkpoint with 'image.' / 'sens.' keys and model {name!r}")
+            meta = checkpoint.get("sense")
+            if meta is None:
+                raise ValueError("a checkpoint with 'image.' / 'sens.' keys carries a 'sense' entry (the factor of the "
+                                 "product and the sensitivity encoder); this one has none")
+            from .networks import FFN
+            weights = [v for k, v in split_sense(checkpoint["net"])[1].items() if k.endswith(".weight")]
+            with torch.random.fork_rng(devices=[]):
+                self.sens_encoder = Positional_Encoder(sens_encoder_config(meta, config["encoder"]), device=self.device)
+                self.sens_model = FFN({"network_input_size": int(weights[0].shape[1]), "network_output_size": 2,
+                                       "network_width": int(weights[0].shape[0]),
+                                       "network_depth": len(weights)}).to(self.device)
+            if emb == "gauss":
+                self.sens_engine = self.sens_model.fused_engine(int(meta["encoder"]["embedding_size"]))
+                self.sens_enc_B = self.sens_encoder.B.contiguous()
+            else:
+                self.sens_engine = self.sens_model._engine()
+            self.sens_engine.drop_training_state()
+            self.sense_scale = float(meta["scale"])
+            self.renders_images = True
+            # coils per forward sweep and per transform: the trainer's groups, so that the native grid gives its bits
+            self.sense_group = max(1, int(meta.get("coils_per_step") or self.shape[0]))
         self.load(checkpoint)
         self._bufs = None
         self._metric_bufs = {}
@@ -140,6 +173,10 @@ class Reconstructor:
             self.enc_B = enc.B.contiguous()
             if self.is_mfn:
                 self.model._enc_B = self.enc_B
+
+    def _rebind_sens_encoder(self, enc) -> None:
+        if self.sens_enc_B is not None:
+            self.sens_enc_B = enc.B.contiguous()
 
     def load(self, checkpoint) -> None:
         """ckpt['net'] and ckpt['enc'] (checkpoint.load_weights); ckpt['opt'] is not read."""
@@ -170,6 +207,13 @@ class Reconstructor:
                 eng.pack()
             load_weights(self.gate, None, {"net": gate})
             self.gate_engine.pack()
+        elif self.sens_model is not None:
+            from .sense import split_state as split_sense
+            img, sen = split_sense(checkpoint["net"])
+            load_weights(self.model, self.encoder, {"net": img, "enc": checkpoint.get("enc")}, self._rebind_encoder)
+            load_weights(self.sens_model, self.sens_encoder, {"net": sen, "enc": checkpoint["sense"].get("enc_B")},
+                         self._rebind_sens_encoder)
+            self.sens_engine.pack()
         elif self.scaler is not None:
             from .train_scaling import split_state
             back, scal = split_state(checkpoint["net"])
@@ -240,6 +284,8 @@ class Reconstructor:
         if self._bufs is None or self._bufs[0].shape[0] < chunk:
             self._bufs = (torch.empty(chunk, 3, device=self.device), torch.empty(chunk, device=self.device))
         cbuf, dbuf = self._bufs
+        if self.sens_model is not None:
+            return self._render_sense(spec, chunk, cbuf)
         out = torch.empty(n, 2, device=self.device)
         with_dist = self.takes_dist or self.ring_table is not None or self.scaler is not None or \
             self.experts is not None
@@ -252,12 +298,57 @@ class Reconstructor:
                 self.ring_table.unscale(d, out[lo:hi], out=out[lo:hi])
         return out.reshape(*spec.shape, 2)
 
+    def _render_sense(self, spec: GridSpec, chunk: int, cbuf: torch.Tensor) -> torch.Tensor:
+        """A SENSE-model checkpoint: coil IMAGES [C', H', W', 2] = scale * S_c * I on the grid, straight from
+        inr_sense_apply(shift = 0) -- the image network on the (y, x) rows of one plane with the coil column set to 0,
+        the sensitivity network on every row, in chunks of rows as the trainer's sweep.  Both networks live in image
+        space, so a finer grid is genuine super-resolution.  kspace() gives the centred transform where it is wanted."""
+        from .sense import sense_apply
+        n_coils, h, w = spec.shape
+        emb = self.config["encoder"]["embedding"]
+
+        def sweep(engine, encoder, enc_B, grid, zero_coil):
+            out = torch.empty(grid.rows, 2, device=self.device)
+            for lo in range(0, grid.rows, chunk):
+                hi = min(lo + chunk, grid.rows)
+                c = grid_rows(grid, lo, hi, coords_out=cbuf[:hi - lo], with_dist=False)[0]
+                if zero_coil:
+                    c[:, 0] = 0.0
+                x = c if enc_B is not None or emb == "none" else encoder.embedding(c).contiguous()
+                out[lo:hi] = engine.forward(x, enc_B, save=False)
+            return out
+
+        plane = GridSpec(spec.coils_total, h, w, coils=spec.coils[:1], window=spec.window)
+        img = sweep(self.engine, self.encoder, self.enc_B, plane, True)
+        out = torch.empty(n_coils, h, w, 2, device=self.device)
+        for c0 in range(0, n_coils, self.sense_group):  # the trainer's coil groups: one group's sensitivities at a time
+            c1 = min(c0 + self.sense_group, n_coils)
+            group = GridSpec(spec.coils_total, h, w, coils=spec.coils[c0:c1], window=spec.window)
+            sens = sweep(self.sens_engine, self.sens_encoder, self.sens_enc_B, group, False)
+            sense_apply(img, sens, c1 - c0, h, w, self.sense_scale, 0, out=out[c0:c1])
+        return out
+
+    @torch.no_grad()
+    def kspace(self, pred: torch.Tensor) -> torch.Tensor:
+        """[C', H', W', 2]: the k-space of a rendering -- the rendering itself for a k-space fit, evalchain.fft2c of the
+        coil images for an image-space one (config['transform'], or a SENSE-model checkpoint, whose k-space on the native
+        grid equals the trainer's predict_all() bit for bit)."""
+        from .evalchain import fft2c
+        if pred.dim() != 4 or pred.shape[-1] != 2:
+            raise RuntimeError(f"pred has shape {tuple(pred.shape)}, expected [C,H,W,2]")
+        if not self.renders_images:
+            return pred.contiguous()
+        if self.sens_model is None:
+            return fft2c(pred).contiguous()
+        g = self.sense_group  # transformed in the trainer's coil groups, as the sweep
+        return torch.cat([fft2c(pred[c:c + g]) for c in range(0, pred.shape[0], g)], 0).contiguous()
+
     # ---- pictures and numbers --------------------------------------------------------------------
     def _coil_images(self, pred: torch.Tensor) -> torch.Tensor:
         from .evalchain import ifft2c
         if pred.dim() != 4 or pred.shape[-1] != 2:
             raise RuntimeError(f"pred has shape {tuple(pred.shape)}, expected [C,H,W,2]")
-        return (pred if self.in_image_space else ifft2c(pred)).contiguous()
+        return (pred if self.renders_images else ifft2c(pred)).contiguous()
 
     @torch.no_grad()
     def rss(self, pred: torch.Tensor) -> torch.Tensor:
@@ -276,7 +367,9 @@ class Reconstructor:
         C, H, W = self.shape
         if tuple(pred.shape) != (C, H, W, 2):
             raise ValueError(f"compare() takes a prediction on the fit's own grid {(C, H, W, 2)}, got {tuple(pred.shape)}")
-        ref = image_metrics(None, self._coil_images(image_full.to(self.device).reshape(C, H, W, 2)))[0]
+        data = image_full.to(self.device).reshape(C, H, W, 2)
+        from .evalchain import ifft2c
+        ref = image_metrics(None, (data if self.in_image_space else ifft2c(data)).contiguous())[0]  # the DATA's domain
         m = image_metrics(ref, self._coil_images(pred))[1]
         psnr, ssim = m[:2].cpu().tolist()
         out = {"psnr": psnr, "ssim": ssim}
@@ -285,6 +378,8 @@ class Reconstructor:
             from .grid import GridSpec, grid_rows
             steps = int((self.config.get("partition") or {}).get("no_steps", 40))
             dist = grid_rows(GridSpec(C, H, W), 0, C * H * W, with_dist=True, device=self.device)[1]
+            if not self.in_image_space:  # k-space data: compare in k-space, whatever render() returns
+                pred = self.kspace(pred)
             out["bands"] = band_report(band_stats(dist, image_full.to(self.device).reshape(-1, 2), pred.reshape(-1, 2),
                                                   bounds=report_bounds(bands, steps)))
         return out
@@ -300,9 +395,9 @@ class Reconstructor:
         np.save(paths[0], pred.detach().cpu().numpy())
         paths.append(os.path.join(directory, "recon.png"))
         D.write_png_gray(paths[-1], D.gray8(self.rss(pred), take_abs=True).cpu())
-        if not self.in_image_space:
+        if not self.in_image_space:  # (where render() gives images of a k-space fit: their transform)
             paths.append(os.path.join(directory, "recon_kspace.png"))
-            D.write_png_gray(paths[-1], D.gray8(D.kspace_display(pred.contiguous())).cpu())
+            D.write_png_gray(paths[-1], D.gray8(D.kspace_display(self.kspace(pred))).cpu())
         return paths
 
 

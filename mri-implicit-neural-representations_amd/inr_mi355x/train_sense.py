@@ -1,0 +1,402 @@
+"""SENSE-model fits (no reference counterpart): every other fit here treats the C coils of a scan
+as C unrelated pictures.  This one has the physics that makes undersampled reconstruction work -- all coils show the same
+anatomy through different smooth sensitivity maps -- as two coordinate networks in IMAGE space, fitted to K-SPACE data:
+
+    I(y, x)      the image network, MODELS[config['model']](config['net']) with 2 outputs (one complex number); its
+                 input is the dataset's coordinate row with the coil column set to 0
+    S(c, y, x)   the sensitivity network, an FFN (64 x 4 unless config['sense']['net'] says otherwise) with 2 outputs on
+                 the dataset's coordinate row as it is, behind an encoder of its own (scale 1.0: coil maps are smooth)
+    X_g = scale * S_g * I,   K_g = fft2c(X_g),   loss = the config's pointwise loss on (K, gt, mask)
+
+One step takes one group of up to G = coils_per_step consecutive coils (the last group is smaller when G does not divide
+C) and is tier 1 throughout: inr_forward of both plans (stashing H*W and G*H*W rows), inr_sense_apply(shift = 1),
+torch.fft.fft2(ortho), inr_loss_grad, torch.fft.ifft2(ortho), inr_sense_grad, inr_backward of both, inr_adam_step of
+both with the same lr, betas, weight decay and per-epoch schedule.  No shifted copy is made in a step: targets and mask
+are stored ifftshift-ed once at ingest (per coil, over H x W), the product kernel writes every pixel where ifftshift
+would put it, and every loss kind of inr_loss_grad is independent of row order.  fftshift is applied only where a
+prediction leaves the trainer (predict_all and what is built on it: validation, pictures, the band report).
+
+Config key ``sense`` (all optional): coils_per_step (default: all coils), scale (default: the RMS of the zero-filled coil
+images, so that O(1) network outputs start at the data's magnitude), net {network_width, network_depth}, encoder {scale,
+embedding_size}, max_stash_bytes (default 8 GB: the sensitivity plan's activation stash for G*H*W rows must fit, or the
+trainer refuses with the largest coils_per_step that does).  Every undersampling pattern and an explicit mask work.
+
+CLI: python -m inr_mi355x.train_sense --config C [--output_path O] [--synthetic C,H,W] [--max_steps N] [--val]
+         [--save-images] [--shuffle] [--shuffle-seed S] [--band-report [N]]
+Every validation record, metrics() and the final JSON line carry ``sense``: coils_per_step, scale, the sensitivity
+network's width and depth, and min / max / mean over the grid of sens_rss = sqrt(sum_c |S_c|^2).
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .cli import cli_fit_data, cli_fits, parse_cli, run_cli
+from .engine import LossSpec
+from .networks import FFN, Positional_Encoder
+from .sense import (IMAGE_PREFIX, SENS_PREFIX, has_sense_keys, join_state, sens_encoder_config, sense_apply,  # noqa: F401
+                    sense_grad, shift_index, split_state)
+from .shuffle import CoilOrder
+from .train import MFN_MODELS, MODELS, hdr_weight
+from .trainer_base import ResidentFit, set_default_configs
+
+SENSE_KEYS = ("coils_per_step", "scale", "net", "encoder", "max_stash_bytes")
+SENS_NET = {"network_width": 64, "network_depth": 4}
+SENS_NET_KEYS = ("network_width", "network_depth")
+SENS_ENC_KEYS = ("scale", "embedding_size")
+MAX_STASH_BYTES = 8 * 10 ** 9
+
+
+def _only(over, allowed, where: str) -> dict:
+    over = over or {}
+    if not isinstance(over, dict):
+        raise ValueError(f"{where} is a mapping of {list(allowed)}, got {over!r}")
+    unknown = sorted(set(over) - set(allowed))
+    if unknown:
+        raise ValueError(f"{where} takes {list(allowed)}, got {unknown}")
+    return over
+
+
+def sense_settings(config: dict, n_coils: Optional[int] = None) -> dict:
+    """config['sense'] with its defaults: {'coils_per_step' (None: all coils; clipped to ``n_coils`` when given), 'scale'
+    (None: from the data), 'net' {network_width, network_depth}, 'encoder' {scale, embedding_size},
+    'max_stash_bytes'}.  Unknown keys, here or under 'net' / 'encoder', raise ValueError."""
+    over = _only(config.get("sense"), SENSE_KEYS, "config['sense']")
+    net = dict(SENS_NET)
+    net.update({k: int(v) for k, v in _only(over.get("net"), SENS_NET_KEYS, "config['sense']['net']").items()})
+    if net["network_depth"] < 2 or net["network_width"] < 1:
+        raise ValueError(f"config['sense']['net'] = {over.get('net')!r}: depth >= 2 and width >= 1")
+    main = config.get("encoder") or {}
+    enc = {"scale": 1.0, "embedding_size": main.get("embedding_size")}
+    enc.update(_only(over.get("encoder"), SENS_ENC_KEYS, "config['sense']['encoder']"))
+    enc["scale"] = float(enc["scale"])
+    if enc["embedding_size"] is not None:
+        enc["embedding_size"] = int(enc["embedding_size"])
+        if enc["embedding_size"] < 1:
+            raise ValueError(f"config['sense']['encoder']['embedding_size'] = {enc['embedding_size']}")
+    G = over.get("coils_per_step")
+    if G is not None:
+        G = int(G)
+        if G < 1:
+            raise ValueError(f"config['sense']['coils_per_step'] = {G} (at least 1)")
+        if n_coils is not None:
+            G = min(G, int(n_coils))
+    elif n_coils is not None:
+        G = int(n_coils)
+    scale = over.get("scale")
+    if scale is not None:
+        scale = float(scale)
+        if not math.isfinite(scale) or scale == 0.0:
+            raise ValueError(f"config['sense']['scale'] = {scale} (finite and not zero)")
+    stash = int(over.get("max_stash_bytes", MAX_STASH_BYTES))
+    if stash < 1:
+        raise ValueError(f"config['sense']['max_stash_bytes'] = {stash}")
+    return {"coils_per_step": G, "scale": scale, "net": net, "encoder": enc, "max_stash_bytes": stash}
+
+
+def coil_groups(n_coils: int, per_step: int) -> list:
+    """[(c0, c1)] of the steps of an epoch: consecutive coils, the last group smaller when per_step does not divide"""
+    return [(c0, min(c0 + per_step, n_coils)) for c0 in range(0, n_coils, per_step)]
+
+
+def sens_net_params(settings: dict, encoder_config: dict) -> dict:
+    """the FFN parameters of the sensitivity network behind its encoder"""
+    emb = encoder_config["embedding"]
+    E = settings["encoder"]["embedding_size"]
+    size = 2 * E if emb == "gauss" else E if emb == "LogF" else int(encoder_config.get("coordinates_size", 3))
+    return {"network_input_size": size, "network_output_size": 2, "network_depth": settings["net"]["network_depth"],
+            "network_width": settings["net"]["network_width"]}
+
+
+def check_sense_config(config: dict, world: int = 1, graph_steps: bool = False) -> None:
+    """What a SENSE-model fit cannot be combined with -- refused before anything is allocated."""
+    name = config["model"]
+    if name in MFN_MODELS:
+        raise NotImplementedError(f"model {name!r}: the image network of a SENSE-model fit is SIREN / FFN / WIRE / WIRE2D, "
+                                  "not one of the filter networks")
+    if name not in MODELS:
+        raise NotImplementedError(f"model {name!r} has no MI355X kernel yet (have {sorted(set(MODELS) - set(MFN_MODELS))})")
+    if config.get("optimizer", "Adam") != "Adam":
+        raise NotImplementedError("only Adam")
+    if config.get("transform", False):
+        raise NotImplementedError("transform: true: a SENSE-model fit lives in image space already and is fitted to "
+                                  "k-space data; image-space data have no sampling mask to profit from")
+    if config["trajectory"] not in (None, "none"):
+        raise NotImplementedError(f"config['trajectory'] = {config['trajectory']!r}: off-grid SENSE fits are not built "
+                                  "(the step's transform is a plain FFT)")
+    if config.get("ring_normalization") not in (None, "none", False):
+        raise NotImplementedError(f"config['ring_normalization'] = {config['ring_normalization']!r}: the targets of a "
+                                  "SENSE-model fit stay in the data's units (the model is linear in image space)")
+    if config.get("row_sampling") not in (None, "none", False):
+        raise NotImplementedError(f"config['row_sampling'] = {config['row_sampling']!r}: a step transforms whole coil "
+                                  "planes; weighted epochs run in INRTrainer (python -m inr_mi355x.train) only")
+    if config["per_coil"] or config["use_tv"]:
+        raise NotImplementedError("per_coil / use_tv: a SENSE-model step takes config['sense']['coils_per_step'] whole "
+                                  "coils; priors on the image are not built")
+    if config.get("virtual_coils"):
+        raise NotImplementedError(f"config['virtual_coils'] = {config['virtual_coils']!r}: compressed coils have no "
+                                  "smooth sensitivity map over a coil coordinate")
+    if config.get("loss") == "LSL":
+        raise NotImplementedError("loss 'LSL' (CenterLoss): its random-pair term is not part of inr_loss_grad")
+    if config.get("loss") == "FFL":
+        raise NotImplementedError("loss 'FFL' (focal frequency loss): FFL fits run in INRTrainer (python -m "
+                                  "inr_mi355x.train) only")
+    if config["regularization"]["type"] != "none":
+        raise NotImplementedError(f"regularization {config['regularization']['type']!r}: the penalty is over all "
+                                  "parameters of both networks and would couple the two engines")
+    if config.get("precision", "f32") != "f32":
+        raise NotImplementedError(f"precision {config['precision']!r}: SENSE-model fits run the fp32 tier-1 calls")
+    if graph_steps:
+        raise NotImplementedError("graph_steps: a SENSE-model step is a sequence of tier-1 calls and FFTs on two plans")
+    if world > 1:
+        raise NotImplementedError("SENSE-model fits run on one rank")
+
+
+def sens_stash_bytes(net_params: dict, gauss: bool, enc_size: int, rows: int) -> int:
+    """bytes of the activation stash the sensitivity plan needs for a step of ``rows`` rows (inr_plan_launch_dims /
+    inr_plan_workspace of a plan made for the question alone: nothing is allocated on the device)"""
+    from .engine import MLPEngine
+    eng = MLPEngine(L.KIND_FFN, net_params["network_input_size"], net_params["network_width"], net_params["network_depth"],
+                    net_params["network_output_size"], L.ACT_SIGMOID, L.INPUT_GAUSS if gauss else L.INPUT_X,
+                    enc_size if gauss else 0)
+    return max(eng.launch_dims(rows)[0], eng.workspace(rows)[0]) * eng.save_floats_per_tile * 4
+
+
+class SenseFitTrainer(ResidentFit):
+    def __init__(self, config: dict, image: torch.Tensor, coords: torch.Tensor, shape, device, seed: int = 0,
+                 mask: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1, process_group=None,
+                 mask_seed: Optional[int] = None, graph_steps: bool = False, coil_compression=None):
+        C_, H, W = (int(v) for v in shape[:3])
+        defaults = set_default_configs(dict(config))
+        if coil_compression is not None:
+            defaults["virtual_coils"] = defaults.get("virtual_coils") or coil_compression.coils_out
+        check_sense_config(defaults, world, graph_steps)
+        self.settings = sense_settings(defaults, C_)
+        emb = defaults["encoder"]["embedding"]
+        if self.settings["encoder"]["embedding_size"] is None:
+            raise ValueError("config['encoder']['embedding_size'] (or config['sense']['encoder']['embedding_size'])")
+        self.sens_params = sens_net_params(self.settings, defaults["encoder"])
+        G = self.coils_per_step = self.settings["coils_per_step"]
+        self._check_stash(G, H * W, emb == "gauss")
+        config = dict(config)
+        config.setdefault("batch_size", H * W)  # the step's batches are coil groups; the key is read by the base only
+        config = self._init_fit(config, shape, device, seed, rank, world, process_group, False, None)
+        # encoder, image network, sensitivity encoder, sensitivity network: all on one CPU generator, in this order
+        self._seeded_encoder(seed)
+        model = MODELS[config["model"]](config["net"])
+        self.sens_encoder = Positional_Encoder(sens_encoder_config(self.settings, config["encoder"]), device=self.device)
+        sens_model = FFN(self.sens_params)
+        self.model, self.sens_model = model.to(self.device), sens_model.to(self.device)
+        if emb == "gauss":
+            self.engine = self.model.fused_engine(config["encoder"]["embedding_size"])
+            self.sens_engine = self.sens_model.fused_engine(self.settings["encoder"]["embedding_size"])
+            self.enc_B, self.sens_enc_B = self.encoder.B.contiguous(), self.sens_encoder.B.contiguous()
+        else:
+            self.engine, self.sens_engine = self.model._engine(), self.sens_model._engine()
+            self.enc_B = self.sens_enc_B = None
+        if self.engine.out_features != 2:
+            raise ValueError(f"config['net']['network_output_size'] = {self.engine.out_features}: the image network gives "
+                             "one complex number (2 outputs)")
+        self.loss = LossSpec.from_config(config)
+        # the base's shuffled epochs permute ROWS; here the order of the coil groups is permuted, as per-coil fits do
+        shuffle, self.shuffle = self.shuffle, False
+        self._resident_data(image, coords, config["undersampling"], mask, mask_seed, False)
+        self.shuffle = shuffle
+        self.plane = H * W
+        self.groups = coil_groups(C_, G)
+        self.bs = G * self.plane  # validation's test loss walks the same groups
+        self.steps_per_epoch = len(self.groups)
+        if self.shuffle and len(self.groups) > 1:
+            self._coil_order = CoilOrder(len(self.groups), self.shuffle_seed)
+        self._ingest(C_, H, W)
+        self._hdr_A = {}
+        self._last_sense = None
+        self._finish_init()
+
+    # ---- set-up ----------------------------------------------------------------------------------
+    def _check_stash(self, G: int, plane: int, gauss: bool) -> None:
+        budget, E = self.settings["max_stash_bytes"], self.settings["encoder"]["embedding_size"]
+        need = sens_stash_bytes(self.sens_params, gauss, E, G * plane)
+        if need <= budget:
+            return
+        fits = next((g for g in range(G - 1, 0, -1) if sens_stash_bytes(self.sens_params, gauss, E, g * plane) <= budget), 0)
+        hint = f"the largest that fits is coils_per_step = {fits}" if fits else "not even coils_per_step = 1 fits"
+        raise ValueError(f"config['sense']['coils_per_step'] = {G}: the sensitivity plan's activation stash for {G} x "
+                         f"{plane} rows is {need} bytes, config['sense']['max_stash_bytes'] = {budget}; {hint}")
+
+    @torch.no_grad()
+    def _ingest(self, C_: int, H: int, W: int) -> None:
+        """Once: the inputs of both networks, the targets and the mask in ifftshift-ed row order per coil (what a plain
+        fft2 of the product kernel's output is compared with), and the factor of the product."""
+        perm = torch.from_numpy(shift_index(H, W)).to(self.device)
+        self._gt_s = self.image.view(C_, self.plane, 2)[:, perm].contiguous().view(-1, 2)
+        self._mask_s = None if self.mask is None else self.mask.view(C_, self.plane)[:, perm].contiguous().view(-1)
+        self._img_coords = self.coords[:self.plane].clone()
+        self._img_coords[:, 0] = 0.0
+        self._img_in = self._encoded(self.encoder, self.enc_B, self._img_coords)
+        self.sense_scale = self.settings["scale"]
+        if self.sense_scale is None:
+            from .evalchain import ifft2c
+            zf = ifft2c(self.image.view(C_, H, W, 2)).double()  # self.image: the zero-filled (masked) k-space
+            self.sense_scale = float(torch.sqrt((zf ** 2).sum(-1).mean()))
+            if not math.isfinite(self.sense_scale):
+                raise ValueError(f"the RMS of the zero-filled coil images is {self.sense_scale}")
+            if self.sense_scale == 0.0:
+                self.sense_scale = 1.0
+        self._x = torch.empty(self.coils_per_step, H, W, 2, device=self.device)
+
+    def _encoded(self, encoder, enc_B, coords: torch.Tensor) -> torch.Tensor:
+        if enc_B is not None or self.config["encoder"]["embedding"] == "none":
+            return coords.contiguous()
+        return encoder.embedding(coords).contiguous()
+
+    def _sens_in(self, lo: int, hi: int) -> torch.Tensor:
+        return self._encoded(self.sens_encoder, self.sens_enc_B, self.coords[lo:hi])
+
+    # ---- one optimizer step ----------------------------------------------------------------------
+    def _batch_hdr_A(self, it: int, lo: int, hi: int) -> float:
+        """A = mean_i((1-f_i)^2) over the group's coordinates (INRTrainer._batch_hdr_A); a mean does not see row order"""
+        if self.loss.kind != L.LOSS_HDR:
+            return 0.0
+        if it not in self._hdr_A:
+            self._hdr_A[it] = float(torch.mean(hdr_weight(self.coords[lo:hi], self.loss.sigma)))
+        return self._hdr_A[it]
+
+    def step(self, epoch: int, it: int) -> torch.Tensor:
+        if self._coil_order is not None:
+            it = self._coil_order.at(epoch, it)
+        c0, c1 = self.groups[it]
+        G, H, W = c1 - c0, int(self.shape[1]), int(self.shape[2])
+        lo, hi = c0 * self.plane, c1 * self.plane
+        count = max(self._count(lo, hi), 1)
+        A = self._batch_hdr_A(it, lo, hi)
+        cfg, lr = self.config, self._lr(epoch)
+        xs = self._sens_in(lo, hi)
+        m = None if self._mask_s is None else self._mask_s[lo:hi]
+        ib = self.engine.forward(self._img_in, self.enc_B, save=True)
+        sb = self.sens_engine.forward(xs, self.sens_enc_B, save=True)
+        x = sense_apply(ib, sb, G, H, W, self.sense_scale, 1, out=self._x[:G])
+        k = torch.view_as_real(torch.fft.fft2(torch.view_as_complex(x), norm="ortho"))
+        loss, gk = self.engine.loss_grad(self.loss, k.view(-1, 2), self._gt_s[lo:hi], count, mask=m, hdr_A=A)
+        gx = torch.view_as_real(torch.fft.ifft2(torch.view_as_complex(gk.view(G, H, W, 2)), norm="ortho"))
+        dimg, dsens = sense_grad(ib, sb, gx, G, H, W, self.sense_scale, 1)
+        self.engine.backward(self._img_in, self.enc_B, dimg)
+        self.sens_engine.backward(xs, self.sens_enc_B, dsens)
+        for eng in (self.engine, self.sens_engine):
+            eng.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
+        self.global_step += 1
+        return loss
+
+    # ---- validation ------------------------------------------------------------------------------
+    def _sweep(self, engine, enc_B, rows: torch.Tensor, chunk: int, encoder) -> torch.Tensor:
+        n = rows.shape[0]
+        return torch.cat([engine.forward(self._encoded(encoder, enc_B, rows[lo:min(lo + chunk, n)]), enc_B, save=False)
+                          for lo in range(0, n, chunk)], 0)
+
+    @torch.no_grad()
+    def _predict_raw(self, chunk: Optional[int] = None) -> torch.Tensor:
+        """k-space [C*H*W,2] in the dataset's own order, without a stash: the image network once, then group by group (the
+        step's coil groups, so that beside the prediction itself only one group's sensitivities and coil images exist at
+        a time) the sensitivity network in chunks of rows, inr_sense_apply(shift = 1), fft2, fftshift.  Leaves sens_rss
+        behind.  reconstruct.Reconstructor sweeps and transforms in the same groups: a forward call's bits depend on how
+        the rows are cut into calls."""
+        chunk = int(chunk or self.predict_chunk)
+        C_, H, W = (int(v) for v in self.shape[:3])
+        img = self._sweep(self.engine, self.enc_B, self._img_coords, chunk, self.encoder)
+        out = torch.empty(C_, H, W, 2, device=self.device)
+        rss2 = torch.zeros(self.plane, dtype=torch.float64, device=self.device)
+        for c0, c1 in self.groups:
+            G = c1 - c0
+            sens = self._sweep(self.sens_engine, self.sens_enc_B, self.coords[c0 * self.plane:c1 * self.plane], chunk,
+                               self.sens_encoder)
+            rss2 += (sens.double() ** 2).view(G, self.plane, 2).sum(dim=(0, 2))
+            x = sense_apply(img, sens, G, H, W, self.sense_scale, 1, out=self._x[:G])
+            k = torch.fft.fftshift(torch.fft.fft2(torch.view_as_complex(x), norm="ortho"), dim=(-2, -1))
+            out[c0:c1] = torch.view_as_real(k)
+        rss = torch.sqrt(rss2)
+        stats = torch.stack((rss.min(), rss.max(), rss.mean())).cpu().tolist()
+        self._last_sense = {"coils_per_step": self.coils_per_step, "scale": self.sense_scale,
+                            "net": {"width": self.sens_params["network_width"], "depth": self.sens_params["network_depth"]},
+                            "sens_rss": {"min": stats[0], "max": stats[1], "mean": stats[2]}}
+        return out.view(-1, 2)
+
+    @property
+    def sense_summary(self) -> Optional[dict]:
+        """{'coils_per_step', 'scale', 'net': {'width', 'depth'}, 'sens_rss': {'min', 'max', 'mean'}} of the last sweep
+        (None before the first)"""
+        return self._last_sense
+
+    @torch.no_grad()
+    def validate(self, epoch: int) -> dict:
+        rec = self._validated(epoch, self._predict_raw())
+        rec["sense"] = self._last_sense
+        return rec
+
+    @torch.no_grad()
+    def metrics(self) -> dict:
+        rec = super().metrics()
+        rec["sense"] = self._last_sense
+        return rec
+
+    # ---- checkpoints -----------------------------------------------------------------------------
+    def _sense_state(self) -> dict:
+        return {"scale": self.sense_scale, "coils_per_step": self.coils_per_step,
+                "enc_B": None if self.sens_encoder.B is None else self.sens_encoder.B.clone(),
+                "net": dict(self.settings["net"]), "encoder": dict(self.settings["encoder"])}
+
+    def checkpoint(self) -> dict:
+        """{'net', 'enc', 'opt'} in the reference's layout -- 'net' with 'image.*' then 'sens.*' keys, 'enc' the image
+        network's encoder matrix, 'opt' in torch.optim.Adam.state_dict() layout over the image network's parameters, then
+        the sensitivity network's -- plus 'sense': the factor, the sensitivity encoder's matrix and the sizes."""
+        from .checkpoint import optimizer_state
+        opt = optimizer_state(self.model, self.engine, self.config)
+        ni = len(opt["param_groups"][0]["params"])
+        sopt = optimizer_state(self.sens_model, self.sens_engine, self.config)
+        opt["state"].update({j + ni: st for j, st in sopt["state"].items()})
+        opt["param_groups"][0]["params"] = list(range(ni + len(sopt["param_groups"][0]["params"])))
+        return {"net": join_state(self.model.state_dict(), self.sens_model.state_dict()),
+                "enc": None if self.encoder.B is None else self.encoder.B.clone(), "opt": opt,
+                "sense": self._sense_state()}
+
+    def _rebind_sens_encoder(self, enc) -> None:
+        if self.sens_enc_B is not None:
+            self.sens_enc_B = enc.B.contiguous()
+
+    def load_checkpoint(self, ckpt: dict) -> None:
+        """Resumes under the same ``sense`` settings only: factor, coils_per_step and both sizes must be the trainer's."""
+        from .checkpoint import load_dict
+        if not has_sense_keys(ckpt["net"]) or ckpt.get("sense") is None:
+            raise ValueError("the checkpoint has no 'image.' / 'sens.' keys: it is not a SENSE-model fit's -- load it with "
+                             "the trainer that wrote it")
+        theirs, mine = ckpt["sense"], self._sense_state()
+        for key in ("scale", "coils_per_step", "net", "encoder"):
+            if theirs.get(key) != mine[key]:
+                raise ValueError(f"checkpoint and trainer disagree on config['sense']: {key} = {theirs.get(key)!r} in the "
+                                 f"checkpoint, {mine[key]!r} here")
+        img, sen = split_state(ckpt["net"])
+        ni = len(list(self.model.parameters()))
+        opt = ckpt.get("opt")
+        iopt = sopt = None
+        if opt:
+            iopt = {"state": {j: st for j, st in opt["state"].items() if j < ni}}
+            sopt = {"state": {j - ni: st for j, st in opt["state"].items() if j >= ni}}
+        load_dict(self.model, self.encoder, self.engine, {"net": img, "enc": ckpt.get("enc"), "opt": iopt},
+                  self._rebind_encoder)
+        load_dict(self.sens_model, self.sens_encoder, self.sens_engine,
+                  {"net": sen, "enc": theirs.get("enc_B"), "opt": sopt}, self._rebind_sens_encoder)
+        self._img_in = self._encoded(self.encoder, self.enc_B, self._img_coords)  # the encoder may have been replaced
+
+
+def main():
+    opts, config = parse_cli()
+    for cfg, fit_opts in cli_fits(config, opts):
+        image, coords, shape, cc = cli_fit_data(opts, cfg, "coil", image_space=False)
+        run_cli(SenseFitTrainer(cfg, image, coords, shape, "cuda", coil_compression=cc), cfg, fit_opts)
+
+
+if __name__ == "__main__":
+    main()
