@@ -66,7 +66,9 @@ extern "C" {
  *    heads: K experts' outputs mixed by a gate network's weights, the loss on the mix plus each expert's own loss on its
  *    k-space ring, and the gradients to all of them in one pass); inr_sense_apply and inr_sense_grad (SENSE-model fits:
  *    coil images as the product of an image network and a sensitivity network in image space, written where ifftshift
- *    puts them, and the adjoint of that product).
+ *    puts them, and the adjoint of that product); inr_sense_lowres, inr_sense_maps and inr_sense_adjoint (SENSE fits on
+ *    coil maps calibrated from the centre of k-space: low-resolution coil images of the centre block on any grid, their
+ *    unit-RSS maps, and the image half of inr_sense_grad alone).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -722,6 +724,34 @@ int inr_sense_apply(const float* img, const float* sens, int32_t G, int64_t H, i
                     float* x, void* stream);
 int inr_sense_grad(const float* img, const float* sens, const float* gx, int32_t G, int64_t H, int64_t W, float scale,
                    int32_t shift, float* dimg, float* dsens, void* stream);
+
+/* (v7 additions) SENSE fits on calibrated coil maps (no reference counterpart): the maps come once
+ * from the fully sampled centre of k-space, and a step needs the image half of inr_sense_grad alone.  Every product, sum,
+ * division and square root below is one correctly rounded fp32 operation (nothing contracted), sums start from zero;
+ * no atomics, the same bits on every call.  A (re, im) pair is one complex number; a complex product u * v is
+ * p0 = ur*vr; p1 = ui*vi; p2 = ur*vi; p3 = ui*vr; (p0 - p1, p2 + p3).
+ *   inr_sense_lowres:  kc [C,a,b,2] the (windowed) centre block of the centred k-space, ey [a,Ho,2] / ex [b,Wo,2] the
+ *       phasor tables of the Ho row and Wo column positions (made on the host in float64 with the phase reduced first,
+ *       carrying 1/sqrt(H) and 1/sqrt(W); the kernel evaluates no sine or cosine), out [C,Ho,Wo,2]:
+ *         T[c][j][x] = sum_i kc[c][j][i] * ex[i][x] (i ascending);  out[c][y][x] = sum_j ey[j][y] * T[c][j][x] (j ascending)
+ *       On the fit's own grid that is the centred orthonormal inverse transform of the zero-padded block; other positions
+ *       interpolate it exactly.
+ *   inr_sense_maps:  low [C,P,2] -> rss [P], maps [C,P,2].  r2 = sum_c (re*re + im*im) in coil order, rss[p] = sqrtf(r2),
+ *       maps[c][p] = low[c][p] / rss[p] where rss[p] > floor * max_p rss[p] and rss[p] > 0, else (0, 0).  Two launches:
+ *       the first writes rss, in the second every workgroup takes the (exact) maximum of rss before it divides.
+ *   inr_sense_adjoint:  sens [G,H*W,2], gx [G,H,W,2] -> dimg [H*W,2]: the dimg of inr_sense_grad on the same inputs, bit
+ *       for bit (same operations per pixel, same coil order, same place q under `shift`, same two-pixel rule); it reads
+ *       no img and writes no dsens.
+ * INR_ERR_INVALID before any launch, the outputs untouched: a null pointer; a or b outside 2..INR_SENSE_CALIB_MAX; C outside
+ * 1..65535, Ho or Wo outside 1..2^20 (lowres); C, P, G, H or W < 1 or more than 2^40 complex numbers; floor outside
+ * [0, 1); shift outside {0, 1}; a non-finite scale; a pointer that is not 8-byte aligned (rss: 4-byte); an output that
+ * overlaps an input or the other output. */
+#define INR_SENSE_CALIB_MAX 64
+int inr_sense_lowres(const float* kc, const float* ey, const float* ex, int32_t C, int32_t a, int32_t b, int64_t Ho,
+                     int64_t Wo, float* out, void* stream);
+int inr_sense_maps(const float* low, int32_t C, int64_t P, float floor, float* maps, float* rss, void* stream);
+int inr_sense_adjoint(const float* sens, const float* gx, int32_t G, int64_t H, int64_t W, float scale, int32_t shift,
+                      float* dimg, void* stream);
 
 /* inr_focal_loss_grad (below): its descriptor, its block count and where the words of its loss_out buffer lie */
 #define INR_FOCAL_BLOCKS 255

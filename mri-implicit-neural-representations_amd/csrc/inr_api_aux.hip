@@ -1,6 +1,6 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network, the off-grid operators apart
 // (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, weighted epochs, grid rows, band
-// statistics, per-ring and continuous radial scaling, learned radial gain, mixture of heads, the SENSE product, focal frequency loss, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
+// statistics, per-ring and continuous radial scaling, learned radial gain, mixture of heads, the SENSE product and its calibrated-map entries, focal frequency loss, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
 // the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -696,6 +696,59 @@ int inr_sense_grad(const float* img, const float* sens, const float* gx, int32_t
     return fail(INR_ERR_INVALID, "inr_sense_grad: dimg / dsens overlaps another buffer");
   hipError_t e = inr::launch_sense_grad(img, sens, gx, G, H, W, scale, shift, dimg, dsens, (hipStream_t)stream);
   return hip_done(e, "inr_sense_grad");
+}
+
+// ---- SENSE fits on calibrated coil maps (inr_sense_calib.hip) ----
+static_assert(INR_SENSE_CALIB_MAX == inr::SENSE_CALIB_MAX, "inr_abi.h and inr_aux.h disagree");
+
+int inr_sense_lowres(const float* kc, const float* ey, const float* ex, int32_t C, int32_t a, int32_t b, int64_t Ho,
+                     int64_t Wo, float* out, void* stream) {
+  if (kc == nullptr || ey == nullptr || ex == nullptr || out == nullptr)
+    return fail(INR_ERR_INVALID, "inr_sense_lowres: null argument");
+  if (a < 2 || a > INR_SENSE_CALIB_MAX || b < 2 || b > INR_SENSE_CALIB_MAX)
+    return fail(INR_ERR_INVALID, "inr_sense_lowres: a = %d, b = %d (each 2..%d)", (int)a, (int)b, INR_SENSE_CALIB_MAX);
+  if (C < 1 || C > 65535 || Ho < 1 || Wo < 1 || Ho > (1LL << 20) || Wo > (1LL << 20) || Ho * Wo > (1LL << 40) / C)
+    return fail(INR_ERR_INVALID, "inr_sense_lowres: C %d, Ho %lld, Wo %lld (C in 1..65535, Ho and Wo in 1..2^20, "
+                "C * Ho * Wo <= 2^40)", (int)C, (long long)Ho, (long long)Wo);
+  if ((((uintptr_t)kc | (uintptr_t)ey | (uintptr_t)ex | (uintptr_t)out) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_sense_lowres: kc / ey / ex / out must be 8-byte aligned ((re, im) pairs move as one "
+                "load)");
+  const int64_t out_bytes = (int64_t)C * Ho * Wo * 8;
+  if (ranges_overlap(out, out_bytes, kc, (int64_t)C * a * b * 8) || ranges_overlap(out, out_bytes, ey, a * Ho * 8) ||
+      ranges_overlap(out, out_bytes, ex, b * Wo * 8))
+    return fail(INR_ERR_INVALID, "inr_sense_lowres: out overlaps kc, ey or ex");
+  hipError_t e = inr::launch_sense_lowres(kc, ey, ex, C, a, b, Ho, Wo, out, (hipStream_t)stream);
+  return hip_done(e, "inr_sense_lowres");
+}
+
+int inr_sense_maps(const float* low, int32_t C, int64_t P, float floor, float* maps, float* rss, void* stream) {
+  if (low == nullptr || maps == nullptr || rss == nullptr) return fail(INR_ERR_INVALID, "inr_sense_maps: null argument");
+  if (C < 1 || P < 1 || P > (1LL << 40) / C)
+    return fail(INR_ERR_INVALID, "inr_sense_maps: C %d, P %lld (each >= 1, C * P <= 2^40)", (int)C, (long long)P);
+  if (!(floor >= 0.f && floor < 1.f))
+    return fail(INR_ERR_INVALID, "inr_sense_maps: floor = %g (0 <= floor < 1)", (double)floor);
+  if ((((uintptr_t)low | (uintptr_t)maps) & 7u) != 0 || ((uintptr_t)rss & 3u) != 0)
+    return fail(INR_ERR_INVALID, "inr_sense_maps: low / maps must be 8-byte aligned ((re, im) pairs move as one load), rss "
+                "4-byte aligned");
+  const int64_t cb = (int64_t)C * P * 8;
+  if (ranges_overlap(maps, cb, low, cb) || ranges_overlap(rss, P * 4, low, cb) || ranges_overlap(rss, P * 4, maps, cb))
+    return fail(INR_ERR_INVALID, "inr_sense_maps: maps / rss overlaps another buffer");
+  hipError_t e = inr::launch_sense_maps(low, C, P, floor, maps, rss, (hipStream_t)stream);
+  return hip_done(e, "inr_sense_maps");
+}
+
+int inr_sense_adjoint(const float* sens, const float* gx, int32_t G, int64_t H, int64_t W, float scale, int32_t shift,
+                      float* dimg, void* stream) {
+  if (sens == nullptr || gx == nullptr || dimg == nullptr) return fail(INR_ERR_INVALID, "inr_sense_adjoint: null argument");
+  int64_t pb;
+  if (int rc = sense_dims_check(G, H, W, scale, shift, &pb, "inr_sense_adjoint")) return rc;
+  if ((((uintptr_t)sens | (uintptr_t)gx | (uintptr_t)dimg) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_sense_adjoint: sens / gx / dimg must be 8-byte aligned ((re, im) pairs move as one "
+                "load)");
+  if (ranges_overlap(dimg, pb, sens, G * pb) || ranges_overlap(dimg, pb, gx, G * pb))
+    return fail(INR_ERR_INVALID, "inr_sense_adjoint: dimg overlaps sens or gx");
+  hipError_t e = inr::launch_sense_adjoint(sens, gx, G, H, W, scale, shift, dimg, (hipStream_t)stream);
+  return hip_done(e, "inr_sense_adjoint");
 }
 
 // ---- focal frequency loss (inr_loss_focal.hip) ----

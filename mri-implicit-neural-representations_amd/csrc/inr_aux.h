@@ -238,6 +238,16 @@ hipError_t launch_sense_apply(const float* img, const float* sens, int G, long l
 hipError_t launch_sense_grad(const float* img, const float* sens, const float* gx, int G, long long H, long long W,
                              float scale, int shift, float* dimg, float* dsens, hipStream_t st);
 
+// SENSE fits on calibrated coil maps (inr_sense_calib.hip): low-resolution coil images of the windowed
+// centre block kc [C,a,b,2] at Ho x Wo separable positions (phasor tables ey [a,Ho,2], ex [b,Wo,2] from the host), unit-RSS
+// maps of them, and the image half of launch_sense_grad alone
+constexpr int SENSE_CALIB_MAX = 64;  // INR_SENSE_CALIB_MAX: entries per axis of the centre block
+hipError_t launch_sense_lowres(const float* kc, const float* ey, const float* ex, int C, int a, int b, long long Ho,
+                               long long Wo, float* out, hipStream_t st);
+hipError_t launch_sense_maps(const float* low, int C, long long P, float floor, float* maps, float* rss, hipStream_t st);
+hipError_t launch_sense_adjoint(const float* sens, const float* gx, int G, long long H, long long W, float scale, int shift,
+                                float* dimg, hipStream_t st);
+
 // focal frequency loss (inr_loss_focal.hip): the batch's largest weight, then the weighted squared error
 // and its gradient; the words of loss_out are laid out by the FOCAL_* constants.  dout may be nullptr
 constexpr int FOCAL_BLOCKS = 255;    // INR_FOCAL_BLOCKS

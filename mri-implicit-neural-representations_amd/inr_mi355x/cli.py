@@ -38,10 +38,10 @@ def apply_shuffle_flags(config: dict, opts) -> dict:
     return config
 
 
-def parse_cli(val_and_samples: bool = True, argv=None):
+def parse_cli(val_and_samples: bool = True, argv=None, extra_flags=None):
     """(opts, config) of a driver's command line: --config, --output_path, --synthetic, --max_steps, the shuffle flags and
     --save-images; ``val_and_samples``: --val and --data_samples as well (the loops with a validation epoch), and then
-    --save-images needs --val."""
+    --save-images needs --val.  ``extra_flags(ap)``: a driver's own flags, added before the line is parsed."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, required=True)
     if val_and_samples:
@@ -68,6 +68,8 @@ def parse_cli(val_and_samples: bool = True, argv=None):
     add_ring_normalize_flag(ap)
     from .sampling import add_row_sampling_flag, apply_row_sampling_flag
     add_row_sampling_flag(ap)
+    if extra_flags is not None:
+        extra_flags(ap)
     opts = ap.parse_args(argv)
     if val_and_samples and opts.save_images and not opts.val:
         ap.error("--save-images needs --val (the pictures are those of the validation epoch)")
@@ -150,6 +152,8 @@ def cli_folders(tr, opts):
     tr.save_training_images(image_dir)
     if getattr(tr, "gridding", None) is not None:
         tr.save_gridding_image(image_dir)
+    if getattr(tr, "cg_sense", None) is not None:  # a calibrated-maps SENSE fit with its CG-SENSE baseline
+        tr.save_cg_sense_image(image_dir)
     return ckpt_dir, image_dir
 
 

@@ -136,6 +136,10 @@ class Reconstructor:
         # follow.  Both networks live in image space: render() gives coil IMAGES (renders_images) although the fit's data
         # are k-space (in_image_space stays what the config says), kspace() their centred transform
         self.sens_model = self.sens_engine = self.sens_encoder = self.sens_enc_B = self.sense_scale = None
+        # ... or, fitted on calibrated maps, 'image.' keys alone and the windowed centre block of
+        # k-space in 'sense': the maps are rebuilt for every rendered grid (inr_sense_lowres, inr_sense_maps)
+        self.sense_block = self.sense_calib = None
+        self._sense_maps = {}
         self.renders_images = self.in_image_space  # what render() returns; in_image_space: what the fit's DATA are
         from .sense import has_sense_keys, sens_encoder_config, split_state as split_sense
         if has_sense_keys(checkpoint.get("net", {})):
@@ -145,6 +149,17 @@ class Reconstructor:
             if meta is None:
                 raise ValueError("a checkpoint with 'image.' / 'sens.' keys carries a 'sense' entry (the factor of the "
                                  "product and the sensitivity encoder); this one has none")
+        if has_sense_keys(checkpoint.get("net", {})) and meta.get("maps", "learned") == "calibrated":
+            if meta.get("block") is None or meta.get("calib") is None:
+                raise ValueError("a calibrated-maps checkpoint carries sense['block'] and sense['calib']; this one does not")
+            self.sense_block = meta["block"].to(self.device, torch.float32).contiguous()
+            if self.sense_block.dim() != 4 or self.sense_block.shape[0] != self.shape[0]:
+                raise ValueError(f"sense['block'] has shape {tuple(self.sense_block.shape)}, the fit {self.shape[0]} coils")
+            self.sense_calib = dict(meta["calib"])
+            self.sense_scale = float(meta["scale"])
+            self.renders_images = True
+            self.sense_group = max(1, int(meta.get("coils_per_step") or self.shape[0]))
+        elif has_sense_keys(checkpoint.get("net", {})):
             from .networks import FFN
             weights = [v for k, v in split_sense(checkpoint["net"])[1].items() if k.endswith(".weight")]
             with torch.random.fork_rng(devices=[]):
@@ -207,6 +222,9 @@ class Reconstructor:
                 eng.pack()
             load_weights(self.gate, None, {"net": gate})
             self.gate_engine.pack()
+        elif self.sense_block is not None:
+            from .sense_calib import image_net_of
+            load_weights(self.model, self.encoder, {"net": image_net_of(checkpoint["net"]), "enc": checkpoint.get("enc")}, self._rebind_encoder)
         elif self.sens_model is not None:
             from .sense import split_state as split_sense
             img, sen = split_sense(checkpoint["net"])
@@ -284,7 +302,7 @@ class Reconstructor:
         if self._bufs is None or self._bufs[0].shape[0] < chunk:
             self._bufs = (torch.empty(chunk, 3, device=self.device), torch.empty(chunk, device=self.device))
         cbuf, dbuf = self._bufs
-        if self.sens_model is not None:
+        if self.sens_model is not None or self.sense_block is not None:
             return self._render_sense(spec, chunk, cbuf)
         out = torch.empty(n, 2, device=self.device)
         with_dist = self.takes_dist or self.ring_table is not None or self.scaler is not None or \
@@ -321,12 +339,28 @@ class Reconstructor:
         plane = GridSpec(spec.coils_total, h, w, coils=spec.coils[:1], window=spec.window)
         img = sweep(self.engine, self.encoder, self.enc_B, plane, True)
         out = torch.empty(n_coils, h, w, 2, device=self.device)
+        if self.sense_block is not None:  # calibrated maps: all coils' maps on this grid (the RSS is over every coil)
+            maps = self._calibrated_maps(h, w, spec.window)
+            for c0 in range(0, n_coils, self.sense_group):
+                c1 = min(c0 + self.sense_group, n_coils)
+                sens = maps[list(spec.coils[c0:c1])].reshape(-1, 2).contiguous()
+                sense_apply(img, sens, c1 - c0, h, w, self.sense_scale, 0, out=out[c0:c1])
+            return out
         for c0 in range(0, n_coils, self.sense_group):  # the trainer's coil groups: one group's sensitivities at a time
             c1 = min(c0 + self.sense_group, n_coils)
             group = GridSpec(spec.coils_total, h, w, coils=spec.coils[c0:c1], window=spec.window)
             sens = sweep(self.sens_engine, self.sens_encoder, self.sens_enc_B, group, False)
             sense_apply(img, sens, c1 - c0, h, w, self.sense_scale, 0, out=out[c0:c1])
         return out
+
+    def _calibrated_maps(self, h: int, w: int, window) -> torch.Tensor:
+        """[C,h*w,2]: the calibrated maps on a grid, rebuilt from the stored block (the last grid is kept)"""
+        from .sense_calib import calibrate
+        key = (int(h), int(w), tuple(float(v) for v in window))
+        if key not in self._sense_maps:
+            _, H, W = self.shape
+            self._sense_maps = {key: calibrate(self.sense_block, H, W, float(self.sense_calib["floor"]), h, w, key[2])[0]}
+        return self._sense_maps[key]
 
     @torch.no_grad()
     def kspace(self, pred: torch.Tensor) -> torch.Tensor:
@@ -338,7 +372,7 @@ class Reconstructor:
             raise RuntimeError(f"pred has shape {tuple(pred.shape)}, expected [C,H,W,2]")
         if not self.renders_images:
             return pred.contiguous()
-        if self.sens_model is None:
+        if self.sens_model is None and self.sense_block is None:
             return fft2c(pred).contiguous()
         g = self.sense_group  # transformed in the trainer's coil groups, as the sweep
         return torch.cat([fft2c(pred[c:c + g]) for c in range(0, pred.shape[0], g)], 0).contiguous()

@@ -25,6 +25,13 @@ CLI: python -m inr_mi355x.train_sense --config C [--output_path O] [--synthetic 
          [--save-images] [--shuffle] [--shuffle-seed S] [--band-report [N]]
 Every validation record, metrics() and the final JSON line carry ``sense``: coils_per_step, scale, the sensitivity
 network's width and depth, and min / max / mean over the grid of sens_rss = sqrt(sum_c |S_c|^2).
+
+``sense.maps: calibrated`` (--sense-maps calibrated): the sensitivities are not learned but
+estimated ONCE from the fully sampled centre of k-space (sense_calib.py: ``sense.calib`` {size [a, b], window, floor, acs};
+with ``acs`` the block is OR-ed into every coil's sampling mask first) and stay fixed.  The sensitivity network, its stash,
+its backward and its Adam update are gone; a step takes every coil and needs the image half of the adjoint alone
+(inr_sense_adjoint).  ``sense.baseline: cg-N`` (--sense-baseline) adds CG-SENSE from the same maps and samples, scored as
+the fit is, to every record as ``cg_sense``.
 """
 from __future__ import annotations
 
@@ -45,6 +52,8 @@ from .train import MFN_MODELS, MODELS, hdr_weight
 from .trainer_base import ResidentFit, set_default_configs
 
 SENSE_KEYS = ("coils_per_step", "scale", "net", "encoder", "max_stash_bytes")
+MAPS_KEYS = ("maps", "calib", "baseline", "cg_lambda")  # DESIGN.md 4.29; the last three with maps: calibrated only
+MAPS_MODES = ("learned", "calibrated")
 SENS_NET = {"network_width": 64, "network_depth": 4}
 SENS_NET_KEYS = ("network_width", "network_depth")
 SENS_ENC_KEYS = ("scale", "embedding_size")
@@ -65,7 +74,8 @@ def sense_settings(config: dict, n_coils: Optional[int] = None) -> dict:
     """config['sense'] with its defaults: {'coils_per_step' (None: all coils; clipped to ``n_coils`` when given), 'scale'
     (None: from the data), 'net' {network_width, network_depth}, 'encoder' {scale, embedding_size},
     'max_stash_bytes'}.  Unknown keys, here or under 'net' / 'encoder', raise ValueError."""
-    over = _only(config.get("sense"), SENSE_KEYS, "config['sense']")
+    over = _only(config.get("sense"), SENSE_KEYS + MAPS_KEYS, "config['sense']")
+    maps_settings(config)  # what the two modes refuse of each other
     net = dict(SENS_NET)
     net.update({k: int(v) for k, v in _only(over.get("net"), SENS_NET_KEYS, "config['sense']['net']").items()})
     if net["network_depth"] < 2 or net["network_width"] < 1:
@@ -96,6 +106,60 @@ def sense_settings(config: dict, n_coils: Optional[int] = None) -> dict:
     if stash < 1:
         raise ValueError(f"config['sense']['max_stash_bytes'] = {stash}")
     return {"coils_per_step": G, "scale": scale, "net": net, "encoder": enc, "max_stash_bytes": stash}
+
+
+def maps_settings(config: dict, H: Optional[int] = None, W: Optional[int] = None) -> Optional[dict]:
+    """None for learned maps (the default: config['sense'] without 'maps', or maps: learned -- then 'calib', 'baseline'
+    and 'cg_lambda' are refused), else {'maps': 'calibrated', 'calib': sense_calib.parse_calib's dict, 'baseline': N of
+    cg-N or None, 'cg_lambda'} -- then 'net', 'encoder' and 'max_stash_bytes' are refused: there is no sensitivity plan.
+    ValueError for every refusal."""
+    from .sense_calib import parse_calib, parse_sense_baseline
+    over = _only(config.get("sense"), SENSE_KEYS + MAPS_KEYS, "config['sense']")
+    mode = over.get("maps", "learned")
+    if mode not in MAPS_MODES:
+        raise ValueError(f"config['sense']['maps'] = {mode!r}: one of {list(MAPS_MODES)}")
+    if mode == "learned":
+        given = [k for k in MAPS_KEYS[1:] if k in over]
+        if given:
+            raise ValueError(f"config['sense'] has {given} but maps: learned -- they belong to maps: calibrated")
+        return None
+    given = [k for k in ("net", "encoder", "max_stash_bytes") if k in over]
+    if given:
+        raise ValueError(f"config['sense'] has {given} but maps: calibrated -- there is no sensitivity network to size")
+    lam = float(over.get("cg_lambda", 0.0))
+    if not math.isfinite(lam) or lam < 0.0:
+        raise ValueError(f"config['sense']['cg_lambda'] = {lam} (finite and >= 0)")
+    return {"maps": "calibrated", "calib": parse_calib(over.get("calib"), H, W),
+            "baseline": parse_sense_baseline(over.get("baseline")), "cg_lambda": lam}
+
+
+def calibration_mask(calib: dict, undersampling, shape, mask: Optional[torch.Tensor] = None, mask_seed=None):
+    """maps: calibrated -- (mask, acceleration): the sampling mask [C*H*W] (bool, CPU) the fit runs under -- the caller's,
+    or the one ``undersampling`` (config['undersampling']) draws as ResidentFit._resident_data would -- with the
+    calibration block OR-ed into every coil (calib['acs']) or checked to be fully sampled (ValueError naming the number
+    of missing entries), and numel / sampled of the result.  (None, 1.0) without any mask: the block is taken as it is."""
+    from .sense_calib import add_acs, missing_in_block
+    from .undersampling import Undersampler, parse_undersampling_argument
+    C_, H, W = (int(v) for v in shape[:3])
+    a, b = calib["size"]
+    if mask is not None:
+        m = mask.detach().cpu().reshape(C_, H, W).numpy() != 0
+    else:
+        method, uparams = parse_undersampling_argument(undersampling)
+        if method is None or method.lower() == "none":
+            return None, 1.0
+        hw = Undersampler(method, seed=mask_seed).create_mask(H, W, uparams).cpu().numpy() != 0
+        m = np.broadcast_to(hw[None], (C_, H, W))
+    if calib["acs"]:
+        m = np.stack([add_acs(m[c], a, b) for c in range(C_)])
+    else:
+        missing = missing_in_block(m, a, b)
+        if missing:
+            raise ValueError(f"config['sense']['calib']: the {a} x {b} centre block is not fully sampled under the mask: "
+                             f"{missing} of its {C_ * a * b} entries (over {C_} coils) are missing; set acs: true to add "
+                             "the block to the mask")
+    acceleration = float(m.size / max(int(np.count_nonzero(m)), 1))
+    return torch.from_numpy(np.ascontiguousarray(m).reshape(-1)), acceleration
 
 
 def coil_groups(n_coils: int, per_step: int) -> list:
@@ -176,28 +240,31 @@ class SenseFitTrainer(ResidentFit):
             defaults["virtual_coils"] = defaults.get("virtual_coils") or coil_compression.coils_out
         check_sense_config(defaults, world, graph_steps)
         self.settings = sense_settings(defaults, C_)
+        self.calib = maps_settings(defaults, H, W)  # None: learned maps
         emb = defaults["encoder"]["embedding"]
-        if self.settings["encoder"]["embedding_size"] is None:
-            raise ValueError("config['encoder']['embedding_size'] (or config['sense']['encoder']['embedding_size'])")
-        self.sens_params = sens_net_params(self.settings, defaults["encoder"])
         G = self.coils_per_step = self.settings["coils_per_step"]
-        self._check_stash(G, H * W, emb == "gauss")
+        if self.calib is None:
+            if self.settings["encoder"]["embedding_size"] is None:
+                raise ValueError("config['encoder']['embedding_size'] (or config['sense']['encoder']['embedding_size'])")
+            self.sens_params = sens_net_params(self.settings, defaults["encoder"])
+            self._check_stash(G, H * W, emb == "gauss")
+        else:  # the mask with the calibration block in it, formed up front and handed on as the explicit mask
+            mask, self.acceleration = calibration_mask(self.calib["calib"], defaults["undersampling"], (C_, H, W), mask,
+                                                       mask_seed)
         config = dict(config)
         config.setdefault("batch_size", H * W)  # the step's batches are coil groups; the key is read by the base only
         config = self._init_fit(config, shape, device, seed, rank, world, process_group, False, None)
         # encoder, image network, sensitivity encoder, sensitivity network: all on one CPU generator, in this order
         self._seeded_encoder(seed)
         model = MODELS[config["model"]](config["net"])
-        self.sens_encoder = Positional_Encoder(sens_encoder_config(self.settings, config["encoder"]), device=self.device)
-        sens_model = FFN(self.sens_params)
-        self.model, self.sens_model = model.to(self.device), sens_model.to(self.device)
-        if emb == "gauss":
-            self.engine = self.model.fused_engine(config["encoder"]["embedding_size"])
-            self.sens_engine = self.sens_model.fused_engine(self.settings["encoder"]["embedding_size"])
-            self.enc_B, self.sens_enc_B = self.encoder.B.contiguous(), self.sens_encoder.B.contiguous()
+        if self.calib is not None:
+            self.model = model.to(self.device)
+            self.sens_encoder = self.sens_model = self.sens_engine = self.sens_enc_B = None
+            self.engine = self.model.fused_engine(config["encoder"]["embedding_size"]) if emb == "gauss" else \
+                self.model._engine()
+            self.enc_B = self.encoder.B.contiguous() if emb == "gauss" else None
         else:
-            self.engine, self.sens_engine = self.model._engine(), self.sens_model._engine()
-            self.enc_B = self.sens_enc_B = None
+            self._two_networks(model, config, emb)
         if self.engine.out_features != 2:
             raise ValueError(f"config['net']['network_output_size'] = {self.engine.out_features}: the image network gives "
                              "one complex number (2 outputs)")
@@ -205,6 +272,9 @@ class SenseFitTrainer(ResidentFit):
         # the base's shuffled epochs permute ROWS; here the order of the coil groups is permuted, as per-coil fits do
         shuffle, self.shuffle = self.shuffle, False
         self._resident_data(image, coords, config["undersampling"], mask, mask_seed, False)
+        if self.calib is not None and self.mask is not None:  # an explicit mask leaves the data unmasked: zero-fill them
+            self.image = (self.image_full * self.mask.view(-1, 1).to(self.image_full.dtype)).contiguous()
+            self.train_values = self._train_values_data = self._t_image = self.image
         self.shuffle = shuffle
         self.plane = H * W
         self.groups = coil_groups(C_, G)
@@ -215,9 +285,25 @@ class SenseFitTrainer(ResidentFit):
         self._ingest(C_, H, W)
         self._hdr_A = {}
         self._last_sense = None
+        self.cg_sense = self._cg_image = self._cg_rss = None
         self._finish_init()
+        if self.calib is not None and self.calib["baseline"] is not None:
+            self._cg_sense_baseline()
 
     # ---- set-up ----------------------------------------------------------------------------------
+    def _two_networks(self, model, config: dict, emb: str) -> None:
+        """learned maps: the sensitivity encoder and network follow the image network on the same CPU generator"""
+        self.sens_encoder = Positional_Encoder(sens_encoder_config(self.settings, config["encoder"]), device=self.device)
+        sens_model = FFN(self.sens_params)
+        self.model, self.sens_model = model.to(self.device), sens_model.to(self.device)
+        if emb == "gauss":
+            self.engine = self.model.fused_engine(config["encoder"]["embedding_size"])
+            self.sens_engine = self.sens_model.fused_engine(self.settings["encoder"]["embedding_size"])
+            self.enc_B, self.sens_enc_B = self.encoder.B.contiguous(), self.sens_encoder.B.contiguous()
+        else:
+            self.engine, self.sens_engine = self.model._engine(), self.sens_model._engine()
+            self.enc_B = self.sens_enc_B = None
+
     def _check_stash(self, G: int, plane: int, gauss: bool) -> None:
         budget, E = self.settings["max_stash_bytes"], self.settings["encoder"]["embedding_size"]
         need = sens_stash_bytes(self.sens_params, gauss, E, G * plane)
@@ -242,12 +328,27 @@ class SenseFitTrainer(ResidentFit):
         if self.sense_scale is None:
             from .evalchain import ifft2c
             zf = ifft2c(self.image.view(C_, H, W, 2)).double()  # self.image: the zero-filled (masked) k-space
-            self.sense_scale = float(torch.sqrt((zf ** 2).sum(-1).mean()))
+            if self.calib is None:
+                self.sense_scale = float(torch.sqrt((zf ** 2).sum(-1).mean()))
+            else:
+                # unit-RSS maps leave the whole magnitude to the image network, whose last_tanh bounds it by 1: the
+                # largest RSS of the zero-filled images, times the acceleration (zero-filling with a fraction 1/R of the
+                # entries shows the object at 1/R of its magnitude, plus aliases)
+                self.sense_scale = float(torch.sqrt((zf ** 2).sum(dim=(0, 3)).max())) * self.acceleration
             if not math.isfinite(self.sense_scale):
                 raise ValueError(f"the RMS of the zero-filled coil images is {self.sense_scale}")
             if self.sense_scale == 0.0:
                 self.sense_scale = 1.0
         self._x = torch.empty(self.coils_per_step, H, W, 2, device=self.device)
+        if self.calib is not None:
+            from .sense_calib import calibrate, cut_block
+            c = self.calib["calib"]
+            self._block = torch.from_numpy(cut_block(self.image.view(C_, H, W, 2), *c["size"], c["window"])).to(self.device)
+            self._maps, self.sens_rss = calibrate(self._block, H, W, c["floor"])  # [C,P,2], [P]: resident
+            self._maps_rows = self._maps.view(-1, 2)
+            self._dimg = torch.empty(self.plane, 2, device=self.device)
+            stats = torch.stack((self.sens_rss.min(), self.sens_rss.max(), self.sens_rss.double().mean().float()))
+            self._rss_stats = dict(zip(("min", "max", "mean"), stats.cpu().tolist()))
 
     def _encoded(self, encoder, enc_B, coords: torch.Tensor) -> torch.Tensor:
         if enc_B is not None or self.config["encoder"]["embedding"] == "none":
@@ -275,8 +376,20 @@ class SenseFitTrainer(ResidentFit):
         count = max(self._count(lo, hi), 1)
         A = self._batch_hdr_A(it, lo, hi)
         cfg, lr = self.config, self._lr(epoch)
-        xs = self._sens_in(lo, hi)
         m = None if self._mask_s is None else self._mask_s[lo:hi]
+        if self.calib is not None:
+            from .sense_calib import sense_adjoint
+            ib = self.engine.forward(self._img_in, self.enc_B, save=True)
+            x = sense_apply(ib, self._maps_rows[lo:hi], G, H, W, self.sense_scale, 1, out=self._x[:G])
+            k = torch.view_as_real(torch.fft.fft2(torch.view_as_complex(x), norm="ortho"))
+            loss, gk = self.engine.loss_grad(self.loss, k.view(-1, 2), self._gt_s[lo:hi], count, mask=m, hdr_A=A)
+            gx = torch.view_as_real(torch.fft.ifft2(torch.view_as_complex(gk.view(G, H, W, 2)), norm="ortho"))
+            dimg = sense_adjoint(self._maps_rows[lo:hi], gx, G, H, W, self.sense_scale, 1, dimg=self._dimg)
+            self.engine.backward(self._img_in, self.enc_B, dimg)
+            self.engine.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
+            self.global_step += 1
+            return loss
+        xs = self._sens_in(lo, hi)
         ib = self.engine.forward(self._img_in, self.enc_B, save=True)
         sb = self.sens_engine.forward(xs, self.sens_enc_B, save=True)
         x = sense_apply(ib, sb, G, H, W, self.sense_scale, 1, out=self._x[:G])
@@ -308,6 +421,16 @@ class SenseFitTrainer(ResidentFit):
         C_, H, W = (int(v) for v in self.shape[:3])
         img = self._sweep(self.engine, self.enc_B, self._img_coords, chunk, self.encoder)
         out = torch.empty(C_, H, W, 2, device=self.device)
+        if self.calib is not None:  # the same sweep through the resident maps
+            for c0, c1 in self.groups:
+                x = sense_apply(img, self._maps_rows[c0 * self.plane:c1 * self.plane], c1 - c0, H, W, self.sense_scale, 1,
+                                out=self._x[:c1 - c0])
+                k = torch.fft.fftshift(torch.fft.fft2(torch.view_as_complex(x), norm="ortho"), dim=(-2, -1))
+                out[c0:c1] = torch.view_as_real(k)
+            self._last_sense = {"coils_per_step": self.coils_per_step, "scale": self.sense_scale, "maps": "calibrated",
+                                "calib": dict(self.calib["calib"], acceleration=self.acceleration),
+                                "sens_rss": dict(self._rss_stats)}
+            return out.view(-1, 2)
         rss2 = torch.zeros(self.plane, dtype=torch.float64, device=self.device)
         for c0, c1 in self.groups:
             G = c1 - c0
@@ -334,16 +457,61 @@ class SenseFitTrainer(ResidentFit):
     def validate(self, epoch: int) -> dict:
         rec = self._validated(epoch, self._predict_raw())
         rec["sense"] = self._last_sense
+        if self.cg_sense is not None:
+            rec["cg_sense"] = self.cg_sense
         return rec
 
     @torch.no_grad()
     def metrics(self) -> dict:
         rec = super().metrics()
         rec["sense"] = self._last_sense
+        if self.cg_sense is not None:
+            rec["cg_sense"] = self.cg_sense
         return rec
+
+    # ---- the conventional reconstruction from the same maps and samples ---------------------------
+    @torch.no_grad()
+    def _cg_sense_baseline(self) -> None:
+        """config['sense']['baseline'] = cg-N: N conjugate-gradient iterations of CG-SENSE
+        (sense_calib.cg_sense) on the fit's own maps, samples and mask, made once; its k-space prediction is scored as
+        the fit's own is (coil images, RSS, PSNR / SSIM against the full data through the validation's kernel).  Leaves
+        the record in self.cg_sense, the image [H*W,2] in self._cg_image and its RSS picture in self._cg_rss; reads no
+        random number and no parameter."""
+        import time
+        from .evalchain import image_metrics
+        from .sense_calib import cg_sense, kspace_of
+        from .validation import coil_images
+        iters, lam = self.calib["baseline"], self.calib["cg_lambda"]
+        torch.cuda.synchronize(self.device)
+        t0 = time.time()
+        iterates, objective = cg_sense(self._maps, self._gt_s, self._mask_s, self.shape, iters, lam)
+        self._cg_image = iterates[-1].contiguous()
+        torch.cuda.synchronize(self.device)
+        seconds = time.time() - t0
+        pred = kspace_of(self._cg_image, self._maps, self.shape)
+        if self._ref_rss is None:
+            self._ref_rss = image_metrics(None, coil_images(self.image_full, self.shape, self.in_image_space))[0]
+        self._cg_rss, m = image_metrics(self._ref_rss, coil_images(pred, self.shape, self.in_image_space))[:2]
+        psnr_, ssim_ = m[:2].cpu().tolist()
+        self.cg_sense = {"iters": iters, "lambda": lam, "psnr": psnr_, "ssim": ssim_,
+                         "objective": [float(v) for v in objective], "seconds": seconds}
+
+    @torch.no_grad()
+    def save_cg_sense_image(self, directory: str, prefix: str = "") -> str:
+        """cg_sense_{psnr}_psnr_{ssim}_ssim.png: the baseline's RSS image through the display kernels"""
+        import os
+        if self.cg_sense is None:
+            raise RuntimeError("save_cg_sense_image: the fit has no config['sense']['baseline']")
+        D, b = self._display()
+        os.makedirs(directory, exist_ok=True)
+        name = prefix + "cg_sense_{:.4g}_psnr_{:.4g}_ssim.png".format(self.cg_sense["psnr"], self.cg_sense["ssim"])
+        return self._write_gray(D, b, os.path.join(directory, name), self._cg_rss, True)
 
     # ---- checkpoints -----------------------------------------------------------------------------
     def _sense_state(self) -> dict:
+        if self.calib is not None:
+            from .sense_calib import calibrated_state
+            return calibrated_state(self.sense_scale, self.coils_per_step, self.calib["calib"], self._block)
         return {"scale": self.sense_scale, "coils_per_step": self.coils_per_step,
                 "enc_B": None if self.sens_encoder.B is None else self.sens_encoder.B.clone(),
                 "net": dict(self.settings["net"]), "encoder": dict(self.settings["encoder"])}
@@ -354,6 +522,10 @@ class SenseFitTrainer(ResidentFit):
         the sensitivity network's -- plus 'sense': the factor, the sensitivity encoder's matrix and the sizes."""
         from .checkpoint import optimizer_state
         opt = optimizer_state(self.model, self.engine, self.config)
+        if self.calib is not None:  # 'image.*' keys only; the maps are not stored: 'sense' holds the windowed block
+            from .sense_calib import image_net_state
+            return {"net": image_net_state(self.model.state_dict()), "enc": None if self.encoder.B is None else self.encoder.B.clone(), "opt": opt,
+                    "sense": self._sense_state()}
         ni = len(opt["param_groups"][0]["params"])
         sopt = optimizer_state(self.sens_model, self.sens_engine, self.config)
         opt["state"].update({j + ni: st for j, st in sopt["state"].items()})
@@ -373,6 +545,15 @@ class SenseFitTrainer(ResidentFit):
             raise ValueError("the checkpoint has no 'image.' / 'sens.' keys: it is not a SENSE-model fit's -- load it with "
                              "the trainer that wrote it")
         theirs, mine = ckpt["sense"], self._sense_state()
+        from .sense_calib import check_calibrated_state, check_sense_mode, image_net_of
+        check_sense_mode(theirs, "learned" if self.calib is None else "calibrated")
+        if self.calib is not None:
+            check_calibrated_state(theirs, mine)
+            img = image_net_of(ckpt["net"])
+            load_dict(self.model, self.encoder, self.engine, {"net": img, "enc": ckpt.get("enc"), "opt": ckpt.get("opt")},
+                      self._rebind_encoder)
+            self._img_in = self._encoded(self.encoder, self.enc_B, self._img_coords)
+            return
         for key in ("scale", "coils_per_step", "net", "encoder"):
             if theirs.get(key) != mine[key]:
                 raise ValueError(f"checkpoint and trainer disagree on config['sense']: {key} = {theirs.get(key)!r} in the "
@@ -391,11 +572,29 @@ class SenseFitTrainer(ResidentFit):
         self._img_in = self._encoded(self.encoder, self.enc_B, self._img_coords)  # the encoder may have been replaced
 
 
+def add_sense_flags(ap) -> None:
+    ap.add_argument("--sense-maps", type=str, default=None, metavar="ARG",
+                    help="learned | calibrated (config['sense']['maps']): coil maps from a second network, or estimated "
+                         "once from the fully sampled centre of k-space and fixed")
+    ap.add_argument("--sense-baseline", type=str, default=None, metavar="ARG",
+                    help="none | cg-N (config['sense']['baseline']; with calibrated maps): CG-SENSE from the same maps and "
+                         "samples, scored as the fit is")
+
+
+def apply_sense_flags(config: dict, opts) -> dict:
+    for key, value in (("maps", opts.sense_maps), ("baseline", opts.sense_baseline)):
+        if value is not None:
+            config["sense"] = dict(config.get("sense") or {}, **{key: value})
+    return config
+
+
 def main():
-    opts, config = parse_cli()
+    opts, config = parse_cli(extra_flags=add_sense_flags)
+    config = apply_sense_flags(config, opts)
     for cfg, fit_opts in cli_fits(config, opts):
         image, coords, shape, cc = cli_fit_data(opts, cfg, "coil", image_space=False)
-        run_cli(SenseFitTrainer(cfg, image, coords, shape, "cuda", coil_compression=cc), cfg, fit_opts)
+        tr = SenseFitTrainer(cfg, image, coords, shape, "cuda", coil_compression=cc)
+        run_cli(tr, cfg, fit_opts, extra=None if tr.cg_sense is None else {"cg_sense": tr.cg_sense})
 
 
 if __name__ == "__main__":
