@@ -68,7 +68,9 @@ extern "C" {
  *    coil images as the product of an image network and a sensitivity network in image space, written where ifftshift
  *    puts them, and the adjoint of that product); inr_sense_lowres, inr_sense_maps and inr_sense_adjoint (SENSE fits on
  *    coil maps calibrated from the centre of k-space: low-resolution coil images of the centre block on any grid, their
- *    unit-RSS maps, and the image half of inr_sense_grad alone).
+ *    unit-RSS maps, and the image half of inr_sense_grad alone); inr_image_tv_grad (a total-variation prior on the
+ *    image of a SENSE fit: smoothed isotropic TV of the image network's output, its value and its gradient in one gather
+ *    pass).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -752,6 +754,35 @@ int inr_sense_lowres(const float* kc, const float* ey, const float* ex, int32_t 
 int inr_sense_maps(const float* low, int32_t C, int64_t P, float floor, float* maps, float* rss, void* stream);
 int inr_sense_adjoint(const float* sens, const float* gx, int32_t G, int64_t H, int64_t W, float scale, int32_t shift,
                       float* dimg, void* stream);
+
+/* (v7 addition) A total-variation prior on the IMAGE of a SENSE fit (no reference counterpart; the
+ * reference's tv_loss, inr_loss_tv_grad here, is on a coil's predicted k-space).  img [H,W,2] is one complex image (the
+ * image network's output, a (re, im) pair per pixel), dimg like it.  Smoothed isotropic TV with forward differences that
+ * are zero past the last row / column; per pixel p = (y, x), in fp32, every product, sum, difference, square root and
+ * division rounded on its own (nothing contracted), in this order:
+ *   ax = I[y][x+1] - I[y][x];  ay = I[y+1][x] - I[y][x]          (per component; 0 where x = W-1 / y = H-1)
+ *   s0 = axr*axr; s1 = axi*axi; s2 = ayr*ayr; s3 = ayi*ayi;  a = s0 + s1;  b = s2 + s3;  q0 = a + b;  q = q0 + e2
+ *   n = sqrtf(q)  (e2 = eps*eps);   u = ax / n;  v = ay / n      (both (0, 0) where n == 0, which only eps == 0 can give)
+ *   term = n - eps
+ *   t0 = u(y, x-1) - u(p);  t1 = v(y-1, x) - v(p);  t = t0 + t1;  d = c * t        (a missing neighbour's u / v is 0)
+ *   c = weight / (H W), formed in fp64 and rounded to fp32 once
+ * dimg[p] = d when accumulate == 0, dimg[p] + d (one fp32 sum per component) when accumulate == 1; dimg may be NULL (the
+ * value alone; whether it is changes no bit of loss_out[0]).  loss_out[0] = S * (weight / (H W)) formed in fp64 and rounded
+ * once -- written, not added -- where S is the fp64 sum of the fp32 terms: a lane's terms in the order it meets them, the
+ * 256 lanes of a block by a fixed tree, the blocks' partials in block order by one thread of a second launch.
+ * loss_out must be 8-byte aligned; loss_out[1] is unused and loss_out[INR_IMAGE_TV_PARTIALS + 2 b], b < the launch's
+ * block count <= INR_IMAGE_TV_BLOCKS, holds block b's fp64 partial: words 2 .. 511 are scratch, and a buffer of
+ * INR_LOSS_WORDS floats serves.  A gather: one lane owns a pixel (two neighbouring pixels where W is even: one 16-byte
+ * access when img and dimg are 16-byte aligned, two of 8 bytes otherwise) and recomputes n at its own pixel, its left and
+ * its upper neighbour.  No atomics: the same inputs give the same bits on every call, whatever the alignment.  Two
+ * launches on `stream`.
+ * INR_ERR_INVALID before any launch, the outputs untouched: a null img or loss_out; H or W < 1 (or > 2^30, or H * W > 2^40);
+ * eps negative or not finite; weight not finite; accumulate outside {0, 1}; img or dimg not 8-byte aligned, loss_out not
+ * 8-byte aligned; dimg or loss_out overlapping img or each other. */
+#define INR_IMAGE_TV_BLOCKS 255
+#define INR_IMAGE_TV_PARTIALS 2
+int inr_image_tv_grad(const float* img, int64_t H, int64_t W, float weight, float eps, int32_t accumulate,
+                      float* loss_out, float* dimg, void* stream);
 
 /* inr_focal_loss_grad (below): its descriptor, its block count and where the words of its loss_out buffer lie */
 #define INR_FOCAL_BLOCKS 255

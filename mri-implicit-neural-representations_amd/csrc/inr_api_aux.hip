@@ -1,6 +1,6 @@
 // inr_api_aux.hip -- the entries of the C-ABI (include/inr_abi.h) that launch no network, the off-grid operators apart
 // (inr_api_offgrid.hip): encoders, losses, TV, Adam, image metrics, display, shuffle, weighted epochs, grid rows, band
-// statistics, per-ring and continuous radial scaling, learned radial gain, mixture of heads, the SENSE product and its calibrated-map entries, focal frequency loss, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
+// statistics, per-ring and continuous radial scaling, learned radial gain, mixture of heads, the SENSE product, its calibrated-map entries and the TV prior on its image, focal frequency loss, coil compression.  Each checks its arguments, fills an argument struct, launches and maps
 // the hipError_t to a code; none allocates device memory or syncs.
 #include <cmath>
 #include <cstring>
@@ -749,6 +749,31 @@ int inr_sense_adjoint(const float* sens, const float* gx, int32_t G, int64_t H, 
     return fail(INR_ERR_INVALID, "inr_sense_adjoint: dimg overlaps sens or gx");
   hipError_t e = inr::launch_sense_adjoint(sens, gx, G, H, W, scale, shift, dimg, (hipStream_t)stream);
   return hip_done(e, "inr_sense_adjoint");
+}
+
+// ---- total-variation prior on the image of a SENSE fit (inr_image_tv.hip) ----
+static_assert(INR_IMAGE_TV_BLOCKS == inr::IMAGE_TV_BLOCKS && INR_IMAGE_TV_PARTIALS == inr::IMAGE_TV_PARTIALS &&
+                  INR_IMAGE_TV_PARTIALS % 2 == 0 && INR_IMAGE_TV_PARTIALS + 2 * INR_IMAGE_TV_BLOCKS <= INR_LOSS_WORDS,
+              "inr_abi.h and inr_aux.h disagree, or the fp64 partials leave the INR_LOSS_WORDS words");
+
+int inr_image_tv_grad(const float* img, int64_t H, int64_t W, float weight, float eps, int32_t accumulate, float* loss_out,
+                      float* dimg, void* stream) {
+  if (img == nullptr || loss_out == nullptr) return fail(INR_ERR_INVALID, "inr_image_tv_grad: null argument");
+  if (H < 1 || W < 1 || H > (1LL << 30) || W > (1LL << 30) || H * W > (1LL << 40))
+    return fail(INR_ERR_INVALID, "inr_image_tv_grad: H %lld, W %lld (each >= 1, H * W <= 2^40)", (long long)H, (long long)W);
+  if (!std::isfinite(eps) || eps < 0.f) return fail(INR_ERR_INVALID, "inr_image_tv_grad: eps = %g (finite and >= 0)", (double)eps);
+  if (!std::isfinite(weight)) return fail(INR_ERR_INVALID, "inr_image_tv_grad: weight = %g (must be finite)", (double)weight);
+  if (accumulate != 0 && accumulate != 1)
+    return fail(INR_ERR_INVALID, "inr_image_tv_grad: accumulate = %d (0 or 1)", (int)accumulate);
+  if ((((uintptr_t)img | (uintptr_t)dimg | (uintptr_t)loss_out) & 7u) != 0)
+    return fail(INR_ERR_INVALID, "inr_image_tv_grad: img / dimg / loss_out must be 8-byte aligned ((re, im) pairs move as "
+                "one load; loss_out holds fp64 partials)");
+  const int64_t pb = H * W * 8, lb = (int64_t)INR_LOSS_WORDS * 4;
+  if (ranges_overlap(loss_out, lb, img, pb) ||
+      (dimg != nullptr && (ranges_overlap(dimg, pb, img, pb) || ranges_overlap(dimg, pb, loss_out, lb))))
+    return fail(INR_ERR_INVALID, "inr_image_tv_grad: dimg / loss_out overlaps another buffer");
+  hipError_t e = inr::launch_image_tv_grad(img, H, W, weight, eps, accumulate != 0, loss_out, dimg, (hipStream_t)stream);
+  return hip_done(e, "inr_image_tv_grad");
 }
 
 // ---- focal frequency loss (inr_loss_focal.hip) ----

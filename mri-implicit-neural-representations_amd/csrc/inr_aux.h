@@ -248,6 +248,15 @@ hipError_t launch_sense_maps(const float* low, int C, long long P, float floor, 
 hipError_t launch_sense_adjoint(const float* sens, const float* gx, int G, long long H, long long W, float scale, int shift,
                                 float* dimg, hipStream_t st);
 
+// total-variation prior on the image of a SENSE fit (inr_image_tv.hip): weight * TV of img [H,W,2] into
+// loss_out[0], weight * dTV/dimg written or added into dimg (nullptr: the value alone).  loss_out[IMAGE_TV_PARTIALS ...]
+// holds one fp64 partial per block
+constexpr int IMAGE_TV_THREADS = 256;
+constexpr int IMAGE_TV_BLOCKS = 255;   // INR_IMAGE_TV_BLOCKS
+constexpr int IMAGE_TV_PARTIALS = 2;   // INR_IMAGE_TV_PARTIALS: word of the first fp64 partial (8-byte aligned with loss_out)
+hipError_t launch_image_tv_grad(const float* img, long long H, long long W, float weight, float eps, bool accumulate,
+                                float* loss_out, float* dimg, hipStream_t st);
+
 // focal frequency loss (inr_loss_focal.hip): the batch's largest weight, then the weighted squared error
 // and its gradient; the words of loss_out are laid out by the FOCAL_* constants.  dout may be nullptr
 constexpr int FOCAL_BLOCKS = 255;    // INR_FOCAL_BLOCKS

@@ -157,6 +157,7 @@ SYMBOLS = {
     "inr_sense_lowres": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
     "inr_sense_maps": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_float, _P, _P, _P]),
     "inr_sense_adjoint": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_float, C.c_int32, _P, _P]),
+    "inr_image_tv_grad": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_int32, _P, _P, _P]),
     "inr_focal_loss_grad": (C.c_int, [C.POINTER(FocalDesc), _P, _P, _P, C.c_int64, _P, _P, _P]),
     "inr_coil_gram_scratch": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "inr_coil_gram": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
@@ -177,6 +178,7 @@ COIL_MAX, COIL_TILE_PIXELS = 32, 128  # INR_COIL_MAX, INR_COIL_TILE_PIXELS
 BAND_MAX, BAND_FIELDS, BAND_TILE_ROWS = 64, 7, 1024  # INR_BAND_MAX, INR_BAND_FIELDS, INR_BAND_TILE_ROWS
 RADIAL_KNOTS_MAX = 4096  # INR_RADIAL_KNOTS_MAX
 SENSE_CALIB_MAX = 64  # INR_SENSE_CALIB_MAX
+IMAGE_TV_BLOCKS, IMAGE_TV_PARTIALS, IMAGE_TV_THREADS = 255, 2, 256  # INR_IMAGE_TV_BLOCKS / _PARTIALS; lanes per block
 ROW_CDF_TILE = 1024  # rows per workgroup of inr_row_cdf (one scratch word each)
 METRICS_WORDS = 8  # inr_image_metrics' metrics_out: psnr, ssim, sse, max_ref, min_ref, max_rec, min_rec, data_range
 

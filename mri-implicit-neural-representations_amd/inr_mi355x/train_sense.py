@@ -32,6 +32,14 @@ with ``acs`` the block is OR-ed into every coil's sampling mask first) and stay 
 its backward and its Adam update are gone; a step takes every coil and needs the image half of the adjoint alone
 (inr_sense_adjoint).  ``sense.baseline: cg-N`` (--sense-baseline) adds CG-SENSE from the same maps and samples, scored as
 the fit is, to every record as ``cg_sense``.
+
+``sense.prior: {kind: tv, weight, eps}`` (--sense-prior tv:WEIGHT[:EPS]), with either maps mode:
+smoothed isotropic total variation of the image network's output I (not of scale * I) is added to every step's loss.
+After inr_sense_adjoint / inr_sense_grad has written dimg, inr_image_tv_grad adds weight * dTV/dI into it; the step
+returns data loss + weight * TV.  With learned maps and several coil groups per epoch every group's step carries the
+prior with its full weight.  Records and metrics() gain a top-level ``prior`` {kind, weight, eps, value} (the value on
+the image of the prediction sweep); the validation's test loss stays data-only.  ``use_tv`` stays refused: it is the
+reference's TV of a coil's predicted k-space.  With the key absent nothing changes.
 """
 from __future__ import annotations
 
@@ -54,6 +62,7 @@ from .trainer_base import ResidentFit, set_default_configs
 SENSE_KEYS = ("coils_per_step", "scale", "net", "encoder", "max_stash_bytes")
 MAPS_KEYS = ("maps", "calib", "baseline", "cg_lambda")  # DESIGN.md 4.29; the last three with maps: calibrated only
 MAPS_MODES = ("learned", "calibrated")
+PRIOR_KEYS = ("prior",)  # DESIGN.md 4.30; with either maps mode
 SENS_NET = {"network_width": 64, "network_depth": 4}
 SENS_NET_KEYS = ("network_width", "network_depth")
 SENS_ENC_KEYS = ("scale", "embedding_size")
@@ -74,7 +83,7 @@ def sense_settings(config: dict, n_coils: Optional[int] = None) -> dict:
     """config['sense'] with its defaults: {'coils_per_step' (None: all coils; clipped to ``n_coils`` when given), 'scale'
     (None: from the data), 'net' {network_width, network_depth}, 'encoder' {scale, embedding_size},
     'max_stash_bytes'}.  Unknown keys, here or under 'net' / 'encoder', raise ValueError."""
-    over = _only(config.get("sense"), SENSE_KEYS + MAPS_KEYS, "config['sense']")
+    over = _only(config.get("sense"), SENSE_KEYS + MAPS_KEYS + PRIOR_KEYS, "config['sense']")
     maps_settings(config)  # what the two modes refuse of each other
     net = dict(SENS_NET)
     net.update({k: int(v) for k, v in _only(over.get("net"), SENS_NET_KEYS, "config['sense']['net']").items()})
@@ -114,7 +123,7 @@ def maps_settings(config: dict, H: Optional[int] = None, W: Optional[int] = None
     cg-N or None, 'cg_lambda'} -- then 'net', 'encoder' and 'max_stash_bytes' are refused: there is no sensitivity plan.
     ValueError for every refusal."""
     from .sense_calib import parse_calib, parse_sense_baseline
-    over = _only(config.get("sense"), SENSE_KEYS + MAPS_KEYS, "config['sense']")
+    over = _only(config.get("sense"), SENSE_KEYS + MAPS_KEYS + PRIOR_KEYS, "config['sense']")
     mode = over.get("maps", "learned")
     if mode not in MAPS_MODES:
         raise ValueError(f"config['sense']['maps'] = {mode!r}: one of {list(MAPS_MODES)}")
@@ -131,6 +140,14 @@ def maps_settings(config: dict, H: Optional[int] = None, W: Optional[int] = None
         raise ValueError(f"config['sense']['cg_lambda'] = {lam} (finite and >= 0)")
     return {"maps": "calibrated", "calib": parse_calib(over.get("calib"), H, W),
             "baseline": parse_sense_baseline(over.get("baseline")), "cg_lambda": lam}
+
+
+def prior_settings(config: dict) -> Optional[dict]:
+    """config['sense']['prior']: None when absent or 'none', else sense_prior.parse_prior's {'kind': 'tv',
+    'weight', 'eps'}.  Valid with learned and with calibrated maps.  ValueError for every refusal."""
+    from .sense_prior import parse_prior
+    over = _only(config.get("sense"), SENSE_KEYS + MAPS_KEYS + PRIOR_KEYS, "config['sense']")
+    return parse_prior(over.get("prior"))
 
 
 def calibration_mask(calib: dict, undersampling, shape, mask: Optional[torch.Tensor] = None, mask_seed=None):
@@ -200,7 +217,8 @@ def check_sense_config(config: dict, world: int = 1, graph_steps: bool = False) 
                                   "planes; weighted epochs run in INRTrainer (python -m inr_mi355x.train) only")
     if config["per_coil"] or config["use_tv"]:
         raise NotImplementedError("per_coil / use_tv: a SENSE-model step takes config['sense']['coils_per_step'] whole "
-                                  "coils; priors on the image are not built")
+                                  "coils, and use_tv is the reference's TV of a coil's predicted k-space; the TV prior "
+                                  "on the image is config['sense']['prior'] (sense.prior: {kind: tv, weight, eps})")
     if config.get("virtual_coils"):
         raise NotImplementedError(f"config['virtual_coils'] = {config['virtual_coils']!r}: compressed coils have no "
                                   "smooth sensitivity map over a coil coordinate")
@@ -241,6 +259,7 @@ class SenseFitTrainer(ResidentFit):
         check_sense_config(defaults, world, graph_steps)
         self.settings = sense_settings(defaults, C_)
         self.calib = maps_settings(defaults, H, W)  # None: learned maps
+        self.prior = prior_settings(defaults)  # None: no prior on the image
         emb = defaults["encoder"]["embedding"]
         G = self.coils_per_step = self.settings["coils_per_step"]
         if self.calib is None:
@@ -284,7 +303,9 @@ class SenseFitTrainer(ResidentFit):
             self._coil_order = CoilOrder(len(self.groups), self.shuffle_seed)
         self._ingest(C_, H, W)
         self._hdr_A = {}
-        self._last_sense = None
+        self._last_sense = self._last_prior = None
+        if self.prior is not None:  # the prior's value and block partials, made once
+            self._prior_out = torch.zeros(L.LOSS_WORDS, device=self.device)
         self.cg_sense = self._cg_image = self._cg_rss = None
         self._finish_init()
         if self.calib is not None and self.calib["baseline"] is not None:
@@ -385,6 +406,8 @@ class SenseFitTrainer(ResidentFit):
             loss, gk = self.engine.loss_grad(self.loss, k.view(-1, 2), self._gt_s[lo:hi], count, mask=m, hdr_A=A)
             gx = torch.view_as_real(torch.fft.ifft2(torch.view_as_complex(gk.view(G, H, W, 2)), norm="ortho"))
             dimg = sense_adjoint(self._maps_rows[lo:hi], gx, G, H, W, self.sense_scale, 1, dimg=self._dimg)
+            if self.prior is not None:
+                loss = loss + self._add_prior(ib, dimg, H, W)
             self.engine.backward(self._img_in, self.enc_B, dimg)
             self.engine.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
             self.global_step += 1
@@ -397,12 +420,21 @@ class SenseFitTrainer(ResidentFit):
         loss, gk = self.engine.loss_grad(self.loss, k.view(-1, 2), self._gt_s[lo:hi], count, mask=m, hdr_A=A)
         gx = torch.view_as_real(torch.fft.ifft2(torch.view_as_complex(gk.view(G, H, W, 2)), norm="ortho"))
         dimg, dsens = sense_grad(ib, sb, gx, G, H, W, self.sense_scale, 1)
+        if self.prior is not None:  # every group's step carries the prior with its full weight
+            loss = loss + self._add_prior(ib, dimg, H, W)
         self.engine.backward(self._img_in, self.enc_B, dimg)
         self.sens_engine.backward(xs, self.sens_enc_B, dsens)
         for eng in (self.engine, self.sens_engine):
             eng.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
         self.global_step += 1
         return loss
+
+    def _add_prior(self, ib: torch.Tensor, dimg: torch.Tensor, H: int, W: int) -> torch.Tensor:
+        """weight * dTV/dI of the image network's output ``ib`` added into ``dimg`` (inr_image_tv_grad, accumulate);
+        returns weight * TV, a view of the prior's resident loss_out buffer.  The prior acts on I, not on scale * I."""
+        from .sense_prior import image_tv
+        return image_tv(ib, H, W, self.prior["weight"], self.prior["eps"], dimg=dimg, accumulate=True,
+                        loss_out=self._prior_out)
 
     # ---- validation ------------------------------------------------------------------------------
     def _sweep(self, engine, enc_B, rows: torch.Tensor, chunk: int, encoder) -> torch.Tensor:
@@ -420,6 +452,10 @@ class SenseFitTrainer(ResidentFit):
         chunk = int(chunk or self.predict_chunk)
         C_, H, W = (int(v) for v in self.shape[:3])
         img = self._sweep(self.engine, self.enc_B, self._img_coords, chunk, self.encoder)
+        if self.prior is not None:  # the prior's value on the swept image: no gradient, one host read
+            from .sense_prior import image_tv
+            value = image_tv(img, H, W, self.prior["weight"], self.prior["eps"], loss_out=self._prior_out)
+            self._last_prior = dict(self.prior, value=float(value))
         out = torch.empty(C_, H, W, 2, device=self.device)
         if self.calib is not None:  # the same sweep through the resident maps
             for c0, c1 in self.groups:
@@ -457,6 +493,8 @@ class SenseFitTrainer(ResidentFit):
     def validate(self, epoch: int) -> dict:
         rec = self._validated(epoch, self._predict_raw())
         rec["sense"] = self._last_sense
+        if self.prior is not None:
+            rec["prior"] = self._last_prior
         if self.cg_sense is not None:
             rec["cg_sense"] = self.cg_sense
         return rec
@@ -465,6 +503,8 @@ class SenseFitTrainer(ResidentFit):
     def metrics(self) -> dict:
         rec = super().metrics()
         rec["sense"] = self._last_sense
+        if self.prior is not None:
+            rec["prior"] = self._last_prior
         if self.cg_sense is not None:
             rec["cg_sense"] = self.cg_sense
         return rec
@@ -511,10 +551,14 @@ class SenseFitTrainer(ResidentFit):
     def _sense_state(self) -> dict:
         if self.calib is not None:
             from .sense_calib import calibrated_state
-            return calibrated_state(self.sense_scale, self.coils_per_step, self.calib["calib"], self._block)
-        return {"scale": self.sense_scale, "coils_per_step": self.coils_per_step,
-                "enc_B": None if self.sens_encoder.B is None else self.sens_encoder.B.clone(),
-                "net": dict(self.settings["net"]), "encoder": dict(self.settings["encoder"])}
+            state = calibrated_state(self.sense_scale, self.coils_per_step, self.calib["calib"], self._block)
+        else:
+            state = {"scale": self.sense_scale, "coils_per_step": self.coils_per_step,
+                     "enc_B": None if self.sens_encoder.B is None else self.sens_encoder.B.clone(),
+                     "net": dict(self.settings["net"]), "encoder": dict(self.settings["encoder"])}
+        if self.prior is not None:  # a record only: resuming under another weight is allowed, as for lr
+            state["prior"] = dict(self.prior)
+        return state
 
     def checkpoint(self) -> dict:
         """{'net', 'enc', 'opt'} in the reference's layout -- 'net' with 'image.*' then 'sens.*' keys, 'enc' the image
@@ -576,13 +620,18 @@ def add_sense_flags(ap) -> None:
     ap.add_argument("--sense-maps", type=str, default=None, metavar="ARG",
                     help="learned | calibrated (config['sense']['maps']): coil maps from a second network, or estimated "
                          "once from the fully sampled centre of k-space and fixed")
+    ap.add_argument("--sense-prior", type=str, default=None, metavar="ARG",
+                    help="none | tv:WEIGHT[:EPS] (config['sense']['prior']): smoothed isotropic total variation of the "
+                         "image network's output, added to every step's loss with this weight (eps defaults to 1e-3)")
     ap.add_argument("--sense-baseline", type=str, default=None, metavar="ARG",
                     help="none | cg-N (config['sense']['baseline']; with calibrated maps): CG-SENSE from the same maps and "
                          "samples, scored as the fit is")
 
 
 def apply_sense_flags(config: dict, opts) -> dict:
-    for key, value in (("maps", opts.sense_maps), ("baseline", opts.sense_baseline)):
+    from .sense_prior import parse_prior_flag
+    prior = parse_prior_flag(getattr(opts, "sense_prior", None))
+    for key, value in (("maps", opts.sense_maps), ("baseline", opts.sense_baseline), ("prior", prior)):
         if value is not None:
             config["sense"] = dict(config.get("sense") or {}, **{key: value})
     return config
