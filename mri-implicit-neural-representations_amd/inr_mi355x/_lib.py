@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INR_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libinr_mi355x.so")
 
@@ -216,6 +218,13 @@ def last_error() -> str:
 # hyperparameter search may record such a trial as a harmless refusal.  An entry that can fail after it has launched
 # something must return another code.
 ERR_UNSUPPORTED = -2
+
+
+def launch(name: str, device, *args) -> None:
+    """One asynchronous entry of the library on ``device``: ``args`` are the entry's arguments without its last, the
+    stream -- the call is made with ``device`` current and torch's current stream of that device, and checked."""
+    with torch.cuda.device(device):
+        check(getattr(load(), name)(*args, torch.cuda.current_stream(device).cuda_stream))
 
 
 def check(rc: int) -> None:

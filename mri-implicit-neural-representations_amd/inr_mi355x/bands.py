@@ -150,11 +150,9 @@ def band_stats_device(dist, gt, pred=None, mask=None, mask_select=1, bounds=()):
                          torch.empty(scratch_doubles(n, K), device=device, dtype=torch.float64))
     stats, scratch = _scratch[key]
     FP = C.POINTER(C.c_float)
-    with torch.cuda.device(device):
-        L.check(L.load().inr_band_stats(
-            dist.data_ptr(), gt.data_ptr(), None if pred is None else pred.data_ptr(),
-            None if mask is None else mask.data_ptr(), int(mask_select), n, lo.ctypes.data_as(FP), hi.ctypes.data_as(FP),
-            K, stats.data_ptr(), scratch.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
+    L.launch("inr_band_stats", device, dist.data_ptr(), gt.data_ptr(), None if pred is None else pred.data_ptr(),
+             None if mask is None else mask.data_ptr(), int(mask_select), n, lo.ctypes.data_as(FP), hi.ctypes.data_as(FP),
+             K, stats.data_ptr(), scratch.data_ptr())
     return lo, hi, stats
 
 

@@ -3,7 +3,8 @@ train_kspace_multiscale.py, with ``'opt'`` in ``torch.optim.Adam.state_dict()`` 
 position of the parameter in ``model.parameters()``; frozen / never-stepped parameters have no entry), and the
 ``config["pretrain"]`` resume path of train.py:117-121.
 """
-from typing import Optional
+from collections import OrderedDict
+from typing import Callable, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -30,6 +31,64 @@ def optimizer_state(model, engine, config: dict) -> dict:
              "weight_decay": config["weight_decay"], "amsgrad": False, "maximize": False, "foreach": None,
              "capturable": False, "differentiable": False, "fused": None, "params": list(range(n_params))}
     return {"state": state, "param_groups": [group]}
+
+
+class Part(NamedTuple):
+    """One network of a fit that drives several under one Adam: its key prefix in 'net', the model, its engine, the
+    encoder that travels with it (or None) and what to call when a checkpoint replaced that encoder's matrix."""
+    prefix: str
+    model: object
+    engine: object
+    encoder: object = None
+    rebind: Optional[Callable] = None
+
+
+def joined_net(parts: Sequence[Part]) -> OrderedDict:
+    """'net' of several networks: prefix + key of every part's state_dict, in part order (clones: a checkpoint must not
+    alias the running weights)"""
+    return OrderedDict((p.prefix + k, v.detach().clone()) for p in parts for k, v in p.model.state_dict().items())
+
+
+def joined_optimizer_state(parts: Sequence[Part], config: dict) -> dict:
+    """'opt' of ONE Adam over the parts' parameters in part order: every part's optimizer_state with its indices moved
+    behind the parameters of the parts in front of it, and one param group over all of them."""
+    opt, base = None, 0
+    for p in parts:
+        part = optimizer_state(p.model, p.engine, config)
+        if opt is None:
+            opt = part
+        else:
+            opt["state"].update({j + base: st for j, st in part["state"].items()})
+        base += len(part["param_groups"][0]["params"])
+    opt["param_groups"][0]["params"] = list(range(base))
+    return opt
+
+
+def split_prefixed(net_state: dict, prefixes: Sequence[str]) -> list:
+    """[state_dict per prefix] of a joined 'net', the prefix cut off; ValueError for keys under none of them"""
+    other = [k for k in net_state if not k.startswith(tuple(prefixes))]
+    if other:
+        raise ValueError(f"keys outside {' / '.join(repr(p) for p in prefixes)}: {other[:4]}")
+    return [OrderedDict((k[len(p):], v) for k, v in net_state.items() if k.startswith(p)) for p in prefixes]
+
+
+def load_parts(parts: Sequence[Part], nets: Sequence[dict], encs: Sequence, opt: Optional[dict],
+               weights_only: bool = False) -> None:
+    """The inverse of joined_net / joined_optimizer_state: ``nets`` the parts' state_dicts (already split), ``encs`` the
+    encoder matrix that goes with each (None: none), ``opt`` the joined 'opt', cut by the running count of
+    model.parameters().  ``weights_only``: load_weights and a re-pack, no optimizer state (a reconstruction's path)."""
+    if not len(parts) == len(nets) == len(encs):
+        raise ValueError(f"{len(parts)} parts, {len(nets)} state dicts and {len(encs)} encoder matrices")
+    base = 0
+    for p, net, enc in zip(parts, nets, encs):
+        n = len(list(p.model.parameters()))
+        if weights_only:
+            load_weights(p.model, p.encoder, {"net": net, "enc": enc}, p.rebind)
+            p.engine.pack()
+        else:
+            sub = {"state": {j - base: st for j, st in opt["state"].items() if base <= j < base + n}} if opt else None
+            load_dict(p.model, p.encoder, p.engine, {"net": net, "enc": enc, "opt": sub}, p.rebind)
+        base += n
 
 
 def save_dict(model, encoder, engine, config: dict) -> dict:

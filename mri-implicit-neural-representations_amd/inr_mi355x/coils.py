@@ -160,9 +160,7 @@ def coil_gram_device(data: torch.Tensor, shape) -> torch.Tensor:
         _scratch[key] = (torch.empty(coils, coils, 2, device=x.device, dtype=torch.float64),
                          torch.empty(scratch_doubles(coils, n), device=x.device, dtype=torch.float64))
     gram, scratch = _scratch[key]
-    with torch.cuda.device(x.device):
-        L.check(L.load().inr_coil_gram(x.data_ptr(), coils, n, gram.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                       torch.cuda.current_stream(x.device).cuda_stream))
+    L.launch("inr_coil_gram", x.device, x.data_ptr(), coils, n, gram.data_ptr(), scratch.data_ptr(), scratch.numel())
     return gram
 
 
@@ -189,9 +187,7 @@ def coil_apply(data: torch.Tensor, A, shape) -> torch.Tensor:
         raise ValueError("coil_apply of no pixels")
     a_dev = torch.from_numpy(_pairs(Ac, np.float32)).to(x.device).contiguous()  # [M, K, 2] row-major
     out = torch.empty(M, n, 2, device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        L.check(L.load().inr_coil_apply(x.data_ptr(), a_dev.data_ptr(), M, coils, n, out.data_ptr(),
-                                        torch.cuda.current_stream(x.device).cuda_stream))
+    L.launch("inr_coil_apply", x.device, x.data_ptr(), a_dev.data_ptr(), M, coils, n, out.data_ptr())
     return out
 
 

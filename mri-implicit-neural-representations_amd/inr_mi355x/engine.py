@@ -48,6 +48,11 @@ class LossSpec:
         return LossSpec(kinds[name], float(opts.get("hdr_eps", 1e-3)), float(opts.get("hdr_ff_sigma", 2.0)),
                         float(opts.get("hdr_ff_factor", 0.5)), int(opts.get("min_sample", 3000)))
 
+    def desc(self, inv_count: float, hdr_A: float = 0.0) -> L.LossDesc:
+        """the inr_loss_desc of a pointwise loss call whose mean is over 1 / inv_count rows"""
+        return L.LossDesc(kind=self.kind, eps=self.eps, sigma=self.sigma, factor=self.factor, inv_count=inv_count,
+                          hdr_A=hdr_A)
+
 
 def _shape(t: Optional[torch.Tensor], name: str, *shape) -> None:
     """Raise unless ``t`` has exactly this shape (the kernels index by these extents: a short tensor would be an
@@ -64,6 +69,13 @@ def _ptr(t: Optional[torch.Tensor], name: str, dtype=torch.float32) -> Optional[
     if t.dtype != dtype or not t.is_contiguous():
         raise RuntimeError(f"{name} must be a contiguous {dtype} tensor (got {t.dtype}, contiguous={t.is_contiguous()})")
     return t.data_ptr()
+
+
+def _same_device(ref: torch.Tensor, **tensors) -> None:
+    """Raise unless every given tensor (None: not given) is on the device of ``ref``, the call's first tensor"""
+    for name, t in tensors.items():
+        if t is not None and t.device != ref.device:
+            raise RuntimeError(f"{name} is on {t.device}, the call's first tensor on {ref.device}")
 
 
 def sharded_exchange(gbuf_pad: torch.Tensor, gchunk: torch.Tensor, pchunk: torch.Tensor, pgather: torch.Tensor,
@@ -263,8 +275,7 @@ class MLPEngine:
         return self.grads
 
     def loss_desc(self, spec: LossSpec, count: int, hdr_A: float = 0.0) -> L.LossDesc:
-        return L.LossDesc(kind=spec.kind, eps=spec.eps, sigma=spec.sigma, factor=spec.factor,
-                          inv_count=1.0 / float(count), hdr_A=hdr_A)
+        return spec.desc(1.0 / float(count), hdr_A)
 
     def loss_grad(self, spec: LossSpec, out: torch.Tensor, gt: torch.Tensor, count: int,
                   mask: Optional[torch.Tensor] = None, hdr_A: float = 0.0):

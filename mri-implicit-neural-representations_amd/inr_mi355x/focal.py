@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import _ptr, _shape
+from .engine import _ptr, _same_device, _shape
 
 KEYS = ("ffl_alpha", "ffl_log_matrix", "ffl_weight")
 
@@ -154,13 +154,9 @@ def focal_loss_grad(spec: FocalSpec, out: torch.Tensor, gt: torch.Tensor, count:
         loss_out = torch.zeros(L.LOSS_WORDS, device=out.device)
     _shape(loss_out, "loss_out", L.LOSS_WORDS)
     p_loss = _ptr(loss_out, "loss_out")
-    for t in (gt, mask, loss_out):
-        if t is not None and t.device != out.device:
-            raise RuntimeError(f"tensors on {t.device} and {out.device}")
+    _same_device(out, gt=gt, mask=mask, loss_out=loss_out)
     dout = torch.empty_like(out) if want_grad else None
     d = L.FocalDesc(alpha=spec.alpha, log_matrix=int(spec.log_matrix), loss_weight=spec.loss_weight,
                     inv_count=1.0 / float(count))
-    with torch.cuda.device(out.device):
-        L.check(L.load().inr_focal_loss_grad(C.byref(d), p_out, p_gt, p_mask, B, p_loss, _ptr(dout, "dout"),
-                                             torch.cuda.current_stream(out.device).cuda_stream))
+    L.launch("inr_focal_loss_grad", out.device, C.byref(d), p_out, p_gt, p_mask, B, p_loss, _ptr(dout, "dout"))
     return loss_out[0], dout

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import LossSpec, _ptr, _shape
+from .engine import LossSpec, _ptr, _same_device, _shape
 
 
 def gain_inputs(coords: torch.Tensor) -> torch.Tensor:
@@ -97,10 +97,6 @@ def gain_loss_grad_numpy(loss: LossSpec, y, s, gt, mask, count: int, hdr_A: floa
 
 
 # ---- the kernels -------------------------------------------------------------------------------------------------------
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def gain_loss_grad(loss: LossSpec, y: torch.Tensor, s: torch.Tensor, gt: torch.Tensor, count: int,
                    mask: Optional[torch.Tensor] = None, hdr_A: float = 0.0, want_res: bool = True,
                    loss_out: Optional[torch.Tensor] = None):
@@ -115,16 +111,12 @@ def gain_loss_grad(loss: LossSpec, y: torch.Tensor, s: torch.Tensor, gt: torch.T
         loss_out = torch.zeros(L.LOSS_WORDS, device=y.device)
     _shape(loss_out, "loss_out", L.LOSS_WORDS)
     ins = (_ptr(y, "y"), _ptr(s, "s"), _ptr(gt, "gt"), _ptr(mask, "mask", torch.uint8), _ptr(loss_out, "loss_out"))
-    for t in (s, gt, mask, loss_out):
-        if t is not None and t.device != y.device:
-            raise RuntimeError(f"tensors on {t.device} and {y.device}")
+    _same_device(y, s=s, gt=gt, mask=mask, loss_out=loss_out)
     dy, ds = torch.empty_like(y), torch.empty_like(s)
     res = torch.empty_like(y) if want_res else None
-    ld = L.LossDesc(kind=loss.kind, eps=loss.eps, sigma=loss.sigma, factor=loss.factor, inv_count=1.0 / float(count),
-                    hdr_A=hdr_A)
-    with torch.cuda.device(y.device):
-        L.check(L.load().inr_gain_loss_grad(C.byref(ld), ins[0], ins[1], ins[2], ins[3], B, _ptr(res, "res"), ins[4],
-                                            _ptr(dy, "dy"), _ptr(ds, "ds"), _stream(y)))
+    ld = loss.desc(1.0 / float(count), hdr_A)
+    L.launch("inr_gain_loss_grad", y.device, C.byref(ld), ins[0], ins[1], ins[2], ins[3], B, _ptr(res, "res"), ins[4],
+             _ptr(dy, "dy"), _ptr(ds, "ds"))
     return loss_out[0], res, dy, ds
 
 
@@ -134,12 +126,9 @@ def gain_apply(y: torch.Tensor, s: torch.Tensor, out: Optional[torch.Tensor] = N
     _shape(y, "y", B, 2)
     _shape(s, "s", B)
     py, ps = _ptr(y, "y"), _ptr(s, "s")
-    if s.device != y.device:
-        raise RuntimeError(f"s is on {s.device}, y on {y.device}")
+    _same_device(y, s=s)
     res = torch.empty_like(y) if out is None else out
     _shape(res, "out", B, 2)
-    if res.device != y.device:
-        raise RuntimeError(f"out is on {res.device}, y on {y.device}")
-    with torch.cuda.device(y.device):
-        L.check(L.load().inr_gain_apply(py, ps, B, _ptr(res, "out"), _stream(y)))
+    _same_device(y, out=res)
+    L.launch("inr_gain_apply", y.device, py, ps, B, _ptr(res, "out"))
     return res

@@ -166,9 +166,7 @@ def grid_rows(spec: GridSpec, lo: int, hi: int, coords_out: Optional[torch.Tenso
     cp = coords_out.data_ptr() or None
     if cp is None and rows == 0:
         cp = torch.empty(4, device=device).data_ptr()
-    with torch.cuda.device(device):
-        L.check(L.load().inr_grid_rows(d, lo, n, cp, None if dist is None else (dist.data_ptr() or None),
-                                       torch.cuda.current_stream(device).cuda_stream))
+    L.launch("inr_grid_rows", device, d, lo, n, cp, None if dist is None else (dist.data_ptr() or None))
     return coords_out, dist
 
 

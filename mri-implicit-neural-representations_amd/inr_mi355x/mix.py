@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import LossSpec, _ptr, _shape
+from .engine import LossSpec, _ptr, _same_device, _shape
 from .gain import loss_rows_float64
 
 MAX_HEADS = L.MIX_MAX_HEADS
@@ -138,10 +138,6 @@ def mix_loss_grad_numpy(loss: LossSpec, ys: Sequence[np.ndarray], w, gt, dist, m
 
 
 # ---- the kernels -------------------------------------------------------------------------------------------------------
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _desc(ys: Sequence[torch.Tensor], dys: Optional[Sequence[torch.Tensor]], radii: Optional[Sequence[float]],
           inv: Optional[Sequence[float]], detach: bool, clamp: bool) -> L.MixDesc:
     K = _check_heads(len(ys))
@@ -150,8 +146,7 @@ def _desc(ys: Sequence[torch.Tensor], dys: Optional[Sequence[torch.Tensor]], rad
     for k, y in enumerate(ys):
         _shape(y, f"y[{k}]", B, 2)
         d.y[k] = _ptr(y, f"y[{k}]")
-        if y.device != ys[0].device:
-            raise RuntimeError(f"y[{k}] is on {y.device}, y[0] on {ys[0].device}")
+        _same_device(ys[0], **{f"y[{k}]": y})
         if dys is not None:
             d.dy[k] = _ptr(dys[k], f"dy[{k}]")
     if radii is not None:
@@ -181,19 +176,14 @@ def mix_loss_grad(loss: LossSpec, ys: Sequence[torch.Tensor], w: torch.Tensor, g
     if loss_out is None:
         loss_out = torch.zeros(L.LOSS_WORDS, device=dev)
     _shape(loss_out, "loss_out", L.LOSS_WORDS)
-    for t in (w, gt, dist, mask, loss_out):
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"tensors on {t.device} and {dev}")
+    _same_device(ys[0], w=w, gt=gt, dist=dist, mask=mask, loss_out=loss_out)
     dys = [torch.empty_like(y) for y in ys]
     dw = torch.empty_like(w)
     res = torch.empty_like(ys[0]) if want_res else None
     d = _desc(ys, dys, radii, inv_count, detach, clamp)
-    ld = L.LossDesc(kind=loss.kind, eps=loss.eps, sigma=loss.sigma, factor=loss.factor, inv_count=float(inv_count[0]),
-                    hdr_A=hdr_A)
-    with torch.cuda.device(dev):
-        L.check(L.load().inr_mix_loss_grad(C.byref(ld), C.byref(d), _ptr(w, "w"), _ptr(gt, "gt"), _ptr(dist, "dist"),
-                                           _ptr(mask, "mask", torch.uint8), B, _ptr(res, "res"),
-                                           _ptr(loss_out, "loss_out"), _ptr(dw, "dw"), _stream(w)))
+    ld = loss.desc(float(inv_count[0]), hdr_A)
+    L.launch("inr_mix_loss_grad", dev, C.byref(ld), C.byref(d), _ptr(w, "w"), _ptr(gt, "gt"), _ptr(dist, "dist"),
+             _ptr(mask, "mask", torch.uint8), B, _ptr(res, "res"), _ptr(loss_out, "loss_out"), _ptr(dw, "dw"))
     return loss_out, res, dys, dw
 
 
@@ -206,10 +196,7 @@ def mix_apply(ys: Sequence[torch.Tensor], w: torch.Tensor, clamp: bool = True,
     pw = _ptr(w, "w")
     res = torch.empty_like(ys[0]) if out is None else out
     _shape(res, "out", B, 2)
-    for t, name in ((w, "w"), (res, "out")):
-        if t.device != ys[0].device:
-            raise RuntimeError(f"{name} is on {t.device}, y[0] on {ys[0].device}")
+    _same_device(ys[0], w=w, out=res)
     d = _desc(ys, None, None, None, True, clamp)
-    with torch.cuda.device(w.device):
-        L.check(L.load().inr_mix_apply(C.byref(d), pw, B, _ptr(res, "out"), _stream(w)))
+    L.launch("inr_mix_apply", w.device, C.byref(d), pw, B, _ptr(res, "out"))
     return res

@@ -52,7 +52,7 @@ class Reconstructor:
     def __init__(self, config: dict, checkpoint, shape, device="cuda", radii: Optional[Sequence[float]] = None):
         from .networks import Positional_Encoder
         from .train import MFN_MODELS, MODELS
-        from .trainer_base import mfn_engine, set_default_configs
+        from .trainer_base import mfn_engine, mlp_engine, set_default_configs
         config = set_default_configs(dict(config))
         self.config = config
         name = config["model"]
@@ -84,13 +84,9 @@ class Reconstructor:
         self.takes_dist = self.multiscale or name == "KGabor"  # forward(x, dist_to_center) in the reference
         if self.is_mfn:
             self.engine, self.enc_B = mfn_engine(self.model, self.encoder, emb)
-        elif emb == "gauss":
-            self.engine = self.model.fused_engine(config["encoder"]["embedding_size"],
-                                                  **({"precision": config["precision"]} if "precision" in config else {}))
-            self.enc_B = self.encoder.B.contiguous()
         else:
-            self.engine = self.model._engine()
-            self.enc_B = None
+            self.engine, self.enc_B = mlp_engine(self.model, self.encoder, config["encoder"],
+                                                   **{k: config[k] for k in ("precision",) if k in config})
         self.engine.drop_training_state()  # forward only: no gradient buffer, no Adam moments
         # a learned-gain fit (train_scaling.py): 'net' holds a ScalerWrapper's keys, and the gain network's
         # size is read from them
@@ -125,7 +121,7 @@ class Reconstructor:
                                      network_depth=len(weights))).to(self.device)
             self.expert_engines = [self.engine]
             for m in self.experts[1:]:
-                eng = m.fused_engine(config["encoder"]["embedding_size"]) if emb == "gauss" else m._engine()
+                eng = mlp_engine(m, self.encoder, config["encoder"])[0]
                 eng.drop_training_state()
                 self.expert_engines.append(eng)
             self.gate_engine = self.gate._engine()
@@ -162,16 +158,13 @@ class Reconstructor:
         elif has_sense_keys(checkpoint.get("net", {})):
             from .networks import FFN
             weights = [v for k, v in split_sense(checkpoint["net"])[1].items() if k.endswith(".weight")]
+            sens_enc = sens_encoder_config(meta, config["encoder"])
             with torch.random.fork_rng(devices=[]):
-                self.sens_encoder = Positional_Encoder(sens_encoder_config(meta, config["encoder"]), device=self.device)
+                self.sens_encoder = Positional_Encoder(sens_enc, device=self.device)
                 self.sens_model = FFN({"network_input_size": int(weights[0].shape[1]), "network_output_size": 2,
                                        "network_width": int(weights[0].shape[0]),
                                        "network_depth": len(weights)}).to(self.device)
-            if emb == "gauss":
-                self.sens_engine = self.sens_model.fused_engine(int(meta["encoder"]["embedding_size"]))
-                self.sens_enc_B = self.sens_encoder.B.contiguous()
-            else:
-                self.sens_engine = self.sens_model._engine()
+            self.sens_engine, self.sens_enc_B = mlp_engine(self.sens_model, self.sens_encoder, sens_enc)
             self.sens_engine.drop_training_state()
             self.sense_scale = float(meta["scale"])
             self.renders_images = True
@@ -193,9 +186,27 @@ class Reconstructor:
         if self.sens_enc_B is not None:
             self.sens_enc_B = enc.B.contiguous()
 
+    def _parts(self):
+        """the part list of the trainer that wrote the checkpoint, over this Reconstructor's networks"""
+        from .checkpoint import Part
+        from .sense import IMAGE_PREFIX, SENS_PREFIX
+        from .train_multihead import GATE_PREFIX, HEAD_PREFIX
+        from .train_scaling import PREFIXES
+        first = (self.model, self.engine, self.encoder, self._rebind_encoder)
+        if self.experts is not None:
+            heads = [Part(f"{HEAD_PREFIX}{k}.", m, e) for k, (m, e) in enumerate(zip(self.experts, self.expert_engines))]
+            heads[0] = Part(heads[0].prefix, *first)  # the encoder travels with expert 0
+            return heads + [Part(GATE_PREFIX, self.gate, self.gate_engine)]
+        if self.sens_model is not None:
+            return [Part(IMAGE_PREFIX, *first),
+                    Part(SENS_PREFIX, self.sens_model, self.sens_engine, self.sens_encoder, self._rebind_sens_encoder)]
+        if self.scaler is not None:
+            return [Part(PREFIXES[0], *first), Part(PREFIXES[1], self.scaler, self.scaler_engine)]
+        return [Part(IMAGE_PREFIX if self.sense_block is not None else "", *first)]
+
     def load(self, checkpoint) -> None:
         """ckpt['net'] and ckpt['enc'] (checkpoint.load_weights); ckpt['opt'] is not read."""
-        from .checkpoint import load_weights
+        from .checkpoint import load_parts
         if not isinstance(checkpoint, dict):
             checkpoint = torch.load(checkpoint, map_location=self.device)
         if "net" not in checkpoint:
@@ -211,36 +222,25 @@ class Reconstructor:
         if checkpoint.get("ring_normalization") is not None:
             from .ringnorm import RingTable
             self.ring_table = RingTable.from_state(checkpoint["ring_normalization"])
+        net, encs = checkpoint["net"], [checkpoint.get("enc")]
         if self.experts is not None:
             from .train_multihead import split_state as split_heads
-            heads, gate = split_heads(checkpoint["net"])
+            heads, gate = split_heads(net)
             if len(heads) != len(self.experts):
                 raise ValueError(f"the checkpoint has {len(heads)} heads, this Reconstructor {len(self.experts)}")
-            for k, (m, eng) in enumerate(zip(self.experts, self.expert_engines)):
-                load_weights(m, self.encoder if k == 0 else None,
-                             {"net": heads[k], "enc": checkpoint.get("enc") if k == 0 else None}, self._rebind_encoder)
-                eng.pack()
-            load_weights(self.gate, None, {"net": gate})
-            self.gate_engine.pack()
+            nets = heads + [gate]
         elif self.sense_block is not None:
             from .sense_calib import image_net_of
-            load_weights(self.model, self.encoder, {"net": image_net_of(checkpoint["net"]), "enc": checkpoint.get("enc")}, self._rebind_encoder)
+            nets = [image_net_of(net)]
         elif self.sens_model is not None:
             from .sense import split_state as split_sense
-            img, sen = split_sense(checkpoint["net"])
-            load_weights(self.model, self.encoder, {"net": img, "enc": checkpoint.get("enc")}, self._rebind_encoder)
-            load_weights(self.sens_model, self.sens_encoder, {"net": sen, "enc": checkpoint["sense"].get("enc_B")},
-                         self._rebind_sens_encoder)
-            self.sens_engine.pack()
+            nets, encs = split_sense(net), encs + [checkpoint["sense"].get("enc_B")]
         elif self.scaler is not None:
             from .train_scaling import split_state
-            back, scal = split_state(checkpoint["net"])
-            load_weights(self.model, self.encoder, {"net": back, "enc": checkpoint.get("enc")}, self._rebind_encoder)
-            load_weights(self.scaler, None, {"net": scal})
-            self.scaler_engine.pack()
+            nets = split_state(net)
         else:
-            load_weights(self.model, self.encoder, checkpoint, self._rebind_encoder)
-        self.engine.pack()
+            nets = [net]
+        load_parts(self._parts(), nets, encs + [None] * (len(nets) - len(encs)), None, weights_only=True)
 
     @torch.no_grad()
     def expand(self, pred: torch.Tensor) -> torch.Tensor:
@@ -263,9 +263,8 @@ class Reconstructor:
 
     def _forward_rows(self, coords: torch.Tensor, dist: Optional[torch.Tensor]) -> torch.Tensor:
         """[n,2]: the forward call of the trainers' _forward_chunk on these coordinates"""
-        x = coords
-        if self.enc_B is None and self.config["encoder"]["embedding"] != "none":
-            x = self.encoder.embedding(coords).contiguous()  # LogF: the filters / first layer read the encoded rows
+        from .trainer_base import _encoded
+        x = _encoded(self.encoder, self.enc_B, coords)  # LogF: the filters / first layer read the encoded rows
         if self.is_mfn:
             o = self.engine.forward(x, self.enc_B, save=False, dist=dist if self.takes_dist else None)
             return o[-1]  # the last head is the reconstruction (train_kspace_multiscale.py:225); single-scale: the only one
@@ -322,8 +321,8 @@ class Reconstructor:
         the sensitivity network on every row, in chunks of rows as the trainer's sweep.  Both networks live in image
         space, so a finer grid is genuine super-resolution.  kspace() gives the centred transform where it is wanted."""
         from .sense import sense_apply
+        from .trainer_base import _encoded
         n_coils, h, w = spec.shape
-        emb = self.config["encoder"]["embedding"]
 
         def sweep(engine, encoder, enc_B, grid, zero_coil):
             out = torch.empty(grid.rows, 2, device=self.device)
@@ -332,8 +331,7 @@ class Reconstructor:
                 c = grid_rows(grid, lo, hi, coords_out=cbuf[:hi - lo], with_dist=False)[0]
                 if zero_coil:
                     c[:, 0] = 0.0
-                x = c if enc_B is not None or emb == "none" else encoder.embedding(c).contiguous()
-                out[lo:hi] = engine.forward(x, enc_B, save=False)
+                out[lo:hi] = engine.forward(_encoded(encoder, enc_B, c), enc_B, save=False)
             return out
 
         plane = GridSpec(spec.coils_total, h, w, coils=spec.coils[:1], window=spec.window)

@@ -124,10 +124,8 @@ def ring_scale(dist: torch.Tensor, values: torch.Tensor, radii, divisors, out: O
         if out.shape[0] != n:
             raise RuntimeError(f"dist has {n} rows, out {out.shape[0]}")
     FP = C.POINTER(C.c_float)
-    with torch.cuda.device(dist.device):
-        L.check(L.load().inr_ring_scale(dist.data_ptr(), values.data_ptr(), out.data_ptr(), n, r32.ctypes.data_as(FP),
-                                        d32.ctypes.data_as(FP), int(d32.size),
-                                        torch.cuda.current_stream(dist.device).cuda_stream))
+    L.launch("inr_ring_scale", dist.device, dist.data_ptr(), values.data_ptr(), out.data_ptr(), n,
+             r32.ctypes.data_as(FP), d32.ctypes.data_as(FP), int(d32.size))
     return out
 
 
@@ -248,10 +246,8 @@ def radial_scale(dist: torch.Tensor, values: torch.Tensor, profile_dev: torch.Te
         out = _device_rows(out, "out", 2, dist.device, who=who)
         if out.shape[0] != n:
             raise RuntimeError(f"dist has {n} rows, out {out.shape[0]}")
-    with torch.cuda.device(dist.device):
-        L.check(L.load().inr_radial_scale(dist.data_ptr(), values.data_ptr(), out.data_ptr(), n, profile_dev.data_ptr(),
-                                          n_knots, float(r_lo), float(inv_step), 1 if multiply else 0,
-                                          torch.cuda.current_stream(dist.device).cuda_stream))
+    L.launch("inr_radial_scale", dist.device, dist.data_ptr(), values.data_ptr(), out.data_ptr(), n,
+             profile_dev.data_ptr(), n_knots, float(r_lo), float(inv_step), 1 if multiply else 0)
     return out
 
 

@@ -157,9 +157,8 @@ def row_cdf(w: torch.Tensor, mask: Optional[torch.Tensor] = None, scale: Optiona
     L.check(lib.inr_row_cdf_scratch(n, C.byref(words)))
     cdf = torch.empty(n, dtype=torch.int64, device=w.device)
     scratch = torch.empty(words.value, dtype=torch.int64, device=w.device)
-    with torch.cuda.device(w.device):
-        L.check(lib.inr_row_cdf(w.data_ptr(), mask_ptr, n, C.c_double(scale), cdf.data_ptr(), scratch.data_ptr(),
-                                words.value, torch.cuda.current_stream(w.device).cuda_stream))
+    L.launch("inr_row_cdf", w.device, w.data_ptr(), mask_ptr, n, C.c_double(scale), cdf.data_ptr(), scratch.data_ptr(),
+             words.value)
     zero = (cdf[1:] == cdf[:-1]).sum() + (cdf[0] == 0)
     total, zero = torch.stack((cdf[n - 1], zero)).tolist()
     if total == 0:
@@ -197,10 +196,8 @@ def sample_epoch(cdf: torch.Tensor, m: int, seed: int, epoch: int, *, coords=Non
             _dev(mask_out, "mask_out", torch.uint8, (m,), device),
             _dev(batch_counts, "batch_counts", torch.int32, (nb,), device),
             _dev(order_out, "order_out", torch.int64, (m,), device)]
-    with torch.cuda.device(device):
-        L.check(L.load().inr_sample_epoch(cdf.data_ptr(), n, m, int(batch_size), C.c_uint64(int(seed) & ((1 << 64) - 1)),
-                                          C.c_uint32(int(epoch) & _M32), *ptrs,
-                                          torch.cuda.current_stream(device).cuda_stream))
+    L.launch("inr_sample_epoch", device, cdf.data_ptr(), n, m, int(batch_size), C.c_uint64(int(seed) & ((1 << 64) - 1)),
+             C.c_uint32(int(epoch) & _M32), *ptrs)
 
 
 def device_draw(cdf: torch.Tensor, m: int, seed: int, epoch: int) -> torch.Tensor:

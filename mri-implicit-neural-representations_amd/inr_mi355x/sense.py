@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import LossSpec, _ptr, _shape
+from .engine import LossSpec, _ptr, _same_device, _shape
 
 
 IMAGE_PREFIX, SENS_PREFIX = "image.", "sens."
@@ -37,21 +37,17 @@ def has_sense_keys(net_state: dict) -> bool:
 
 def join_state(image_state: dict, sens_state: dict) -> OrderedDict:
     """'image.' + the image network's keys, then 'sens.' + the sensitivity network's (clones: a checkpoint must not alias
-    the running weights)"""
-    net = OrderedDict()
-    for prefix, sd in ((IMAGE_PREFIX, image_state), (SENS_PREFIX, sens_state)):
-        for k, v in sd.items():
-            net[prefix + k] = v.detach().clone()
-    return net
+    the running weights).  Kept for callers outside the package: the trainer writes the same keys through
+    checkpoint.joined_net over its _parts()."""
+    return OrderedDict((prefix + k, v.detach().clone()) for prefix, sd in ((IMAGE_PREFIX, image_state),
+                                                                          (SENS_PREFIX, sens_state))
+                       for k, v in sd.items())
 
 
 def split_state(net_state: dict):
     """(image network state_dict, sensitivity network state_dict) of join_state's"""
-    other = [k for k in net_state if not k.startswith((IMAGE_PREFIX, SENS_PREFIX))]
-    if other:
-        raise ValueError(f"keys outside '{IMAGE_PREFIX}' / '{SENS_PREFIX}': {other[:4]}")
-    img = OrderedDict((k[len(IMAGE_PREFIX):], v) for k, v in net_state.items() if k.startswith(IMAGE_PREFIX))
-    sen = OrderedDict((k[len(SENS_PREFIX):], v) for k, v in net_state.items() if k.startswith(SENS_PREFIX))
+    from .checkpoint import split_prefixed
+    img, sen = split_prefixed(net_state, (IMAGE_PREFIX, SENS_PREFIX))
     if not img or not sen:
         raise ValueError(f"a SENSE checkpoint holds both '{IMAGE_PREFIX}' and '{SENS_PREFIX}' keys")
     return img, sen
@@ -157,16 +153,6 @@ def sense_chain_numpy(img, sens, gt, mask, loss: LossSpec, count: int, G: int, H
 
 
 # ---- the kernels -------------------------------------------------------------------------------------------------------
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _same_device(ref: torch.Tensor, **tensors) -> None:
-    for name, t in tensors.items():
-        if t.device != ref.device:
-            raise RuntimeError(f"{name} is on {t.device}, img on {ref.device}")
-
-
 def sense_apply(img: torch.Tensor, sens: torch.Tensor, G: int, H: int, W: int, scale: float, shift: int = 1,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """inr_sense_apply on device tensors img [H*W,2], sens [G*H*W,2] -> x [G,H,W,2] (``out`` when given): the coil images
@@ -177,8 +163,7 @@ def sense_apply(img: torch.Tensor, sens: torch.Tensor, G: int, H: int, W: int, s
     _shape(x, "out", G, H, W, 2)
     pi, ps, px = _ptr(img, "img"), _ptr(sens, "sens"), _ptr(x, "out")
     _same_device(img, sens=sens, out=x)
-    with torch.cuda.device(img.device):
-        L.check(L.load().inr_sense_apply(pi, ps, G, H, W, float(scale), int(shift), px, _stream(img)))
+    L.launch("inr_sense_apply", img.device, pi, ps, G, H, W, float(scale), int(shift), px)
     return x
 
 
@@ -194,7 +179,5 @@ def sense_grad(img: torch.Tensor, sens: torch.Tensor, gx: torch.Tensor, G: int, 
     _shape(dsens, "dsens", G * H * W, 2)
     ptrs = (_ptr(img, "img"), _ptr(sens, "sens"), _ptr(gx, "gx"), _ptr(dimg, "dimg"), _ptr(dsens, "dsens"))
     _same_device(img, sens=sens, gx=gx, dimg=dimg, dsens=dsens)
-    with torch.cuda.device(img.device):
-        L.check(L.load().inr_sense_grad(ptrs[0], ptrs[1], ptrs[2], G, H, W, float(scale), int(shift), ptrs[3], ptrs[4],
-                                        _stream(img)))
+    L.launch("inr_sense_grad", img.device, ptrs[0], ptrs[1], ptrs[2], G, H, W, float(scale), int(shift), ptrs[3], ptrs[4])
     return dimg, dsens

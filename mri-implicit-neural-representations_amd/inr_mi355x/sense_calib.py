@@ -24,8 +24,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import _ptr, _shape
-from .sense import _c, _f32, _pairs, _same_device, _stream, fft2c_numpy, place_index, sense_apply, sense_apply_numpy
+from .engine import _ptr, _same_device, _shape
+from .sense import _c, _f32, _pairs, fft2c_numpy, place_index, sense_apply, sense_apply_numpy
 
 WINDOWS = ("hann", "none")
 CALIB_KEYS = ("size", "window", "floor", "acs")
@@ -81,7 +81,8 @@ def calibrated_state(scale: float, coils_per_step: int, calib: dict, block: torc
 
 
 def image_net_state(state_dict: dict):
-    """'image.' + the image network's keys (clones): the 'net' of a calibrated-maps checkpoint"""
+    """'image.' + the image network's keys (clones): the 'net' of a calibrated-maps checkpoint.  Kept for callers
+    outside the package: the trainer writes the same keys through checkpoint.joined_net over its one part."""
     from collections import OrderedDict
     from .sense import IMAGE_PREFIX
     return OrderedDict((IMAGE_PREFIX + k, v.detach().clone()) for k, v in state_dict.items())
@@ -377,8 +378,7 @@ def sense_lowres(kc: torch.Tensor, ey: torch.Tensor, ex: torch.Tensor, out: Opti
     _shape(out, "out", C, Ho, Wo, 2)
     ptrs = (_ptr(kc, "kc"), _ptr(ey, "ey"), _ptr(ex, "ex"), _ptr(out, "out"))
     _same_device(kc, ey=ey, ex=ex, out=out)
-    with torch.cuda.device(kc.device):
-        L.check(L.load().inr_sense_lowres(ptrs[0], ptrs[1], ptrs[2], C, a, b, Ho, Wo, ptrs[3], _stream(kc)))
+    L.launch("inr_sense_lowres", kc.device, ptrs[0], ptrs[1], ptrs[2], C, a, b, Ho, Wo, ptrs[3])
     return out
 
 
@@ -393,8 +393,7 @@ def sense_maps(low: torch.Tensor, C: int, P: int, floor: float = 0.0, maps: Opti
     _shape(rss, "rss", P)
     ptrs = (_ptr(low, "low"), _ptr(maps, "maps"), _ptr(rss, "rss"))
     _same_device(low, maps=maps, rss=rss)
-    with torch.cuda.device(low.device):
-        L.check(L.load().inr_sense_maps(ptrs[0], C, P, float(floor), ptrs[1], ptrs[2], _stream(low)))
+    L.launch("inr_sense_maps", low.device, ptrs[0], C, P, float(floor), ptrs[1], ptrs[2])
     return maps, rss
 
 
@@ -407,8 +406,7 @@ def sense_adjoint(sens: torch.Tensor, gx: torch.Tensor, G: int, H: int, W: int, 
     _shape(dimg, "dimg", H * W, 2)
     ptrs = (_ptr(sens, "sens"), _ptr(gx, "gx"), _ptr(dimg, "dimg"))
     _same_device(sens, gx=gx, dimg=dimg)
-    with torch.cuda.device(sens.device):
-        L.check(L.load().inr_sense_adjoint(ptrs[0], ptrs[1], G, H, W, float(scale), int(shift), ptrs[2], _stream(sens)))
+    L.launch("inr_sense_adjoint", sens.device, ptrs[0], ptrs[1], G, H, W, float(scale), int(shift), ptrs[2])
     return dimg
 
 

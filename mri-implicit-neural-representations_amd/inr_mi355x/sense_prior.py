@@ -23,8 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import _ptr, _shape
-from .sense import _f32, _same_device, _stream
+from .engine import _ptr, _same_device, _shape
+from .sense import _f32
 
 PRIOR_FIELDS = ("kind", "weight", "eps")
 PRIOR_KINDS = ("tv",)
@@ -167,7 +167,6 @@ def image_tv(img: torch.Tensor, H: int, W: int, weight: float, eps: float, dimg:
     pi, pd = _ptr(img, "img"), _ptr(dimg, "dimg")  # host tensors: no CPU fallback
     loss_out = torch.empty(L.LOSS_WORDS, device=img.device) if loss_out is None else loss_out
     pl = _ptr(loss_out, "loss_out")
-    _same_device(img, loss_out=loss_out, **({} if dimg is None else {"dimg": dimg}))
-    with torch.cuda.device(img.device):
-        L.check(L.load().inr_image_tv_grad(pi, H, W, float(weight), float(eps), int(bool(accumulate)), pl, pd, _stream(img)))
+    _same_device(img, loss_out=loss_out, dimg=dimg)
+    L.launch("inr_image_tv_grad", img.device, pi, H, W, float(weight), float(eps), int(bool(accumulate)), pl, pd)
     return loss_out[0]

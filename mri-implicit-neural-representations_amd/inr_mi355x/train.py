@@ -36,8 +36,8 @@ from .engine import LossSpec
 from .focal import focal_loss_grad
 from .mfn import FourierNet, GaborNet, KGaborNet
 from .networks import FFN, SIREN, WIRE, WIRE2D
-from .trainer_base import (ResidentFit, lr_factor, mfn_engine, run_epochs, set_default_configs,  # noqa: F401
-                           shard_rows)
+from .trainer_base import (ResidentFit, hdr_weight, lr_factor, mfn_engine, mlp_engine, run_epochs,  # noqa: F401
+                           set_default_configs, shard_rows)
 
 MODELS = {"SIREN": SIREN, "FFN": FFN, "WIRE": WIRE, "WIRE2D": WIRE2D,  # train.py:55-68
           "Fourier": FourierNet, "Gabor": GaborNet, "KGabor": KGaborNet}
@@ -127,13 +127,6 @@ def center_pair_rows(kcoords: torch.Tensor, min_sample: int, n_bands: int = 2):
         yield rows1[a].contiguous(), rows2[b].contiguous()
 
 
-def hdr_weight(kcoords: torch.Tensor, sigma: float) -> torch.Tensor:
-    """(1 - f)^2 per row, f the Gaussian of the k-space radius: the HDR / Center losses' A is its mean over a batch
-    (losses.py:241-242,258; SURVEY A.4 #17)."""
-    f = torch.exp(-(kcoords[:, 1] ** 2 + kcoords[:, 2] ** 2) / (2 * sigma ** 2))
-    return (1 - f) ** 2
-
-
 class INRTrainer(ResidentFit):
     def __init__(self, config: dict, image: torch.Tensor, coords: torch.Tensor, shape, device,
                  seed: int = 0, mask: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1,
@@ -160,13 +153,9 @@ class INRTrainer(ResidentFit):
             raise NotImplementedError("output_act in the fused training step (no shipped config sets it)")
         if self.is_mfn:
             self.engine, self.enc_B = mfn_engine(self.model, self.encoder, emb)
-        elif emb == "gauss":  # config["precision"]: "f32" (parity path, default) | "bf16" (throughput path)
-            self.engine = self.model.fused_engine(config["encoder"]["embedding_size"],
-                                                  **({"precision": config["precision"]} if "precision" in config else {}))
-            self.enc_B = self.encoder.B.contiguous()
-        else:
-            self.engine = self.model._engine()
-            self.enc_B = None
+        else:  # config["precision"]: "f32" (parity path, default) | "bf16" (throughput path)
+            self.engine, self.enc_B = mlp_engine(self.model, self.encoder, config["encoder"],
+                                                   **{k: config[k] for k in ("precision",) if k in config})
         self.sharded_update = wants_sharded_update(config, self.engine.n_params, world)
         if self.sharded_update:
             self.engine.enable_sharded_update(rank, world)
@@ -210,9 +199,7 @@ class INRTrainer(ResidentFit):
                 raise NotImplementedError("loss 'LSL' (CenterLoss) with an undersampling mask")
             if self.is_mfn or world > 1 or self.per_coil:
                 raise NotImplementedError("loss 'LSL' (CenterLoss): single-rank SIREN / FFN / WIRE fits on plain batches")
-        self._hdr_A = {}  # the HDR / Center scalar A per batch of the unshuffled data, and of the epoch buffers
-        self._hdr_A_epoch = []
-        self._hdr_A_train = {}  # ... and per batch of the off-grid training rows (config['trajectory'])
+        self._hdr_A_train = {}  # the HDR / Center scalar A per batch of the off-grid training rows (config['trajectory'])
         # graph_steps: every batch of the epoch becomes one captured HIP graph (fused kernel, weight-gradient GEMM,
         # reduction, Adam, step advance) replayed from then on -- the batches are fixed views of the resident data
         # (sequential sampler, models/utils.py:126-130), the step count and learning rate live in device memory.
@@ -265,22 +252,6 @@ class INRTrainer(ResidentFit):
                                       "forward, inr_focal_loss_grad and the fp32 backward")
 
     # ---- one optimizer step on batch `it` of epoch `epoch` --------------------------------------
-    def _inputs(self, lo: int, hi: int, train: bool = False):
-        coords = self._t_coords if train else self.coords
-        if self.enc_B is not None:
-            return coords[lo:hi]
-        if self.config["encoder"]["embedding"] == "none":
-            return coords[lo:hi]
-        return self.encoder.embedding(coords[lo:hi])
-
-    def _batch_hdr_A(self, it: int, lo: int, hi: int) -> float:
-        """A = mean_i((1-f_i)^2) over ALL batch coordinates (losses.py:241-242,258; SURVEY A.4 #17)."""
-        if self.loss.kind not in (L.LOSS_HDR, L.LOSS_CENTER):
-            return 0.0
-        if it not in self._hdr_A:
-            self._hdr_A[it] = float(torch.mean(hdr_weight(self.coords[lo:hi], self.loss.sigma)))
-        return self._hdr_A[it]
-
     def _train_hdr_A(self, it: int, lo: int, hi: int) -> float:
         """A of TRAINING batch ``it``: the grid batch's unless the fit trains on off-grid rows"""
         if self.trajectory is None:
@@ -290,12 +261,6 @@ class INRTrainer(ResidentFit):
         if it not in self._hdr_A_train:
             self._hdr_A_train[it] = float(torch.mean(hdr_weight(self._t_coords[lo:hi], self.loss.sigma)))
         return self._hdr_A_train[it]
-
-    def _refilled(self) -> None:
-        """The HDR / Center scalar A of every batch of the epoch buffers: one batched op over the epoch's coordinates and
-        one read-back."""
-        if self.loss.kind in (L.LOSS_HDR, L.LOSS_CENTER):
-            self._hdr_A_epoch = self._epoch_buf.batch_means(hdr_weight(self._t_coords, self.loss.sigma))
 
     def set_row_weights(self, weights: torch.Tensor) -> None:
         """Weighted epochs (config['row_sampling']): new per-row weights (device fp32 [n_train]) for the

@@ -81,10 +81,6 @@ class MultiscaleTrainer(ResidentFit):
         self._cons_epoch = []
         self._finish_init()
 
-    def _inputs(self, lo: int, hi: int, train: bool = False) -> torch.Tensor:
-        coords = self._t_coords if train else self.coords
-        return coords[lo:hi] if self.enc_B is not None else self.encoder.embedding(coords[lo:hi]).contiguous()
-
     def _refilled(self) -> None:
         """Recounts, per batch and disc, the rows outside the disc (the consistency term's mean): one batched op over
         the epoch's dist and one read-back."""

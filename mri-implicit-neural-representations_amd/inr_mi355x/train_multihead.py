@@ -37,13 +37,14 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .checkpoint import Part, joined_net, joined_optimizer_state, load_parts
 from .cli import cli_fit_data, cli_fits, parse_cli, run_cli
 from .engine import LossSpec
 from .gain import gain_inputs
 from .mix import MAX_HEADS, check_radii, inv_counts, mix_apply, mix_loss_grad
 from .networks import FFN
-from .train import MFN_MODELS, MODELS, hdr_weight
-from .trainer_base import ResidentFit, set_default_configs
+from .train import MFN_MODELS, MODELS
+from .trainer_base import ResidentFit, mlp_engine, set_default_configs
 
 GATE_NET = {"network_input_size": 2, "network_depth": 5, "network_width": 128}  # networks.py:293-299 (+ output size K)
 GATE_KEYS = ("network_width", "network_depth")
@@ -79,13 +80,11 @@ def has_head_keys(net_state: dict) -> bool:
 
 def merge_state(experts: Sequence[dict], gate: dict) -> OrderedDict:
     """MultiHeadWrapper.state_dict() with its heads in a ModuleList: 'heads.{k}.' + expert k's keys, then 'weighted_avg.'
-    + the gate FFN's (clones: a checkpoint must not alias the running weights)"""
+    + the gate FFN's (clones: a checkpoint must not alias the running weights).  Kept for callers outside the package:
+    the trainer writes the same keys through checkpoint.joined_net over its _parts()."""
     net = OrderedDict()
-    for k, sd in enumerate(experts):
-        for name, v in sd.items():
-            net[f"{HEAD_PREFIX}{k}.{name}"] = v.detach().clone()
-    for name, v in gate.items():
-        net[GATE_PREFIX + name] = v.detach().clone()
+    for prefix, sd in [(f"{HEAD_PREFIX}{k}.", sd) for k, sd in enumerate(experts)] + [(GATE_PREFIX, gate)]:
+        net.update((prefix + name, v.detach().clone()) for name, v in sd.items())
     return net
 
 
@@ -193,15 +192,14 @@ class MixtureFitTrainer(ResidentFit):
         self.gate_params = gate_net(self.mixture, self.K)
         # encoder, experts 0..K-1, gate on one CPU generator
         self._seeded_encoder(seed)
-        emb = config["encoder"]["embedding"]
-        self.enc_B = self.encoder.B.contiguous() if emb == "gauss" else None
-        self.models, self.engines = [], []
+        self.models, made = [], []
         for _ in range(self.K):
             self.models.append(MODELS[config["model"]](config["net"]))
         self.gate = FFN(self.gate_params)
         for k in range(self.K):
             m = self.models[k] = self.models[k].to(self.device)
-            self.engines.append(m.fused_engine(config["encoder"]["embedding_size"]) if emb == "gauss" else m._engine())
+            made.append(mlp_engine(m, self.encoder, config["encoder"]))
+        self.engines, self.enc_B = [eng for eng, _ in made], made[0][1]  # one encoder: every expert got the same matrix
         self.gate = self.gate.to(self.device)
         self.gate_engine = self.gate._engine()  # an INR_INPUT_X plan on z
         self.model, self.engine = self.models[0], self.engines[0]  # ResidentFit's test loss runs inr_loss_grad through it
@@ -210,8 +208,6 @@ class MixtureFitTrainer(ResidentFit):
         self.z = self._t_z = gain_inputs(self.coords)
         self.dist = self._t_dist = self.z[:, 1].contiguous()
         self._mix_loss = torch.zeros(L.LOSS_WORDS, device=self.device)
-        self._hdr_A = {}
-        self._hdr_A_epoch = []
         self._inv = self._batch_inv_counts(self._t_dist, self._t_mask if self.mask is not None else None) \
             if self._epoch_buf is None else []
         self._gate_parts = None
@@ -237,23 +233,14 @@ class MixtureFitTrainer(ResidentFit):
         self._t_z = gain_inputs(self._t_coords)
         self._t_dist = self._t_z[:, 1].contiguous()
         self._inv = self._batch_inv_counts(self._t_dist, self._t_mask if self.mask is not None else None)
-        if self.loss.kind == L.LOSS_HDR:
-            self._hdr_A_epoch = self._epoch_buf.batch_means(hdr_weight(self._t_coords, self.loss.sigma))
+        self._refill_hdr_A()
 
     # ---- one optimizer step ----------------------------------------------------------------------
-    def _inputs(self, lo: int, hi: int, train: bool = False):
-        coords = self._t_coords if train else self.coords
-        if self.enc_B is not None or self.config["encoder"]["embedding"] == "none":
-            return coords[lo:hi]
-        return self.encoder.embedding(coords[lo:hi])
-
-    def _batch_hdr_A(self, it: int, lo: int, hi: int) -> float:
-        """A = mean_i((1-f_i)^2) over all batch coordinates (INRTrainer._batch_hdr_A)"""
-        if self.loss.kind != L.LOSS_HDR:
-            return 0.0
-        if it not in self._hdr_A:
-            self._hdr_A[it] = float(torch.mean(hdr_weight(self.coords[lo:hi], self.loss.sigma)))
-        return self._hdr_A[it]
+    def _parts(self):
+        """experts in head order (the encoder travels with expert 0), then the gate"""
+        experts = [Part(f"{HEAD_PREFIX}{k}.", m, eng) for k, (m, eng) in enumerate(zip(self.models, self.engines))]
+        experts[0] = experts[0]._replace(encoder=self.encoder, rebind=self._rebind_encoder)
+        return experts + [Part(GATE_PREFIX, self.gate, self.gate_engine)]
 
     def step(self, epoch: int, it: int) -> torch.Tensor:
         if self.shuffle:
@@ -271,8 +258,8 @@ class MixtureFitTrainer(ResidentFit):
         for eng, dy in zip(self.engines, dys):
             eng.backward(x, self.enc_B, dy)
         self.gate_engine.backward(z, None, dw)
-        for eng in self.engines + [self.gate_engine]:
-            eng.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
+        for part in self._parts():
+            part.engine.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
         self.global_step += 1
         return out[0]
 
@@ -329,52 +316,25 @@ class MixtureFitTrainer(ResidentFit):
     def checkpoint(self) -> dict:
         """{'net', 'enc', 'opt', 'mixture'}: 'net' with the key names of a MultiHeadWrapper whose heads sit in a ModuleList,
         'opt' in torch.optim.Adam.state_dict() layout over the experts' parameters in head order, then the gate's."""
-        from .checkpoint import optimizer_state
-        net = merge_state([m.state_dict() for m in self.models], self.gate.state_dict())
-        opt, base = None, 0
-        for mod, eng in zip(self.models + [self.gate], self.engines + [self.gate_engine]):
-            part = optimizer_state(mod, eng, self.config)
-            if opt is None:
-                opt = part
-            else:
-                opt["state"].update({j + base: st for j, st in part["state"].items()})
-            base += len(part["param_groups"][0]["params"])
-        opt["param_groups"][0]["params"] = list(range(base))
-        ckpt = {"net": net, "enc": None if self.encoder.B is None else self.encoder.B.clone(), "opt": opt,
+        parts = self._parts()
+        ckpt = {"net": joined_net(parts), "enc": None if self.encoder.B is None else self.encoder.B.clone(),
+                "opt": joined_optimizer_state(parts, self.config),
                 "mixture": {"radii": list(self.radii), "detach": self.mixture["detach"], "clamp": self.mixture["clamp"]}}
         if self.coil_compression is not None:
             ckpt["coil_compression"] = self.coil_compression.state()
         return ckpt
 
     def load_checkpoint(self, ckpt: dict) -> None:
-        from .checkpoint import load_dict
-        from .coils import same_compression
         if not has_head_keys(ckpt["net"]):
             raise ValueError(wrong_checkpoint(ckpt["net"]))
-        mine = None if self.coil_compression is None else self.coil_compression.state()
-        differs = same_compression(ckpt.get("coil_compression"), mine)
-        if differs is not None:
-            raise ValueError(f"checkpoint and trainer disagree: {differs} (checkpoint first)")
+        self._check_same_compression(ckpt)
         experts, gate = split_state(ckpt["net"])
         if len(experts) != self.K:
             raise ValueError(f"the checkpoint has {len(experts)} heads, the trainer {self.K}")
         mix = ckpt.get("mixture")
         if mix is not None and [float(np.float32(r)) for r in mix["radii"]] != self.radii:
             raise ValueError(f"checkpoint and trainer disagree: radii {mix['radii']} against {self.radii}")
-        opt = ckpt.get("opt")
-        base = 0
-        for k, (mod, eng) in enumerate(zip(self.models + [self.gate], self.engines + [self.gate_engine])):
-            n = len(list(mod.parameters()))
-            part = None
-            if opt:
-                part = {"state": {j - base: st for j, st in opt["state"].items() if base <= j < base + n}}
-            if k < self.K:
-                load_dict(mod, self.encoder if k == 0 else None, eng,
-                          {"net": experts[k], "enc": ckpt.get("enc") if k == 0 else None, "opt": part},
-                          self._rebind_encoder)
-            else:
-                load_dict(mod, None, eng, {"net": gate, "enc": None, "opt": part})
-            base += n
+        load_parts(self._parts(), experts + [gate], [ckpt.get("enc")] + [None] * self.K, ckpt.get("opt"))
 
 
 def main():

@@ -25,7 +25,7 @@ import torch
 from .cli import cli_band_report, cli_data, cli_fit_data, cli_folders, cli_validation_images, parse_cli, print_band_tables
 from .engine import LossSpec
 from .train import MODELS, MFN_MODELS
-from .trainer_base import ResidentFit
+from .trainer_base import ResidentFit, mlp_engine
 
 
 def ring_owner(i: int, world: int) -> int:
@@ -68,16 +68,15 @@ class RingEnsembleTrainer(ResidentFit):
         # one shared encoder, then the models in ring order: every rank builds ALL of them so that the RNG stream
         # (and therefore each ring's initial weights) does not depend on the world size; only owned ones move to HBM
         self._seeded_encoder(seed)
-        emb = config["encoder"]["embedding"]
-        self.enc_B = self.encoder.B.contiguous() if emb == "gauss" else None
+        # (a rank may own no ring and still encodes its batches: enc_B does not wait for an engine)
+        self.enc_B = self.encoder.B.contiguous() if config["encoder"]["embedding"] == "gauss" else None
         self.models, self.engines = {}, {}
         for i in range(self.no_models):
             m = MODELS[config["model"]](config["net"])
             if i in self.owned:
                 m = m.to(self.device)
                 self.models[i] = m
-                self.engines[i] = (m.fused_engine(config["encoder"]["embedding_size"]) if emb == "gauss"
-                                   else m._engine())
+                self.engines[i] = mlp_engine(m, self.encoder, config["encoder"])[0]
         self.loss = LossSpec.from_config(config)
         # no mask and plain batches (image_full is the image itself); in a shuffled fit every rank fills its own epoch
         # buffers with the same order, and dist is recomputed from the epoch's coordinates (_refilled)
@@ -92,12 +91,8 @@ class RingEnsembleTrainer(ResidentFit):
         """the ensemble's own rings"""
         return [(self.radii[i], self.radii[i + 1]) for i in range(self.no_models)]
 
-    def _inputs(self, lo: int, hi: int, train: bool = False):
-        coords = self._t_coords if train else self.coords
-        emb = self.config["encoder"]["embedding"]
-        if self.enc_B is not None or emb == "none":
-            return coords[lo:hi]
-        return self.encoder.embedding(coords[lo:hi])
+    def _batch_hdr_A(self, it: int, lo: int, hi: int) -> float:
+        return 0.0  # loss 'HDR' is not refused here, and the ring loop has never handed the kernels an A
 
     def _refilled(self) -> None:
         """Every ring's row mask over the whole epoch buffer and its per-batch counts -- one batched op and one read-back

@@ -27,16 +27,17 @@ from typing import Optional
 
 import torch
 
-from . import _lib as L
+from .checkpoint import Part, joined_net, joined_optimizer_state, load_parts, split_prefixed
 from .cli import cli_fit_data, cli_fits, parse_cli, run_cli
 from .engine import LossSpec
 from .gain import gain_apply, gain_inputs, gain_loss_grad
 from .networks import FFN
-from .train import MFN_MODELS, MODELS, hdr_weight
-from .trainer_base import ResidentFit, set_default_configs
+from .train import MFN_MODELS, MODELS
+from .trainer_base import ResidentFit, mlp_engine, set_default_configs
 
 SCALER_NET = {"network_input_size": 2, "network_output_size": 1, "network_depth": 8, "network_width": 512}  # networks.py:388-393
 SCALER_KEYS = ("network_width", "network_depth")
+PREFIXES = ("backbone.", "scaler.")
 
 
 def scaler_net(config: dict) -> dict:
@@ -61,21 +62,12 @@ def has_scaler_keys(net_state: dict) -> bool:
 def wrapper_state(backbone, scaler) -> OrderedDict:
     """ScalerWrapper.state_dict() of the two models: 'backbone.' + the backbone's keys, then 'scaler.' + the FFN's
     (clones: a checkpoint must not alias the running weights)"""
-    net = OrderedDict()
-    for prefix, mod in (("backbone.", backbone), ("scaler.", scaler)):
-        for k, v in mod.state_dict().items():
-            net[prefix + k] = v.detach().clone()
-    return net
+    return joined_net([Part(p, m, None) for p, m in zip(PREFIXES, (backbone, scaler))])
 
 
 def split_state(net_state: dict):
     """(backbone state_dict, gain-network state_dict) of a ScalerWrapper's"""
-    back = OrderedDict((k[len("backbone."):], v) for k, v in net_state.items() if k.startswith("backbone."))
-    scal = OrderedDict((k[len("scaler."):], v) for k, v in net_state.items() if k.startswith("scaler."))
-    other = [k for k in net_state if not k.startswith(("backbone.", "scaler."))]
-    if other:
-        raise ValueError(f"keys outside 'backbone.' / 'scaler.': {other[:4]}")
-    return back, scal
+    return tuple(split_prefixed(net_state, PREFIXES))
 
 
 def check_scaled_config(config: dict, world: int = 1, graph_steps: bool = False) -> None:
@@ -128,44 +120,25 @@ class ScaledFitTrainer(ResidentFit):
         self._seeded_encoder(seed)
         self.model = MODELS[config["model"]](config["net"]).to(self.device)
         self.scaler = FFN(self.scaler_params).to(self.device)
-        emb = config["encoder"]["embedding"]
-        if emb == "gauss":
-            self.engine = self.model.fused_engine(config["encoder"]["embedding_size"])
-            self.enc_B = self.encoder.B.contiguous()
-        else:
-            self.engine = self.model._engine()
-            self.enc_B = None
+        self.engine, self.enc_B = mlp_engine(self.model, self.encoder, config["encoder"])
         self.scaler_engine = self.scaler._engine()  # an INR_INPUT_X plan on z
         self.loss = LossSpec.from_config(config)
         self._resident_data(image, coords, config["undersampling"], mask, mask_seed, False)
         self.z = self._t_z = gain_inputs(self.coords)
-        self._hdr_A = {}
-        self._hdr_A_epoch = []
         self._gain_parts = None
         self._last_gain = None
         self._finish_init()
 
     # ---- one optimizer step ----------------------------------------------------------------------
-    def _inputs(self, lo: int, hi: int, train: bool = False):
-        coords = self._t_coords if train else self.coords
-        if self.enc_B is not None or self.config["encoder"]["embedding"] == "none":
-            return coords[lo:hi]
-        return self.encoder.embedding(coords[lo:hi])
-
-    def _batch_hdr_A(self, it: int, lo: int, hi: int) -> float:
-        """A = mean_i((1-f_i)^2) over all batch coordinates (INRTrainer._batch_hdr_A)"""
-        if self.loss.kind != L.LOSS_HDR:
-            return 0.0
-        if it not in self._hdr_A:
-            self._hdr_A[it] = float(torch.mean(hdr_weight(self.coords[lo:hi], self.loss.sigma)))
-        return self._hdr_A[it]
+    def _parts(self):
+        return [Part(PREFIXES[0], self.model, self.engine, self.encoder, self._rebind_encoder),
+                Part(PREFIXES[1], self.scaler, self.scaler_engine)]
 
     def _refilled(self) -> None:
         """The epoch buffers hold a new epoch's rows: z from the epoch's coordinates (as the ring ensemble's dist), and
         the HDR scalar of every batch."""
         self._t_z = gain_inputs(self._t_coords)
-        if self.loss.kind == L.LOSS_HDR:
-            self._hdr_A_epoch = self._epoch_buf.batch_means(hdr_weight(self._t_coords, self.loss.sigma))
+        self._refill_hdr_A()
 
     def step(self, epoch: int, it: int) -> torch.Tensor:
         if self.shuffle:
@@ -182,8 +155,8 @@ class ScaledFitTrainer(ResidentFit):
                                          loss_out=self.engine._loss)
         self.engine.backward(x, self.enc_B, dy)
         self.scaler_engine.backward(z, None, ds.view(-1, 1))
-        for eng in (self.engine, self.scaler_engine):
-            eng.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
+        for part in self._parts():
+            part.engine.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
         self.global_step += 1
         return loss
 
@@ -232,38 +205,19 @@ class ScaledFitTrainer(ResidentFit):
         """{'net', 'enc', 'opt'} as train_scaling.py:220-223 writes it: 'net' with ScalerWrapper's state_dict keys, 'opt'
         in torch.optim.Adam.state_dict() layout over model.parameters() -- the backbone's parameters, then the gain
         network's."""
-        from .checkpoint import optimizer_state
-        net = wrapper_state(self.model, self.scaler)
-        opt =optimizer_state(self.model, self.engine, self.config)
-        nb = len(opt["param_groups"][0]["params"])
-        sopt = optimizer_state(self.scaler, self.scaler_engine, self.config)
-        opt["state"].update({j + nb: st for j, st in sopt["state"].items()})
-        opt["param_groups"][0]["params"] = list(range(nb + len(sopt["param_groups"][0]["params"])))
-        ckpt = {"net": net, "enc": None if self.encoder.B is None else self.encoder.B.clone(), "opt": opt}
+        parts = self._parts()
+        ckpt = {"net": joined_net(parts), "enc": None if self.encoder.B is None else self.encoder.B.clone(),
+                "opt": joined_optimizer_state(parts, self.config)}
         if self.coil_compression is not None:
             ckpt["coil_compression"] = self.coil_compression.state()
         return ckpt
 
     def load_checkpoint(self, ckpt: dict) -> None:
-        from .checkpoint import load_dict
-        from .coils import same_compression
         if not has_scaler_keys(ckpt["net"]):
             raise ValueError("the checkpoint has no 'scaler.' keys: it is a plain fit's -- load it with INRTrainer "
                              "(python -m inr_mi355x.train)")
-        mine = None if self.coil_compression is None else self.coil_compression.state()
-        differs = same_compression(ckpt.get("coil_compression"), mine)
-        if differs is not None:
-            raise ValueError(f"checkpoint and trainer disagree: {differs} (checkpoint first)")
-        back, scal = split_state(ckpt["net"])
-        nb = len(list(self.model.parameters()))
-        opt = ckpt.get("opt")
-        bopt = sopt = None
-        if opt:
-            bopt = {"state": {j: st for j, st in opt["state"].items() if j < nb}}
-            sopt = {"state": {j - nb: st for j, st in opt["state"].items() if j >= nb}}
-        load_dict(self.model, self.encoder, self.engine, {"net": back, "enc": ckpt.get("enc"), "opt": bopt},
-                  self._rebind_encoder)
-        load_dict(self.scaler, None, self.scaler_engine, {"net": scal, "enc": None, "opt": sopt})
+        self._check_same_compression(ckpt)
+        load_parts(self._parts(), split_state(ckpt["net"]), [ckpt.get("enc"), None], ckpt.get("opt"))
 
 
 def main():

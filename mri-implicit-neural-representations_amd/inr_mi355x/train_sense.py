@@ -50,14 +50,15 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .checkpoint import Part, joined_net, joined_optimizer_state, load_parts
 from .cli import cli_fit_data, cli_fits, parse_cli, run_cli
 from .engine import LossSpec
 from .networks import FFN, Positional_Encoder
 from .sense import (IMAGE_PREFIX, SENS_PREFIX, has_sense_keys, join_state, sens_encoder_config, sense_apply,  # noqa: F401
                     sense_grad, shift_index, split_state)
 from .shuffle import CoilOrder
-from .train import MFN_MODELS, MODELS, hdr_weight
-from .trainer_base import ResidentFit, set_default_configs
+from .train import MFN_MODELS, MODELS
+from .trainer_base import ResidentFit, _encoded, mlp_engine, set_default_configs
 
 SENSE_KEYS = ("coils_per_step", "scale", "net", "encoder", "max_stash_bytes")
 MAPS_KEYS = ("maps", "calib", "baseline", "cg_lambda")  # DESIGN.md 4.29; the last three with maps: calibrated only
@@ -279,11 +280,9 @@ class SenseFitTrainer(ResidentFit):
         if self.calib is not None:
             self.model = model.to(self.device)
             self.sens_encoder = self.sens_model = self.sens_engine = self.sens_enc_B = None
-            self.engine = self.model.fused_engine(config["encoder"]["embedding_size"]) if emb == "gauss" else \
-                self.model._engine()
-            self.enc_B = self.encoder.B.contiguous() if emb == "gauss" else None
+            self.engine, self.enc_B = mlp_engine(self.model, self.encoder, config["encoder"])
         else:
-            self._two_networks(model, config, emb)
+            self._two_networks(model, config)
         if self.engine.out_features != 2:
             raise ValueError(f"config['net']['network_output_size'] = {self.engine.out_features}: the image network gives "
                              "one complex number (2 outputs)")
@@ -302,7 +301,6 @@ class SenseFitTrainer(ResidentFit):
         if self.shuffle and len(self.groups) > 1:
             self._coil_order = CoilOrder(len(self.groups), self.shuffle_seed)
         self._ingest(C_, H, W)
-        self._hdr_A = {}
         self._last_sense = self._last_prior = None
         if self.prior is not None:  # the prior's value and block partials, made once
             self._prior_out = torch.zeros(L.LOSS_WORDS, device=self.device)
@@ -312,18 +310,14 @@ class SenseFitTrainer(ResidentFit):
             self._cg_sense_baseline()
 
     # ---- set-up ----------------------------------------------------------------------------------
-    def _two_networks(self, model, config: dict, emb: str) -> None:
+    def _two_networks(self, model, config: dict) -> None:
         """learned maps: the sensitivity encoder and network follow the image network on the same CPU generator"""
-        self.sens_encoder = Positional_Encoder(sens_encoder_config(self.settings, config["encoder"]), device=self.device)
+        sens_enc = sens_encoder_config(self.settings, config["encoder"])
+        self.sens_encoder = Positional_Encoder(sens_enc, device=self.device)
         sens_model = FFN(self.sens_params)
         self.model, self.sens_model = model.to(self.device), sens_model.to(self.device)
-        if emb == "gauss":
-            self.engine = self.model.fused_engine(config["encoder"]["embedding_size"])
-            self.sens_engine = self.sens_model.fused_engine(self.settings["encoder"]["embedding_size"])
-            self.enc_B, self.sens_enc_B = self.encoder.B.contiguous(), self.sens_encoder.B.contiguous()
-        else:
-            self.engine, self.sens_engine = self.model._engine(), self.sens_model._engine()
-            self.enc_B = self.sens_enc_B = None
+        self.engine, self.enc_B = mlp_engine(self.model, self.encoder, config["encoder"])
+        self.sens_engine, self.sens_enc_B = mlp_engine(self.sens_model, self.sens_encoder, sens_enc)
 
     def _check_stash(self, G: int, plane: int, gauss: bool) -> None:
         budget, E = self.settings["max_stash_bytes"], self.settings["encoder"]["embedding_size"]
@@ -344,7 +338,7 @@ class SenseFitTrainer(ResidentFit):
         self._mask_s = None if self.mask is None else self.mask.view(C_, self.plane)[:, perm].contiguous().view(-1)
         self._img_coords = self.coords[:self.plane].clone()
         self._img_coords[:, 0] = 0.0
-        self._img_in = self._encoded(self.encoder, self.enc_B, self._img_coords)
+        self._img_in = _encoded(self.encoder, self.enc_B, self._img_coords)
         self.sense_scale = self.settings["scale"]
         if self.sense_scale is None:
             from .evalchain import ifft2c
@@ -371,22 +365,16 @@ class SenseFitTrainer(ResidentFit):
             stats = torch.stack((self.sens_rss.min(), self.sens_rss.max(), self.sens_rss.double().mean().float()))
             self._rss_stats = dict(zip(("min", "max", "mean"), stats.cpu().tolist()))
 
-    def _encoded(self, encoder, enc_B, coords: torch.Tensor) -> torch.Tensor:
-        if enc_B is not None or self.config["encoder"]["embedding"] == "none":
-            return coords.contiguous()
-        return encoder.embedding(coords).contiguous()
-
     def _sens_in(self, lo: int, hi: int) -> torch.Tensor:
-        return self._encoded(self.sens_encoder, self.sens_enc_B, self.coords[lo:hi])
+        return _encoded(self.sens_encoder, self.sens_enc_B, self.coords[lo:hi])
 
     # ---- one optimizer step ----------------------------------------------------------------------
-    def _batch_hdr_A(self, it: int, lo: int, hi: int) -> float:
-        """A = mean_i((1-f_i)^2) over the group's coordinates (INRTrainer._batch_hdr_A); a mean does not see row order"""
-        if self.loss.kind != L.LOSS_HDR:
-            return 0.0
-        if it not in self._hdr_A:
-            self._hdr_A[it] = float(torch.mean(hdr_weight(self.coords[lo:hi], self.loss.sigma)))
-        return self._hdr_A[it]
+    def _parts(self):
+        """the image network; with learned maps the sensitivity network behind it, its encoder travelling with it"""
+        parts = [Part(IMAGE_PREFIX, self.model, self.engine, self.encoder, self._rebind_encoder)]
+        if self.calib is None:
+            parts.append(Part(SENS_PREFIX, self.sens_model, self.sens_engine, self.sens_encoder, self._rebind_sens_encoder))
+        return parts
 
     def step(self, epoch: int, it: int) -> torch.Tensor:
         if self._coil_order is not None:
@@ -424,8 +412,8 @@ class SenseFitTrainer(ResidentFit):
             loss = loss + self._add_prior(ib, dimg, H, W)
         self.engine.backward(self._img_in, self.enc_B, dimg)
         self.sens_engine.backward(xs, self.sens_enc_B, dsens)
-        for eng in (self.engine, self.sens_engine):
-            eng.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
+        for part in self._parts():
+            part.engine.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
         self.global_step += 1
         return loss
 
@@ -439,7 +427,7 @@ class SenseFitTrainer(ResidentFit):
     # ---- validation ------------------------------------------------------------------------------
     def _sweep(self, engine, enc_B, rows: torch.Tensor, chunk: int, encoder) -> torch.Tensor:
         n = rows.shape[0]
-        return torch.cat([engine.forward(self._encoded(encoder, enc_B, rows[lo:min(lo + chunk, n)]), enc_B, save=False)
+        return torch.cat([engine.forward(_encoded(encoder, enc_B, rows[lo:min(lo + chunk, n)]), enc_B, save=False)
                           for lo in range(0, n, chunk)], 0)
 
     @torch.no_grad()
@@ -564,19 +552,9 @@ class SenseFitTrainer(ResidentFit):
         """{'net', 'enc', 'opt'} in the reference's layout -- 'net' with 'image.*' then 'sens.*' keys, 'enc' the image
         network's encoder matrix, 'opt' in torch.optim.Adam.state_dict() layout over the image network's parameters, then
         the sensitivity network's -- plus 'sense': the factor, the sensitivity encoder's matrix and the sizes."""
-        from .checkpoint import optimizer_state
-        opt = optimizer_state(self.model, self.engine, self.config)
-        if self.calib is not None:  # 'image.*' keys only; the maps are not stored: 'sense' holds the windowed block
-            from .sense_calib import image_net_state
-            return {"net": image_net_state(self.model.state_dict()), "enc": None if self.encoder.B is None else self.encoder.B.clone(), "opt": opt,
-                    "sense": self._sense_state()}
-        ni = len(opt["param_groups"][0]["params"])
-        sopt = optimizer_state(self.sens_model, self.sens_engine, self.config)
-        opt["state"].update({j + ni: st for j, st in sopt["state"].items()})
-        opt["param_groups"][0]["params"] = list(range(ni + len(sopt["param_groups"][0]["params"])))
-        return {"net": join_state(self.model.state_dict(), self.sens_model.state_dict()),
-                "enc": None if self.encoder.B is None else self.encoder.B.clone(), "opt": opt,
-                "sense": self._sense_state()}
+        parts = self._parts()  # calibrated maps: 'image.*' alone; the maps are not stored, 'sense' holds their block
+        return {"net": joined_net(parts), "enc": None if self.encoder.B is None else self.encoder.B.clone(),
+                "opt": joined_optimizer_state(parts, self.config), "sense": self._sense_state()}
 
     def _rebind_sens_encoder(self, enc) -> None:
         if self.sens_enc_B is not None:
@@ -584,7 +562,6 @@ class SenseFitTrainer(ResidentFit):
 
     def load_checkpoint(self, ckpt: dict) -> None:
         """Resumes under the same ``sense`` settings only: factor, coils_per_step and both sizes must be the trainer's."""
-        from .checkpoint import load_dict
         if not has_sense_keys(ckpt["net"]) or ckpt.get("sense") is None:
             raise ValueError("the checkpoint has no 'image.' / 'sens.' keys: it is not a SENSE-model fit's -- load it with "
                              "the trainer that wrote it")
@@ -593,27 +570,15 @@ class SenseFitTrainer(ResidentFit):
         check_sense_mode(theirs, "learned" if self.calib is None else "calibrated")
         if self.calib is not None:
             check_calibrated_state(theirs, mine)
-            img = image_net_of(ckpt["net"])
-            load_dict(self.model, self.encoder, self.engine, {"net": img, "enc": ckpt.get("enc"), "opt": ckpt.get("opt")},
-                      self._rebind_encoder)
-            self._img_in = self._encoded(self.encoder, self.enc_B, self._img_coords)
-            return
-        for key in ("scale", "coils_per_step", "net", "encoder"):
-            if theirs.get(key) != mine[key]:
-                raise ValueError(f"checkpoint and trainer disagree on config['sense']: {key} = {theirs.get(key)!r} in the "
-                                 f"checkpoint, {mine[key]!r} here")
-        img, sen = split_state(ckpt["net"])
-        ni = len(list(self.model.parameters()))
-        opt = ckpt.get("opt")
-        iopt = sopt = None
-        if opt:
-            iopt = {"state": {j: st for j, st in opt["state"].items() if j < ni}}
-            sopt = {"state": {j - ni: st for j, st in opt["state"].items() if j >= ni}}
-        load_dict(self.model, self.encoder, self.engine, {"net": img, "enc": ckpt.get("enc"), "opt": iopt},
-                  self._rebind_encoder)
-        load_dict(self.sens_model, self.sens_encoder, self.sens_engine,
-                  {"net": sen, "enc": theirs.get("enc_B"), "opt": sopt}, self._rebind_sens_encoder)
-        self._img_in = self._encoded(self.encoder, self.enc_B, self._img_coords)  # the encoder may have been replaced
+            nets = [image_net_of(ckpt["net"])]
+        else:
+            for key in ("scale", "coils_per_step", "net", "encoder"):
+                if theirs.get(key) != mine[key]:
+                    raise ValueError(f"checkpoint and trainer disagree on config['sense']: {key} = {theirs.get(key)!r} in "
+                                     f"the checkpoint, {mine[key]!r} here")
+            nets = split_state(ckpt["net"])
+        load_parts(self._parts(), nets, [ckpt.get("enc"), theirs.get("enc_B")][:len(nets)], ckpt.get("opt"))
+        self._img_in = _encoded(self.encoder, self.enc_B, self._img_coords)  # the encoder may have been replaced
 
 
 def add_sense_flags(ap) -> None:

@@ -13,6 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import _lib as L
 from .evalchain import image_metrics, psnr, reconstruct
 from .networks import Positional_Encoder
 from .shuffle import CoilOrder, EpochBuffers, shuffle_settings
@@ -33,6 +34,13 @@ def set_default_configs(config: dict) -> dict:
     config.setdefault("trajectory_density", None)  # the baseline's density weights; None: ramp (spokes) / uniform (file)
     config.setdefault("trajectory_operator", None)  # the baseline's operator pair: exact | gridding; None: exact, unrecorded
     return config
+
+
+def hdr_weight(kcoords: torch.Tensor, sigma: float) -> torch.Tensor:
+    """(1 - f)^2 per row, f the Gaussian of the k-space radius: the HDR / Center losses' A is its mean over a batch
+    (losses.py:241-242,258; SURVEY A.4 #17)."""
+    f = torch.exp(-(kcoords[:, 1] ** 2 + kcoords[:, 2] ** 2) / (2 * sigma ** 2))
+    return (1 - f) ** 2
 
 
 def lr_factor(epoch: int, max_epoch: int) -> float:
@@ -65,6 +73,22 @@ def mfn_engine(model, encoder, embedding: str):
         model.bind_encoder(encoder)
         return model._engine("gauss"), encoder.B.contiguous()
     return model._engine("x"), None
+
+
+def mlp_engine(model, encoder, enc_config: dict, **fused):
+    """(engine, enc_B) of a SIREN / FFN / WIRE model on the device behind ``encoder`` (``enc_config``: that encoder's
+    'embedding' and 'embedding_size'): 'gauss' is fused into layer 0 (raw coordinates in, the kernels take the encoder
+    matrix); with 'LogF' / 'none' the first layer reads its input rows from memory.  ``fused``: fused_engine's further
+    arguments -- ``precision=config['precision']`` where the key is there and the driver honours it."""
+    if enc_config["embedding"] == "gauss":
+        return model.fused_engine(enc_config["embedding_size"], **fused), encoder.B.contiguous()
+    return model._engine(), None
+
+
+def _encoded(encoder, enc_B, coords: torch.Tensor) -> torch.Tensor:
+    """the rows an engine made by mlp_engine takes for ``coords``: the coordinates themselves where the encoder is fused
+    into layer 0, else encoder.embedding's rows ('none': the coordinates again)"""
+    return coords if enc_B is not None else encoder.embedding(coords)
 
 
 def run_epochs(trainer, max_steps, log_every, val_epoch, on_validate, on_epoch_end):
@@ -207,6 +231,8 @@ class ResidentFit(ValidationMixin):
             self._ring_normalize()
         self.steps_per_epoch = math.ceil(self.n_train / self.bs)
         self.global_step = 0
+        self._hdr_A = {}  # the HDR / Center scalar A per batch of the unshuffled data, and of the epoch buffers
+        self._hdr_A_epoch = []
         # config['shuffle']: plain batches are views of a second set of resident buffers, refilled by one kernel call per
         # epoch (shuffle.EpochBuffers); per-coil batches stay views of the grid and are visited in a permuted order.
         # Validation, predict_all and the test loss keep reading the unshuffled data (the reference's val loader is
@@ -325,6 +351,13 @@ class ResidentFit(ValidationMixin):
 
     def _refilled(self) -> None:
         """The epoch buffers hold a new epoch's rows."""
+        self._refill_hdr_A()
+
+    def _refill_hdr_A(self) -> None:
+        """The HDR / Center scalar A of every batch of the epoch buffers: one batched op over the epoch's coordinates and
+        one read-back."""
+        if self.loss.kind in (L.LOSS_HDR, L.LOSS_CENTER):
+            self._hdr_A_epoch = self._epoch_buf.batch_means(hdr_weight(self._t_coords, self.loss.sigma))
 
     def _row_sampling_summary(self) -> Optional[dict]:
         return self._epoch_buf.summary() if self.row_sampling is not None else None
@@ -371,9 +404,18 @@ class ResidentFit(ValidationMixin):
         ref = reconstruct(self.image_full, self.shape, self.in_image_space)
         return float(psnr(ref, reconstruct(self.predict_all(), self.shape, self.in_image_space)))
 
+    def _inputs(self, lo: int, hi: int, train: bool = False) -> torch.Tensor:
+        """the engine's input rows [lo, hi) of the resident data, or of the training views"""
+        return _encoded(self.encoder, self.enc_B, (self._t_coords if train else self.coords)[lo:hi])
+
     def _batch_hdr_A(self, it: int, lo: int, hi: int) -> float:
-        """the loss's scalar A of batch ``it`` of the unshuffled data, where the loss has one"""
-        return 0.0
+        """the loss's scalar A of batch ``it`` of the unshuffled data, where the loss has one: A = mean_i((1-f_i)^2) over
+        ALL batch coordinates (losses.py:241-242,258; SURVEY A.4 #17)"""
+        if self.loss.kind not in (L.LOSS_HDR, L.LOSS_CENTER):
+            return 0.0
+        if it not in self._hdr_A:
+            self._hdr_A[it] = float(torch.mean(hdr_weight(self.coords[lo:hi], self.loss.sigma)))
+        return self._hdr_A[it]
 
     def _validated(self, epoch: int, pred: torch.Tensor) -> dict:
         """Scores the sweep ``pred`` of a validation epoch: the test loss (the config's loss over sequential val batches of
@@ -444,14 +486,18 @@ class ResidentFit(ValidationMixin):
         if self.enc_B is not None:
             self.enc_B = enc.B.contiguous()
 
-    def load_checkpoint(self, ckpt: dict) -> None:
-        """train.py:117-121 (config['pretrain']): weights, Adam moments / step count and the encoder matrix."""
-        from .checkpoint import load_dict
+    def _check_same_compression(self, ckpt: dict) -> None:
+        """ValueError unless the checkpoint was written under the coil compression the trainer's data came through"""
         from .coils import same_compression
         mine = None if self.coil_compression is None else self.coil_compression.state()
         differs = same_compression(ckpt.get("coil_compression"), mine)
         if differs is not None:
             raise ValueError(f"checkpoint and trainer disagree: {differs} (checkpoint first)")
+
+    def load_checkpoint(self, ckpt: dict) -> None:
+        """train.py:117-121 (config['pretrain']): weights, Adam moments / step count and the encoder matrix."""
+        from .checkpoint import load_dict
+        self._check_same_compression(ckpt)
         from .ringnorm import same_table
         differs = same_table(ckpt.get("ring_normalization"), None if self.ring_table is None else self.ring_table.state())
         if differs is not None:

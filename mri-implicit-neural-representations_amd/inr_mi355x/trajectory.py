@@ -203,9 +203,8 @@ def nudft(img: torch.Tensor, pos, scratch: Optional[torch.Tensor] = None) -> tor
     if scratch is None:
         scratch = torch.empty(scratch_floats(coils, H, W, M), device=img.device, dtype=torch.float32)
     out = torch.empty(coils, M, 2, device=img.device, dtype=torch.float32)
-    with torch.cuda.device(img.device):
-        L.check(L.load().inr_nudft(img.data_ptr(), coils, H, W, p.data_ptr(), M, out.data_ptr(), scratch.data_ptr(),
-                                   scratch.numel(), torch.cuda.current_stream(img.device).cuda_stream))
+    L.launch("inr_nudft", img.device, img.data_ptr(), coils, H, W, p.data_ptr(), M, out.data_ptr(), scratch.data_ptr(),
+             scratch.numel())
     return out
 
 
@@ -299,10 +298,8 @@ def nudft_adjoint(val: torch.Tensor, pos, shape, weights=None, scratch: Optional
         scratch = torch.empty(adjoint_scratch_floats(coils, H, W, M), device=val.device, dtype=torch.float32)
     if out is None:
         out = torch.empty(coils, H, W, 2, device=val.device, dtype=torch.float32)
-    with torch.cuda.device(val.device):
-        L.check(L.load().inr_adjoint_nudft(val.data_ptr(), p.data_ptr(), None if w is None else w.data_ptr(), coils, H, W,
-                                           M, out.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                           torch.cuda.current_stream(val.device).cuda_stream))
+    L.launch("inr_adjoint_nudft", val.device, val.data_ptr(), p.data_ptr(), None if w is None else w.data_ptr(), coils,
+             H, W, M, out.data_ptr(), scratch.data_ptr(), scratch.numel())
     return out
 
 
@@ -528,15 +525,14 @@ def nufft(img: torch.Tensor, pos, scratch: Optional[torch.Tensor] = None, apod=N
     if scratch is None:
         scratch = torch.empty(nufft_scratch_floats(coils, H, W, M), device=img.device, dtype=torch.float32)
     ay, ax = apod if apod is not None else nufft_device_apodisation(H, W, img.device)
-    lib = L.load()
     grid = torch.empty(coils, 2 * H, 2 * W, 2, device=img.device, dtype=torch.float32)
     out = torch.empty(coils, M, 2, device=img.device, dtype=torch.float32)
-    with torch.cuda.device(img.device):
-        stream = torch.cuda.current_stream(img.device).cuda_stream
-        L.check(lib.inr_nufft_prepare(img.data_ptr(), ay.data_ptr(), ax.data_ptr(), coils, H, W, grid.data_ptr(), stream))
+    with torch.cuda.device(img.device):  # the FFT between the two calls runs on this device too
+        L.launch("inr_nufft_prepare", img.device, img.data_ptr(), ay.data_ptr(), ax.data_ptr(), coils, H, W,
+                 grid.data_ptr())
         grid = fft2c(grid).contiguous()
-        L.check(lib.inr_nufft_interp(grid.data_ptr(), p.data_ptr(), coils, H, W, M, out.data_ptr(), scratch.data_ptr(),
-                                     scratch.numel(), stream))
+        L.launch("inr_nufft_interp", img.device, grid.data_ptr(), p.data_ptr(), coils, H, W, M, out.data_ptr(),
+                 scratch.data_ptr(), scratch.numel())
     return out
 
 
@@ -560,15 +556,14 @@ def nufft_adjoint(val: torch.Tensor, pos, shape, weights=None, scratch: Optional
     ay, ax = apod if apod is not None else nufft_device_apodisation(H, W, val.device)
     if out is None:
         out = torch.empty(coils, H, W, 2, device=val.device, dtype=torch.float32)
-    lib = L.load()
     grid = torch.empty(coils, 2 * H, 2 * W, 2, device=val.device, dtype=torch.float32)
-    with torch.cuda.device(val.device):
-        stream = torch.cuda.current_stream(val.device).cuda_stream
-        L.check(lib.inr_nufft_spread(val.data_ptr(), p.data_ptr(), None if w is None else w.data_ptr(),
-                                     bin_start.data_ptr(), order.data_ptr(), coils, H, W, M, grid.data_ptr(),
-                                     scratch.data_ptr(), scratch.numel(), stream))
+    with torch.cuda.device(val.device):  # the FFT between the two calls runs on this device too
+        L.launch("inr_nufft_spread", val.device, val.data_ptr(), p.data_ptr(), None if w is None else w.data_ptr(),
+                 bin_start.data_ptr(), order.data_ptr(), coils, H, W, M, grid.data_ptr(), scratch.data_ptr(),
+                 scratch.numel())
         grid = ifft2c(grid).contiguous()
-        L.check(lib.inr_nufft_finish(grid.data_ptr(), ay.data_ptr(), ax.data_ptr(), coils, H, W, out.data_ptr(), stream))
+        L.launch("inr_nufft_finish", val.device, grid.data_ptr(), ay.data_ptr(), ax.data_ptr(), coils, H, W,
+                 out.data_ptr())
     return out
 
 

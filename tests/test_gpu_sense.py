@@ -300,6 +300,28 @@ def test_predict_all_is_the_shifted_transform_of_the_product(dev, fit):
     assert rec["test_loss"] is not None and np.isfinite(rec["psnr"]) and np.isfinite(rec["ssim"])
 
 
+def test_resume_is_bit_identical(dev):
+    """coils_per_step = 2 of 3 coils (a short last group): 4 steps, checkpoint() into a new trainer through
+    load_checkpoint, 2 more steps -- parameters, Adam moments and step count of both engines equal to the bit to those of
+    6 uninterrupted steps"""
+    whole, a, b = (_trainer(dev, coils_per_step=2) for _ in range(3))
+    assert whole.groups == [(0, 2), (2, 3)]
+    whole.fit(6)
+    a.fit(4)
+    ckpt = a.checkpoint()
+    assert [k.split(".")[0] for k in ckpt["net"]] == ["image"] * 6 + ["sens"] * 6
+    assert sorted(ckpt["opt"]["state"]) == list(range(12)) and ckpt["opt"]["param_groups"][0]["params"] == list(range(12))
+    b.load_checkpoint(ckpt)
+    assert b.engine.step == 4 and b.sens_engine.step == 4
+    b.global_step = a.global_step  # fit() takes up the epoch loop where the checkpoint was written
+    for epoch, it in ((2, 0), (2, 1)):
+        b.step(epoch, it)
+    for eb, ew in ((b.engine, whole.engine), (b.sens_engine, whole.sens_engine)):
+        assert eb.step == ew.step == 6
+        for name in ("params", "exp_avg", "exp_avg_sq"):
+            assert _bits(getattr(eb, name), getattr(ew, name)), name
+
+
 def test_reconstructor(dev, fit, tmp_path):
     """k-space of the native grid equals predict_all() bit for bit; the rendering itself is coil images; --scale 2 has the
     doubled shape and finite values; coils and window work"""

@@ -351,6 +351,24 @@ def test_cg_sense_against_float64(dev, fit):
     assert all(abs(a_ - b_) <= 1e-5 * want_obj[0] for a_, b_ in zip(objective, want_obj))
 
 
+def test_resume_is_bit_identical(dev):
+    """one part under 'image.': 4 steps, checkpoint() into a new trainer through load_checkpoint, 2 more steps --
+    parameters, Adam moments and step count equal to the bit to those of 6 uninterrupted steps"""
+    whole, a, b = (_trainer(dev) for _ in range(3))
+    whole.fit(6)
+    a.fit(4)
+    ckpt = a.checkpoint()
+    assert all(k.startswith("image.") for k in ckpt["net"]) and len(ckpt["net"]) == 6
+    assert sorted(ckpt["opt"]["state"]) == list(range(6)) and ckpt["opt"]["param_groups"][0]["params"] == list(range(6))
+    b.load_checkpoint(ckpt)
+    assert b.engine.step == 4
+    for epoch in (4, 5):  # one group: one step per epoch
+        b.step(epoch, 0)
+    assert b.engine.step == whole.engine.step == 6
+    for name in ("params", "exp_avg", "exp_avg_sq"):
+        assert _bits(getattr(b.engine, name), getattr(whole.engine, name)), name
+
+
 def test_reconstructor_round_trip(dev, fit, tmp_path):
     from inr_mi355x.reconstruct import Reconstructor
     tr = fit[0]
