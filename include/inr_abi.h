@@ -70,7 +70,8 @@ extern "C" {
  *    coil maps calibrated from the centre of k-space: low-resolution coil images of the centre block on any grid, their
  *    unit-RSS maps, and the image half of inr_sense_grad alone); inr_image_tv_grad (a total-variation prior on the
  *    image of a SENSE fit: smoothed isotropic TV of the image network's output, its value and its gradient in one gather
- *    pass).
+ *    pass); inr_sense_nufft_prepare, inr_sense_nufft_finish, inr_nufft_interp_plain and inr_nufft_spread_plain (off-grid
+ *    SENSE fits: the coil product fused with the gridding operators on a grid laid out as a plain FFT reads it).
  * 6: inr_plan_step_info, inr_loss_tv_grad, 16-word gradient-scale state.  5: bf16 plans.  4: inr_adam_step_dev.  3: inr_workspace. */
 #define INR_ABI_VERSION 7
 
@@ -923,6 +924,40 @@ int inr_nufft_spread(const float* val, const double* pos, const float* w, const 
                      void* stream);
 int inr_nufft_finish(const float* grid, const float* apod_y, const float* apod_x, int32_t C, int64_t H, int64_t W,
                      float* out, void* stream);
+
+/* (v7 addition) Off-grid SENSE fits on calibrated coil maps (no reference counterpart): the
+ * gridding operators above with the coil product of inr_sense_apply / inr_sense_adjoint fused into their first and last
+ * pass, on a grid in PLAIN layout -- the layout a plain (unshifted) 2-D FFT reads and writes.  Gy = 2 H and Gx = 2 W are
+ * even, so fftshift and ifftshift are both the roll by (H, W): the plain grid is the centred grid of inr_nufft_* rolled
+ * by (H, W), cell (jy, jx) of the centred grid lives at ((jy + H) mod Gy, (jx + W) mod Gx), and pixel (y, x) at
+ * ((y - H/2) mod Gy, (x - W/2) mod Gx) with integer H/2, W/2.  The caller's FFT between the calls is the plain
+ * orthonormal one; no shifted copy and no coil images are made.
+ *   inr_nufft_interp_plain, inr_nufft_spread_plain: inr_nufft_interp / inr_nufft_spread on a plain-layout grid -- same
+ *       arguments, checks, scratch, bins and cell list, same arithmetic in the same order (interp's output is bit for bit
+ *       that of inr_nufft_interp on the centred grid; spread's grid is bit for bit the roll of inr_nufft_spread's).
+ *   inr_sense_nufft_prepare: img [H*W,2], maps [G,H*W,2] -> grid [G,Gy,Gx,2].  Per coil and pixel, in fp32, nothing
+ *       contracted: (xr, xi) = inr_sense_apply's x (re = sr*ir - si*ii; im = sr*ii + si*ir; scale*re, scale*im), then
+ *       d = 2 / (apod_y[y] * apod_x[x]) and the cell (xr * d, xi * d).  Padding cells are written as zeros: every
+ *       element of grid is written.  Bit for bit inr_sense_apply(shift 0) + inr_nufft_prepare, rolled by (H, W).
+ *   inr_sense_nufft_finish: grid, maps -> dimg [H*W,2].  Per pixel, coils in ascending order from zero:
+ *       (gr, gi) = the pixel's cell; v = (gr * d, gi * d); ur = scale*vr; ui = scale*vi;
+ *       t_g = (sr*ur + si*ui, sr*ui - si*ur); dI = (((0 + t_0) + t_1) + ...) + t_{G-1};
+ *       dimg[p] = dI, or with accumulate = 1 dimg[p] + dI (one fp32 addition).  Bit for bit inr_nufft_finish of the grid
+ *       rolled back + inr_sense_adjoint(shift 0).  One lane owns a pixel for every coil: no atomics, same bits every call.
+ * prepare / finish: one launch on `stream`; with every pointer 16-byte aligned and W and W/2 even two neighbouring cells
+ * move per 16-byte access, else one per 8-byte access; the results do not depend on which path ran.
+ * INR_ERR_INVALID before any launch: a null pointer; G outside 1..INR_COIL_MAX; H or W < 3; H * W >= 2^31; a non-finite
+ * scale; accumulate outside {0, 1}; img / dimg / maps / grid not 8-byte or apod_y / apod_x not 4-byte aligned; the output
+ * (grid, dimg) overlapping an input.  The _plain entries refuse what inr_nufft_interp / inr_nufft_spread refuse. */
+int inr_nufft_interp_plain(const float* grid, const double* pos, int32_t C, int64_t H, int64_t W, int64_t M, float* out,
+                           float* scratch, int64_t scratch_floats, void* stream);
+int inr_nufft_spread_plain(const float* val, const double* pos, const float* w, const int32_t* bin_start,
+                           const int32_t* order, int32_t C, int64_t H, int64_t W, int64_t M, float* grid, float* scratch,
+                           int64_t scratch_floats, void* stream);
+int inr_sense_nufft_prepare(const float* img, const float* maps, const float* apod_y, const float* apod_x, int32_t G,
+                            int64_t H, int64_t W, float scale, float* grid, void* stream);
+int inr_sense_nufft_finish(const float* grid, const float* maps, const float* apod_y, const float* apod_x, int32_t G,
+                           int64_t H, int64_t W, float scale, float* dimg, int32_t accumulate, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,8 @@
 // inr_api_offgrid.hip -- the entries of the C-ABI (include/inr_abi.h) for the off-grid operators: inr_nudft, its conjugate
-// transpose and the Kaiser-Bessel gridding form of both.  Each checks null pointers, shapes, alignment, scratch size and
+// transpose, the Kaiser-Bessel gridding form of both, and the coil product fused with that form for off-grid SENSE fits.
+// Each checks null pointers, shapes, alignment, scratch size and
 // overlaps, in that order, then launches and maps the hipError_t to a code; none allocates device memory or syncs.
+#include <cmath>
 #include <cstring>
 #include <initializer_list>
 
@@ -82,7 +84,7 @@ static int nufft_check(int32_t C, int64_t H, int64_t W, int64_t M, const char* w
 }
 
 // bin_start where the host can read it (pinned host memory): 0 = bin_start[0] <= ... <= bin_start[T] = M
-static int nufft_bins_check(const int32_t* bin_start, int64_t T, int64_t M) {
+static int nufft_bins_check(const char* who, const int32_t* bin_start, int64_t T, int64_t M) {
   hipPointerAttribute_t attr;
   memset(&attr, 0, sizeof(attr));
   if (hipPointerGetAttributes(&attr, bin_start) != hipSuccess) {
@@ -94,7 +96,7 @@ static int nufft_bins_check(const int32_t* bin_start, int64_t T, int64_t M) {
   bool ok = b[0] == 0 && b[T] == M;
   for (int64_t i = 0; ok && i < T; ++i) ok = b[i] <= b[i + 1];
   if (!ok)
-    return fail(INR_ERR_INVALID, "inr_nufft_spread: bin_start is not 0 = b[0] <= ... <= b[%lld] = %lld", (long long)T,
+    return fail(INR_ERR_INVALID, "%s: bin_start is not 0 = b[0] <= ... <= b[%lld] = %lld", who, (long long)T,
                 (long long)M);
   return INR_OK;
 }
@@ -181,23 +183,21 @@ int inr_nufft_finish(const float* grid, const float* apod_y, const float* apod_x
   return hip_done(e, "inr_nufft_finish");
 }
 
-int inr_nufft_interp(const float* grid, const double* pos, int32_t C, int64_t H, int64_t W, int64_t M, float* out,
-                     float* scratch, int64_t scratch_floats, void* stream) {
-  const char* who = "inr_nufft_interp";
+static int nufft_interp(const char* who, bool plain, const float* grid, const double* pos, int32_t C, int64_t H, int64_t W,
+                        int64_t M, float* out, float* scratch, int64_t scratch_floats, void* stream) {
   if (int rc = null_check(who, {grid, pos, out, scratch})) return rc;
   if (int rc = nufft_check(C, H, W, M, who)) return rc;
   if (int rc = operands_check(who, {{out, (int64_t)C * M * 8, "out", 8}},
                               {{grid, (int64_t)C * H * W * 32, "grid", 16}, {pos, M * 16, "pos", 8}}, scratch,
                               scratch_floats, inr::nufft_scratch_floats(M)))
     return rc;
-  hipError_t e = inr::launch_nufft_interp(grid, pos, C, (int)H, (int)W, M, out, scratch, (hipStream_t)stream);
+  hipError_t e = inr::launch_nufft_interp(grid, pos, C, (int)H, (int)W, M, plain, out, scratch, (hipStream_t)stream);
   return hip_done(e, who);
 }
 
-int inr_nufft_spread(const float* val, const double* pos, const float* w, const int32_t* bin_start, const int32_t* order,
-                     int32_t C, int64_t H, int64_t W, int64_t M, float* grid, float* scratch, int64_t scratch_floats,
-                     void* stream) {
-  const char* who = "inr_nufft_spread";
+static int nufft_spread(const char* who, bool plain, const float* val, const double* pos, const float* w,
+                        const int32_t* bin_start, const int32_t* order, int32_t C, int64_t H, int64_t W, int64_t M,
+                        float* grid, float* scratch, int64_t scratch_floats, void* stream) {
   if (int rc = null_check(who, {val, pos, bin_start, order, grid, scratch})) return rc;
   if (int rc = nufft_check(C, H, W, M, who)) return rc;
   const int64_t T = inr::nufft_bin_count(H, W);
@@ -206,9 +206,71 @@ int inr_nufft_spread(const float* val, const double* pos, const float* w, const 
                                {bin_start, (T + 1) * 4, "bin_start", 4}, {order, M * 4, "order", 4}},
                               scratch, scratch_floats, inr::nufft_scratch_floats(M)))
     return rc;
-  if (int rc = nufft_bins_check(bin_start, T, M)) return rc;
-  hipError_t e = inr::launch_nufft_spread(val, pos, w, bin_start, order, C, (int)H, (int)W, M, grid, scratch,
+  if (int rc = nufft_bins_check(who, bin_start, T, M)) return rc;
+  hipError_t e = inr::launch_nufft_spread(val, pos, w, bin_start, order, C, (int)H, (int)W, M, plain, grid, scratch,
                                           (hipStream_t)stream);
+  return hip_done(e, who);
+}
+
+int inr_nufft_interp(const float* grid, const double* pos, int32_t C, int64_t H, int64_t W, int64_t M, float* out,
+                     float* scratch, int64_t scratch_floats, void* stream) {
+  return nufft_interp("inr_nufft_interp", false, grid, pos, C, H, W, M, out, scratch, scratch_floats, stream);
+}
+
+int inr_nufft_interp_plain(const float* grid, const double* pos, int32_t C, int64_t H, int64_t W, int64_t M, float* out,
+                           float* scratch, int64_t scratch_floats, void* stream) {
+  return nufft_interp("inr_nufft_interp_plain", true, grid, pos, C, H, W, M, out, scratch, scratch_floats, stream);
+}
+
+int inr_nufft_spread(const float* val, const double* pos, const float* w, const int32_t* bin_start, const int32_t* order,
+                     int32_t C, int64_t H, int64_t W, int64_t M, float* grid, float* scratch, int64_t scratch_floats,
+                     void* stream) {
+  return nufft_spread("inr_nufft_spread", false, val, pos, w, bin_start, order, C, H, W, M, grid, scratch, scratch_floats,
+                      stream);
+}
+
+int inr_nufft_spread_plain(const float* val, const double* pos, const float* w, const int32_t* bin_start,
+                           const int32_t* order, int32_t C, int64_t H, int64_t W, int64_t M, float* grid, float* scratch,
+                           int64_t scratch_floats, void* stream) {
+  return nufft_spread("inr_nufft_spread_plain", true, val, pos, w, bin_start, order, C, H, W, M, grid, scratch,
+                      scratch_floats, stream);
+}
+
+// ---- the coil product fused with prepare / finish on the plain-layout grid (inr_sense_nufft.hip) ----
+// img or dimg [H*W,2], maps [G,H*W,2], grid [G,2H,2W,2], the two apodisation vectors; `image_is_output`: finish
+static int sense_nufft_check(const char* who, const float* image, const char* image_name, const float* maps,
+                             const float* grid, const float* apod_y, const float* apod_x, int32_t G, int64_t H, int64_t W,
+                             float scale, bool image_is_output) {
+  if (int rc = null_check(who, {image, maps, grid, apod_y, apod_x})) return rc;
+  if (int rc = nufft_check(G, H, W, 1, who)) return rc;
+  if (!std::isfinite(scale)) return fail(INR_ERR_INVALID, "%s: scale = %g (must be finite)", who, (double)scale);
+  const int64_t plane = H * W * 8;
+  const Span im = {image, plane, image_name, 8}, mp = {maps, G * plane, "maps", 8}, gr = {grid, 4 * G * plane, "grid", 8};
+  const Span ay = {apod_y, H * 4, "apod_y", 4}, ax = {apod_x, W * 4, "apod_x", 4};
+  for (const Span& s : {im, mp, gr, ay, ax})
+    if (((uintptr_t)s.p & (s.align - 1)) != 0) return fail(INR_ERR_INVALID, "%s: %s is not %u-byte aligned", who, s.name, s.align);
+  const Span& out = image_is_output ? im : gr;
+  for (const Span& in : {image_is_output ? gr : im, mp, ay, ax})
+    if (int rc = overlap_check(who, out, in)) return rc;
+  return INR_OK;
+}
+
+int inr_sense_nufft_prepare(const float* img, const float* maps, const float* apod_y, const float* apod_x, int32_t G,
+                            int64_t H, int64_t W, float scale, float* grid, void* stream) {
+  const char* who = "inr_sense_nufft_prepare";
+  if (int rc = sense_nufft_check(who, img, "img", maps, grid, apod_y, apod_x, G, H, W, scale, false)) return rc;
+  hipError_t e = inr::launch_sense_nufft_prepare(img, maps, apod_y, apod_x, G, (int)H, (int)W, scale, grid,
+                                                 (hipStream_t)stream);
+  return hip_done(e, who);
+}
+
+int inr_sense_nufft_finish(const float* grid, const float* maps, const float* apod_y, const float* apod_x, int32_t G,
+                           int64_t H, int64_t W, float scale, float* dimg, int32_t accumulate, void* stream) {
+  const char* who = "inr_sense_nufft_finish";
+  if (int rc = sense_nufft_check(who, dimg, "dimg", maps, grid, apod_y, apod_x, G, H, W, scale, true)) return rc;
+  if (accumulate != 0 && accumulate != 1) return fail(INR_ERR_INVALID, "%s: accumulate = %d (0 or 1)", who, (int)accumulate);
+  hipError_t e = inr::launch_sense_nufft_finish(grid, maps, apod_y, apod_x, G, (int)H, (int)W, scale, dimg, accumulate != 0,
+                                                (hipStream_t)stream);
   return hip_done(e, who);
 }
 

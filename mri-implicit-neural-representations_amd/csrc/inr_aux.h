@@ -304,10 +304,21 @@ hipError_t launch_nufft_prepare(const float* img, const float* apod_y, const flo
                                 float* grid, hipStream_t st);
 hipError_t launch_nufft_finish(const float* grid, const float* apod_y, const float* apod_x, int C, int H, int W,
                                float* out, hipStream_t st);
-hipError_t launch_nufft_interp(const float* grid, const double* pos, int C, int H, int W, long long M, float* out,
-                               float* scratch, hipStream_t st);
+// `plain`: the grid is laid out as torch.fft reads and writes it -- the centred grid rolled by (H, W), so that cell
+// (jy, jx) lives at ((jy + H) mod 2H, (jx + W) mod 2W) and no shifted copy surrounds the caller's FFT
+hipError_t launch_nufft_interp(const float* grid, const double* pos, int C, int H, int W, long long M, bool plain,
+                               float* out, float* scratch, hipStream_t st);
 hipError_t launch_nufft_spread(const float* val, const double* pos, const float* w, const int* bin_start,
-                               const int* order, int C, int H, int W, long long M, float* grid, float* scratch,
+                               const int* order, int C, int H, int W, long long M, bool plain, float* grid, float* scratch,
                                hipStream_t st);
+// 2 / (a_y a_x): one product, one division, the doubling exact
+__device__ inline float deapodise(float ay, float ax) { return 2.0f / (ay * ax); }
+
+// off-grid SENSE fits on calibrated maps (inr_sense_nufft.hip): launch_sense_apply(shift 0) fused with
+// launch_nufft_prepare, and launch_nufft_finish fused with launch_sense_adjoint(shift 0), both on the plain-layout grid
+hipError_t launch_sense_nufft_prepare(const float* img, const float* maps, const float* apod_y, const float* apod_x, int G,
+                                      int H, int W, float scale, float* grid, hipStream_t st);
+hipError_t launch_sense_nufft_finish(const float* grid, const float* maps, const float* apod_y, const float* apod_x, int G,
+                                     int H, int W, float scale, float* dimg, bool accumulate, hipStream_t st);
 
 }  // namespace inr

@@ -15,6 +15,7 @@
 //   nufft_finish_kernel   the other way: the centre H x W of grid times 2 / (a_y[y] a_x[x]).
 //   nufft_interp_kernel   forward gather, a sample per lane: taps read once, then for every coil the 36 cells in the
 //                         order ky, kx.
+//   (interp and spread take the grid centred, or -- PLAIN, DESIGN.md 4.31 -- as a plain FFT lays it out)
 //   nufft_spread_kernel   the adjoint as a gather, no atomics: a workgroup owns a 16 x 16 tile of grid cells for up to
 //                         four coils, a thread one cell.  Samples come sorted into bins of 16 x 16 cells by the cell
 //                         that holds floor(g) (trajectory.nufft_bins: bin_start [T + 1], order [M]); the taps of such
@@ -98,9 +99,6 @@ __global__ __launch_bounds__(NF_THREADS) void nufft_taps_kernel(const double* __
   }
 }
 
-// 2 / (a_y a_x): one product, one division, the doubling exact
-__device__ inline float deapodise(float ay, float ax) { return 2.0f / (ay * ax); }
-
 __global__ __launch_bounds__(NF_THREADS) void nufft_prepare_kernel(const float* __restrict__ img,
                                                                     const float* __restrict__ apod_y,
                                                                     const float* __restrict__ apod_x, const int H,
@@ -150,6 +148,8 @@ __global__ __launch_bounds__(NF_THREADS) void nufft_finish_kernel(const float* _
   *reinterpret_cast<float2*>(out + 2 * (size_t)i) = make_float2(v.x * d, v.y * d);
 }
 
+// PLAIN (both kernels below): the grid in the layout of a plain FFT, the centred one rolled by (Gy / 2, Gx / 2)
+template <bool PLAIN>
 __global__ __launch_bounds__(NF_THREADS) void nufft_interp_kernel(const float* __restrict__ grid,
                                                                    const float* __restrict__ taps, const long long M,
                                                                    const long long Mp, const int C, const int Gy,
@@ -170,6 +170,10 @@ __global__ __launch_bounds__(NF_THREADS) void nufft_interp_kernel(const float* _
     y -= y >= Gy ? Gy : 0;
     x += x < 0 ? Gx : 0;
     x -= x >= Gx ? Gx : 0;
+    if constexpr (PLAIN) {
+      y += y < Gy / 2 ? Gy / 2 : -(Gy / 2);
+      x += x < Gx / 2 ? Gx / 2 : -(Gx / 2);
+    }
     rowy[k] = (size_t)y * Gx;
     colx[k] = x;
   }
@@ -211,6 +215,7 @@ __device__ inline int reach_bins(int tile, int G, int* list) {
   return n;
 }
 
+template <bool PLAIN>
 __global__ __launch_bounds__(NF_THREADS) void nufft_spread_kernel(const float* __restrict__ val,
                                                                    const float* __restrict__ w,
                                                                    const float* __restrict__ taps,
@@ -293,9 +298,11 @@ __global__ __launch_bounds__(NF_THREADS) void nufft_spread_kernel(const float* _
   }
   if (gy < Gy && gx < Gx) {
     const size_t plane = (size_t)Gy * Gx;
+    const int sy = PLAIN ? (gy < Gy / 2 ? gy + Gy / 2 : gy - Gy / 2) : gy;  // only the store address moves
+    const int sx = PLAIN ? (gx < Gx / 2 ? gx + Gx / 2 : gx - Gx / 2) : gx;
 #pragma unroll
     for (int cc = 0; cc < NF_CG; ++cc)
-      if (cc < nc) *reinterpret_cast<float2*>(grid + 2 * ((size_t)(c0 + cc) * plane + (size_t)gy * Gx + gx)) = acc[cc];
+      if (cc < nc) *reinterpret_cast<float2*>(grid + 2 * ((size_t)(c0 + cc) * plane + (size_t)sy * Gx + sx)) = acc[cc];
   }
 }
 
@@ -327,21 +334,23 @@ hipError_t launch_nufft_finish(const float* grid, const float* apod_y, const flo
   return hipGetLastError();
 }
 
-hipError_t launch_nufft_interp(const float* grid, const double* pos, int C, int H, int W, long long M, float* out,
-                               float* scratch, hipStream_t st) {
+hipError_t launch_nufft_interp(const float* grid, const double* pos, int C, int H, int W, long long M, bool plain,
+                               float* out, float* scratch, hipStream_t st) {
   launch_taps(pos, M, H, W, scratch, st);
-  hipLaunchKernelGGL(nufft_interp_kernel, dim3((unsigned)((M + NF_THREADS - 1) / NF_THREADS)), dim3(NF_THREADS), 0, st,
-                     grid, scratch, M, padded_samples(M), C, 2 * H, 2 * W, out);
+  hipLaunchKernelGGL(plain ? nufft_interp_kernel<true> : nufft_interp_kernel<false>,
+                     dim3((unsigned)((M + NF_THREADS - 1) / NF_THREADS)), dim3(NF_THREADS), 0, st, grid, scratch, M,
+                     padded_samples(M), C, 2 * H, 2 * W, out);
   return hipGetLastError();
 }
 
 hipError_t launch_nufft_spread(const float* val, const double* pos, const float* w, const int* bin_start,
-                               const int* order, int C, int H, int W, long long M, float* grid, float* scratch,
+                               const int* order, int C, int H, int W, long long M, bool plain, float* grid, float* scratch,
                                hipStream_t st) {
   launch_taps(pos, M, H, W, scratch, st);
   const unsigned tiles = (unsigned)nufft_bin_count(H, W);
-  hipLaunchKernelGGL(nufft_spread_kernel, dim3(tiles, (unsigned)((C + NF_CG - 1) / NF_CG)), dim3(NF_THREADS), 0, st, val,
-                     w, scratch, bin_start, order, M, padded_samples(M), C, 2 * H, 2 * W, grid);
+  hipLaunchKernelGGL(plain ? nufft_spread_kernel<true> : nufft_spread_kernel<false>,
+                     dim3(tiles, (unsigned)((C + NF_CG - 1) / NF_CG)), dim3(NF_THREADS), 0, st, val, w, scratch, bin_start,
+                     order, M, padded_samples(M), C, 2 * H, 2 * W, grid);
   return hipGetLastError();
 }
 

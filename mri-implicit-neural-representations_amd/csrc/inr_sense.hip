@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "inr_aux.h"
+#include "inr_sense_ops.h"
 #include "inr_sense_place.h"
 
 #pragma clang fp contract(off)
@@ -34,12 +35,7 @@ namespace inr {
 
 namespace {
 
-__device__ __forceinline__ void apply_one(float ir, float ii, float sr, float si, float scale, float& xr, float& xi) {
-  const float a = sr * ir, b = si * ii, c = sr * ii, e = si * ir;
-  const float re = a - b, im = c + e;
-  xr = scale * re, xi = scale * im;
-}
-
+// apply_one: inr_sense_ops.h
 __device__ __forceinline__ void grad_one(float ir, float ii, float sr, float si, float gr, float gi, float scale, float& dsr,
                                          float& dsi, float& dir, float& dii) {
   const float ur = scale * gr, ui = scale * gi;

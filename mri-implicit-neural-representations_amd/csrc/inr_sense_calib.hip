@@ -28,6 +28,7 @@
 #include <type_traits>
 #include "inr_aux.h"
 #include "inr_reduce.h"
+#include "inr_sense_ops.h"
 #include "inr_sense_place.h"
 
 #pragma clang fp contract(off)
@@ -128,14 +129,7 @@ __global__ __launch_bounds__(MP_THREADS) void sense_maps_kernel(const float2* __
   }
 }
 
-// sense_grad_kernel's dI half: the operations of grad_one that feed dir / dii, in its order
-__device__ __forceinline__ void adjoint_one(float sr, float si, float gr, float gi, float scale, float& dir, float& dii) {
-  const float ur = scale * gr, ui = scale * gi;
-  const float f = sr * ur, h = si * ui, k = sr * ui, l = si * ur;
-  const float tr = f + h, ti = k - l;
-  dir = dir + tr, dii = dii + ti;
-}
-
+// sense_grad_kernel's dI half: adjoint_one of inr_sense_ops.h
 template <bool PAIR>
 __global__ __launch_bounds__(SN_THREADS) void sense_adjoint_kernel(const float* __restrict__ sens,
                                                                    const float* __restrict__ gx, float* __restrict__ dimg,

@@ -173,6 +173,11 @@ SYMBOLS = {
     "inr_nufft_interp": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
     "inr_nufft_spread": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
     "inr_nufft_finish": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
+    "inr_nufft_interp_plain": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
+    "inr_nufft_spread_plain": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64,
+                                         _P]),
+    "inr_sense_nufft_prepare": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_float, _P, _P]),
+    "inr_sense_nufft_finish": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_float, _P, C.c_int32, _P]),
 }
 STEP_SPLIT_WORDS = 16  # INR_STEP_SPLIT_WORDS
 NUDFT_TILE = 64  # INR_NUDFT_TILE

@@ -40,6 +40,15 @@ returns data loss + weight * TV.  With learned maps and several coil groups per 
 prior with its full weight.  Records and metrics() gain a top-level ``prior`` {kind, weight, eps, value} (the value on
 the image of the prediction sweep); the validation's test loss stays data-only.  ``use_tv`` stays refused: it is the
 reference's TV of a coil's predicted k-space.  With the key absent nothing changes.
+
+``trajectory`` with ``sense.maps: calibrated`` (--trajectory, --trajectory-operator,
+--trajectory-density): the fit runs on off-grid samples.  The targets are the exact NUDFT samples [C, M, 2] of the scan;
+the maps are calibrated from those samples alone (density-weighted exact adjoint -> fft2c -> the usual block); a step is
+forward -> sense_nufft -> inr_loss_grad -> sense_nufft_adjoint -> prior -> backward -> Adam on all coils
+(sense_nufft.py).  ``trajectory_operator`` defaults to "gridding" HERE; "exact" runs the step from inr_sense_apply ->
+inr_nudft and inr_adjoint_nudft -> inr_sense_adjoint.  ``sense.baseline: cg-N`` is then non-Cartesian CG-SENSE.  Learned
+maps refuse a trajectory; with one, ``undersampling``, a mask, ``calib.acs``, ``trajectory_baseline`` and loss 'HDR'
+are refused.
 """
 from __future__ import annotations
 
@@ -194,6 +203,38 @@ def sens_net_params(settings: dict, encoder_config: dict) -> dict:
             "network_width": settings["net"]["network_width"]}
 
 
+def check_offgrid_sense_config(config: dict, mask=None) -> None:
+    """config['trajectory'] in a SENSE fit: built for calibrated maps only, and -- as INRTrainer's
+    off-grid fits -- with the trajectory as the only sampling.  Refused before any device call."""
+    t = config["trajectory"]
+    sense = config.get("sense")
+    if not isinstance(sense, dict) or sense.get("maps", "learned") != "calibrated":
+        raise NotImplementedError(f"config['trajectory'] = {t!r}: off-grid SENSE fits are built for sense.maps: calibrated "
+                                  "only (with learned maps the step's transform is a plain FFT)")
+    from .undersampling import parse_undersampling_argument
+    method, _ = parse_undersampling_argument(config.get("undersampling"))
+    if mask is not None or (method is not None and method.lower() != "none"):
+        raise ValueError(f"trajectory = {t!r} with an undersampling pattern or a mask: the trajectory IS the sampling")
+    if isinstance(sense.get("calib"), dict) and "acs" in sense["calib"]:
+        raise ValueError(f"trajectory = {t!r} with config['sense']['calib']['acs']: an off-grid acquisition has no "
+                         "Cartesian centre block to add; the maps are calibrated from the samples")
+    if config.get("loss") == "HDR":
+        raise NotImplementedError(f"trajectory = {t!r} with loss 'HDR': its scalar A over the off-grid rows is not built "
+                                  "for SENSE fits")
+    if config.get("trajectory_baseline") not in (None, "none"):
+        raise ValueError(f"trajectory = {t!r} with config['trajectory_baseline']: the conventional reconstruction of a "
+                         "SENSE fit is config['sense']['baseline'] = cg-N (non-Cartesian CG-SENSE)")
+
+
+def sense_operator(config: dict) -> Optional[str]:
+    """the operator pair of an off-grid SENSE step: None without a trajectory, else config['trajectory_operator'] with
+    "gridding" as the default (elsewhere the key belongs to a baseline and defaults to "exact")"""
+    from .trajectory import parse_operator
+    if config.get("trajectory") in (None, "none"):
+        return None
+    return parse_operator(config.get("trajectory_operator")) or "gridding"
+
+
 def check_sense_config(config: dict, world: int = 1, graph_steps: bool = False) -> None:
     """What a SENSE-model fit cannot be combined with -- refused before anything is allocated."""
     name = config["model"]
@@ -208,8 +249,7 @@ def check_sense_config(config: dict, world: int = 1, graph_steps: bool = False) 
         raise NotImplementedError("transform: true: a SENSE-model fit lives in image space already and is fitted to "
                                   "k-space data; image-space data have no sampling mask to profit from")
     if config["trajectory"] not in (None, "none"):
-        raise NotImplementedError(f"config['trajectory'] = {config['trajectory']!r}: off-grid SENSE fits are not built "
-                                  "(the step's transform is a plain FFT)")
+        check_offgrid_sense_config(config)
     if config.get("ring_normalization") not in (None, "none", False):
         raise NotImplementedError(f"config['ring_normalization'] = {config['ring_normalization']!r}: the targets of a "
                                   "SENSE-model fit stay in the data's units (the model is linear in image space)")
@@ -258,6 +298,9 @@ class SenseFitTrainer(ResidentFit):
         if coil_compression is not None:
             defaults["virtual_coils"] = defaults.get("virtual_coils") or coil_compression.coils_out
         check_sense_config(defaults, world, graph_steps)
+        self.operator = sense_operator(defaults)  # None: Cartesian; "gridding" | "exact": off-grid
+        if self.operator is not None:
+            check_offgrid_sense_config(defaults, mask)
         self.settings = sense_settings(defaults, C_)
         self.calib = maps_settings(defaults, H, W)  # None: learned maps
         self.prior = prior_settings(defaults)  # None: no prior on the image
@@ -268,12 +311,17 @@ class SenseFitTrainer(ResidentFit):
                 raise ValueError("config['encoder']['embedding_size'] (or config['sense']['encoder']['embedding_size'])")
             self.sens_params = sens_net_params(self.settings, defaults["encoder"])
             self._check_stash(G, H * W, emb == "gauss")
+        elif self.operator is not None:  # the trajectory is the sampling; the maps come from the samples (_ingest)
+            self.acceleration = 1.0
+            if G != C_:
+                raise ValueError(f"config['sense']['coils_per_step'] = {G}: an off-grid step takes all {C_} coils")
         else:  # the mask with the calibration block in it, formed up front and handed on as the explicit mask
             mask, self.acceleration = calibration_mask(self.calib["calib"], defaults["undersampling"], (C_, H, W), mask,
                                                        mask_seed)
         config = dict(config)
         config.setdefault("batch_size", H * W)  # the step's batches are coil groups; the key is read by the base only
-        config = self._init_fit(config, shape, device, seed, rank, world, process_group, False, None)
+        config = self._init_fit(config, shape, device, seed, rank, world, process_group, False, None,
+                                trajectory_ok=self.operator is not None, step_operator_ok=self.operator is not None)
         # encoder, image network, sensitivity encoder, sensitivity network: all on one CPU generator, in this order
         self._seeded_encoder(seed)
         model = MODELS[config["model"]](config["net"])
@@ -307,7 +355,7 @@ class SenseFitTrainer(ResidentFit):
         self.cg_sense = self._cg_image = self._cg_rss = None
         self._finish_init()
         if self.calib is not None and self.calib["baseline"] is not None:
-            self._cg_sense_baseline()
+            self._cg_sense_offgrid_baseline() if self.operator is not None else self._cg_sense_baseline()
 
     # ---- set-up ----------------------------------------------------------------------------------
     def _two_networks(self, model, config: dict) -> None:
@@ -333,6 +381,8 @@ class SenseFitTrainer(ResidentFit):
     def _ingest(self, C_: int, H: int, W: int) -> None:
         """Once: the inputs of both networks, the targets and the mask in ifftshift-ed row order per coil (what a plain
         fft2 of the product kernel's output is compared with), and the factor of the product."""
+        if self.operator is not None:
+            return self._ingest_offgrid(C_, H, W)
         perm = torch.from_numpy(shift_index(H, W)).to(self.device)
         self._gt_s = self.image.view(C_, self.plane, 2)[:, perm].contiguous().view(-1, 2)
         self._mask_s = None if self.mask is None else self.mask.view(C_, self.plane)[:, perm].contiguous().view(-1)
@@ -365,6 +415,79 @@ class SenseFitTrainer(ResidentFit):
             stats = torch.stack((self.sens_rss.min(), self.sens_rss.max(), self.sens_rss.double().mean().float()))
             self._rss_stats = dict(zip(("min", "max", "mean"), stats.cpu().tolist()))
 
+    @torch.no_grad()
+    def _ingest_offgrid(self, C_: int, H: int, W: int) -> None:
+        """Once, for an off-grid fit: the targets are the [C, M, 2] samples _resident_data took (the exact
+        NUDFT of the coil images).  Everything else comes from those samples alone: their density-weighted exact adjoint
+        gives coil images whose largest RSS is the default factor (the weights sum to H W: no acceleration factor) and
+        whose centred k-space gives the calibration block; from the block on, the Cartesian path's calibrate()."""
+        from .evalchain import fft2c
+        from .sense_calib import calibrate, cut_block
+        from .sense_nufft import SenseNufft
+        from .trajectory import (adjoint_scratch_floats, nudft_adjoint, parse_density, positions, scratch_floats,
+                                 _device_positions)
+        self.plane = H * W
+        self._gt_s = self._mask_s = None
+        self._pos = positions(self.trajectory, H, W)
+        self.M = int(self._pos.shape[0])
+        self._gt = self._train_values_data  # [(C*M), 2]
+        self.density_name, w = parse_density(self.config["trajectory_density"], self.trajectory, H, W)
+        self._img_coords = self.coords[:self.plane].clone()
+        self._img_coords[:, 0] = 0.0
+        self._img_in = _encoded(self.encoder, self.enc_B, self._img_coords)
+        back = nudft_adjoint(self._gt.view(C_, self.M, 2), self._pos, (H, W), w)  # [C,H,W,2]
+        self.sense_scale = self.settings["scale"]
+        if self.sense_scale is None:
+            self.sense_scale = float(torch.sqrt((back.double() ** 2).sum(dim=(0, 3)).max()))
+            if not math.isfinite(self.sense_scale):
+                raise ValueError(f"the largest RSS of the adjoint coil images is {self.sense_scale}")
+            if self.sense_scale == 0.0:
+                self.sense_scale = 1.0
+        c = self.calib["calib"]
+        self._block = torch.from_numpy(cut_block(fft2c(back), *c["size"], c["window"])).to(self.device)
+        self._maps, self.sens_rss = calibrate(self._block, H, W, c["floor"])
+        self._maps_rows = self._maps.view(-1, 2)
+        self._x = torch.empty(C_, H, W, 2, device=self.device)  # the prediction sweep's coil images; the exact step's
+        self._dimg = torch.empty(self.plane, 2, device=self.device)
+        stats = torch.stack((self.sens_rss.min(), self.sens_rss.max(), self.sens_rss.double().mean().float()))
+        self._rss_stats = dict(zip(("min", "max", "mean"), stats.cpu().tolist()))
+        self._op = None  # the fused pair's buffers: the gridding step's, and the CG baseline's under either operator
+        if self.operator == "gridding" or self.calib["baseline"] is not None:
+            self._op = SenseNufft(self._maps, self._pos, (C_, H, W), self.sense_scale, w)
+        if self.operator == "exact":
+            self._pos_dev = _device_positions(self._pos, self.device)
+            self._scratch_fwd = torch.empty(scratch_floats(C_, H, W, self.M), device=self.device)
+            self._scratch_adj = torch.empty(adjoint_scratch_floats(C_, H, W, self.M), device=self.device)
+            self._gx = torch.empty(C_, H, W, 2, device=self.device)
+
+    def _step_offgrid(self, epoch: int) -> torch.Tensor:
+        """forward -> E -> inr_loss_grad on [G*M, 2] -> E^H -> prior -> backward -> Adam, all coils.  E is the fused
+        gridding pair (sense_nufft.py), or under trajectory_operator: exact the existing kernels alone --
+        inr_sense_apply(shift 0) -> inr_nudft and inr_adjoint_nudft -> inr_sense_adjoint(shift 0): slow, and the yardstick."""
+        C_, H, W = (int(v) for v in self.shape[:3])
+        cfg, lr = self.config, self._lr(epoch)
+        ib = self.engine.forward(self._img_in, self.enc_B, save=True)
+        if self.operator == "gridding":
+            k = self._op.forward(ib)
+        else:
+            from .trajectory import nudft
+            x = sense_apply(ib, self._maps_rows, C_, H, W, self.sense_scale, 0, out=self._x)
+            k = nudft(x, self._pos_dev, scratch=self._scratch_fwd)
+        loss, gk = self.engine.loss_grad(self.loss, k.view(-1, 2), self._gt, C_ * self.M)
+        if self.operator == "gridding":
+            dimg = self._op.adjoint(gk.view(C_, self.M, 2), dimg=self._dimg)
+        else:
+            from .sense_calib import sense_adjoint
+            from .trajectory import nudft_adjoint
+            gx = nudft_adjoint(gk.view(C_, self.M, 2), self._pos_dev, (H, W), None, scratch=self._scratch_adj, out=self._gx)
+            dimg = sense_adjoint(self._maps_rows, gx, C_, H, W, self.sense_scale, 0, dimg=self._dimg)
+        if self.prior is not None:
+            loss = loss + self._add_prior(ib, dimg, H, W)
+        self.engine.backward(self._img_in, self.enc_B, dimg)
+        self.engine.adam_step(lr, cfg["beta1"], cfg["beta2"], 1e-8, cfg["weight_decay"])
+        self.global_step += 1
+        return loss
+
     def _sens_in(self, lo: int, hi: int) -> torch.Tensor:
         return _encoded(self.sens_encoder, self.sens_enc_B, self.coords[lo:hi])
 
@@ -377,6 +500,8 @@ class SenseFitTrainer(ResidentFit):
         return parts
 
     def step(self, epoch: int, it: int) -> torch.Tensor:
+        if self.operator is not None:
+            return self._step_offgrid(epoch)
         if self._coil_order is not None:
             it = self._coil_order.at(epoch, it)
         c0, c1 = self.groups[it]
@@ -474,13 +599,17 @@ class SenseFitTrainer(ResidentFit):
     @property
     def sense_summary(self) -> Optional[dict]:
         """{'coils_per_step', 'scale', 'net': {'width', 'depth'}, 'sens_rss': {'min', 'max', 'mean'}} of the last sweep
-        (None before the first)"""
-        return self._last_sense
+        (None before the first).  Off-grid fits add which pair the step runs and where the block came
+        from: 'operator', and 'calib' with source "samples" and the density's name in place of 'acs' / 'acceleration'."""
+        if self.operator is None or self._last_sense is None:
+            return self._last_sense
+        calib = {k: v for k, v in self.calib["calib"].items() if k != "acs"}
+        return dict(self._last_sense, operator=self.operator, calib=dict(calib, source="samples", density=self.density_name))
 
     @torch.no_grad()
     def validate(self, epoch: int) -> dict:
         rec = self._validated(epoch, self._predict_raw())
-        rec["sense"] = self._last_sense
+        rec["sense"] = self.sense_summary
         if self.prior is not None:
             rec["prior"] = self._last_prior
         if self.cg_sense is not None:
@@ -490,7 +619,7 @@ class SenseFitTrainer(ResidentFit):
     @torch.no_grad()
     def metrics(self) -> dict:
         rec = super().metrics()
-        rec["sense"] = self._last_sense
+        rec["sense"] = self.sense_summary
         if self.prior is not None:
             rec["prior"] = self._last_prior
         if self.cg_sense is not None:
@@ -523,6 +652,33 @@ class SenseFitTrainer(ResidentFit):
         psnr_, ssim_ = m[:2].cpu().tolist()
         self.cg_sense = {"iters": iters, "lambda": lam, "psnr": psnr_, "ssim": ssim_,
                          "objective": [float(v) for v in objective], "seconds": seconds}
+
+    @torch.no_grad()
+    def _cg_sense_offgrid_baseline(self) -> None:
+        """config['sense']['baseline'] = cg-N of an off-grid fit: non-Cartesian CG-SENSE (Pruessmann 2001),
+        N iterations on (E^H W E + lambda) x = E^H W y with E the fused gridding pair at scale 1 and W the density weights
+        (sense_nufft.cg_sense_offgrid), from the fit's own maps and samples; scored and kept as the Cartesian baseline is."""
+        import time
+        from .evalchain import image_metrics
+        from .sense_calib import kspace_of
+        from .sense_nufft import cg_sense_offgrid
+        from .validation import coil_images
+        iters, lam = self.calib["baseline"], self.calib["cg_lambda"]
+        C_ = int(self.shape[0])
+        torch.cuda.synchronize(self.device)
+        t0 = time.time()
+        iterates, objective = cg_sense_offgrid(self._op, self._gt.view(C_, self.M, 2), iters, lam)
+        self._cg_image = iterates[-1].contiguous()
+        torch.cuda.synchronize(self.device)
+        seconds = time.time() - t0
+        pred = kspace_of(self._cg_image, self._maps, self.shape)
+        if self._ref_rss is None:
+            self._ref_rss = image_metrics(None, coil_images(self.image_full, self.shape, self.in_image_space))[0]
+        self._cg_rss, m = image_metrics(self._ref_rss, coil_images(pred, self.shape, self.in_image_space))[:2]
+        psnr_, ssim_ = m[:2].cpu().tolist()
+        self.cg_sense = {"iters": iters, "lambda": lam, "psnr": psnr_, "ssim": ssim_,
+                         "objective": [float(v) for v in objective], "seconds": seconds, "operator": "gridding",
+                         "density": self.density_name}
 
     @torch.no_grad()
     def save_cg_sense_image(self, directory: str, prefix: str = "") -> str:

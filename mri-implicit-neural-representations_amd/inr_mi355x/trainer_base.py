@@ -123,7 +123,7 @@ class ResidentFit(ValidationMixin):
     # ---- set-up ----------------------------------------------------------------------------------
     def _init_fit(self, config: dict, shape, device, seed: int, rank: int, world: int, process_group,
                   graph_steps: bool = False, coil_compression=None, trajectory_ok: bool = False,
-                  ring_norm_ok: bool = False, row_sampling_ok: bool = False) -> dict:
+                  ring_norm_ok: bool = False, row_sampling_ok: bool = False, step_operator_ok: bool = False) -> dict:
         """Defaults, the shuffle settings (which refuse shuffle with graph steps before anything is allocated), the coil
         compression the data came through (config['virtual_coils'] = K needs the record of a K-coil compression and
         K-coil data, and the other way round: ValueError before anything is allocated), the trajectory of an off-grid fit
@@ -154,10 +154,11 @@ class ResidentFit(ValidationMixin):
             raise ValueError(f"config['trajectory_baseline'] = {config['trajectory_baseline']!r} / ['trajectory_density'] = "
                              f"{config['trajectory_density']!r} without config['trajectory']: there are no off-grid "
                              "samples to reconstruct")
-        # config['trajectory_operator'] belongs to the baseline; the training samples stay exact
+        # config['trajectory_operator'] belongs to the baseline; the training samples stay exact.  A driver
+        # whose STEP runs the operator pair (off-grid SENSE fits) passes ``step_operator_ok``
         from .trajectory import parse_operator
         self.trajectory_operator = parse_operator(config["trajectory_operator"])
-        if self.trajectory_operator is not None and self.trajectory_baseline is None:
+        if self.trajectory_operator is not None and self.trajectory_baseline is None and not step_operator_ok:
             raise ValueError(f"config['trajectory_operator'] = {config['trajectory_operator']!r} without "
                              "config['trajectory_baseline']: it selects the operator inside the baseline only")
         if self.trajectory is not None and (self.trajectory_baseline is not None or config["trajectory_density"] is not None):

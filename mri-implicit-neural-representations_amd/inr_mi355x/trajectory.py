@@ -757,8 +757,9 @@ def add_baseline_flags(ap) -> None:
                     help="the baseline's density compensation: ramp (spokes), uniform or a .npy file of [M] positive "
                          "float64 (config['trajectory_density']; default: ramp for spokes, uniform for a file)")
     ap.add_argument("--trajectory-operator", type=str, default=None, metavar="ARG",
-                    help="the operator pair inside the baseline: exact (inr_nudft and its adjoint) or gridding "
-                         "(Kaiser-Bessel gridding around an FFT) (config['trajectory_operator']; default: exact)")
+                    help="the operator pair inside the baseline -- in train_sense, of the off-grid step itself: exact "
+                         "(inr_nudft and its adjoint) or gridding (Kaiser-Bessel gridding around an FFT) "
+                         "(config['trajectory_operator']; default: exact, in train_sense gridding)")
 
 
 def apply_baseline_flags(config: dict, opts) -> dict:
